@@ -9,6 +9,11 @@ Workload at N=1 = BASELINE.json configs[1]: LineMOD 13-class training, batch 8, 
 BGR means; targets: the HIP target-assignment kernel on seeded synthetic annotations).  N > 1 is weak
 scaling: batch 8 per GPU, gradient all-reduce over RCCL (pyrapose_amd/parallel.py).
 
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`).  `--dump-outputs DIR` also
+writes what the last timed step computed (dump_outputs).  Everything else -- `roofline`, `other_mode`, `sparse_backward`,
+`value_dense_backward`, `cpu_baseline`, `inference`, `p16_audit`, `--dump-ops` -- is measured with `--full` only, and is null
+in a plain line.
+
 `roofline`: the dominant kernel family is the implicit-GEMM MFMA convolution; every launch of it is
 bracketed with HIP events inside the timed region (torch.cuda.Event on the ctx stream, which IS the
 stream the kernels are launched on) and achieved = sum(algorithmic 2*MAC flops) / sum(durations).
@@ -50,6 +55,23 @@ DTYPE_NOTES = {
 EVENT_EVERY = 4  # per-launch HIP events on steps 0, 4, 8, ... of the timed region
 P16_AUDIT = {}           # Engine.p16_stats() of the most recent run() (rank 0)
 P16_AUDIT_HEADLINE = {}  # ... of the headline run
+
+LOSS_KEYS = ("3Dbox", "cls", "mask", "l2", "total")
+DUMP_WEIGHTS = 1 << 22  # trainable weights in weights.npy: 16 MB of the 169 MB of config 1 (42.2 M)
+
+
+def dump_outputs(path, eng, losses):
+    """--dump-outputs: what a caller of the timed path (Keras train_on_batch) holds after its last step.  losses.npy: float64
+    [3Dbox, cls, mask, l2, total]; weights.npy: float32, the updated trainable weights concatenated in Keras layout and
+    graph order (ParamStore.export_trainable), or a fixed sample of DUMP_WEIGHTS of them (seed 0, ascending indices) when
+    there are more.  Inputs and initial weights are seeded, so two builds run with the same arguments compare file by file."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "losses.npy"), np.array([losses[k] for k in LOSS_KEYS], np.float64))
+    torch.cuda.synchronize()
+    flat = np.concatenate([a.ravel() for a in eng.params.export_trainable(eng.params.w_master).values()])
+    if flat.size > DUMP_WEIGHTS:
+        flat = flat[np.sort(np.random.default_rng(0).choice(flat.size, DUMP_WEIGHTS, replace=False))]
+    np.save(os.path.join(path, "weights.npy"), flat.astype(np.float32))
 
 
 def measured_peak(mode, achieved):  # achieved: MFMA-unit TFLOP/s (executed flops x units per product)
@@ -340,15 +362,26 @@ def parse_args(argv=None):
                          "`value` depend on the annotation density: LineMOD has 1 object per image, YCB-V / T-LESS 5-15")
     ap.add_argument("--rank-timeout", type=float, default=DEFAULT_RANK_TIMEOUT_S,
                     help="--gpus N without a launcher: seconds after which ranks that have not exited are terminated (0 = none)")
-    ap.add_argument("--no-alt-mode", action="store_true", help="skip the short run of the other conv mode")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: per-launch events + roofline (--no-kernel-events, --dump-ops), the other "
+                         "arithmetics (--no-alt-mode), the dense-backward and sparse-forward steps, the CPU baseline (--no-cpu-baseline), "
+                         "the inference leg (--no-inference) and the P16 audit")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/losses.npy and DIR/weights.npy (dump_outputs)")
+    ap.add_argument("--no-alt-mode", action="store_true", help="--full: skip the short run of the other conv mode")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true")
-    ap.add_argument("--dump-ops", default=None, help="write a per-launch table (name, kind, GFLOP, avg us, TFLOP/s)")
-    ap.add_argument("--no-inference", action="store_true", help="skip the config-3 inference leg (B=32, C=8)")
+    ap.add_argument("--dump-ops", default=None, help="--full: write a per-launch table (name, kind, GFLOP, avg us, TFLOP/s)")
+    ap.add_argument("--no-inference", action="store_true", help="--full: skip the config-3 inference leg (B=32, C=8)")
     ap.add_argument("--no-prefetch", action="store_true",
                     help="with PP_PREFETCH=1 (engine built with a prefix lane): do not use the look-ahead -- the frozen prefix (conv1 + res2) "
                          "of a batch runs inside its own step instead of beside the previous one.  Without PP_PREFETCH=1 (default) there is no look-ahead.")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_ops and not args.full:
+        ap.error("--dump-ops reads the per-launch events of --full")
+    return args
 
 
 def main():
@@ -429,8 +462,9 @@ def main_worker(args):
 
     pf_flags = []  # per run(): did the steps use the look-ahead?
 
-    def run(mode, steps, warmup, events, dump_ops=None, sparse=None, sparse_fwd=False):
-        """Build an engine in `mode`, run warmup + timed steps, return (dt, images, losses, roofline dict)."""
+    def run(mode, steps, warmup, events, dump_ops=None, sparse=None, sparse_fwd=False, dump_dir=None):
+        """Build an engine in `mode`, run warmup + timed steps, return (dt, images, losses, roofline dict).
+        dump_dir: write the last step's outputs there (dump_outputs, rank 0)."""
         if sparse is not None:
             os.environ["PP_SPARSE_BWD"] = sparse
         if sparse_fwd:
@@ -493,8 +527,10 @@ def main_worker(args):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
         losses = eng.losses()
+        if dump_dir and rank == 0:
+            dump_outputs(dump_dir, eng, losses)
         roof = None
-        sp_frac = sparse_fractions(eng) if rank == 0 else {}
+        sp_frac = sparse_fractions(eng) if (rank == 0 and args.full) else {}
         if records and rank == 0:
             # Launches of independent chains run on different lanes (streams) and overlap, so the family rate is
             # algorithmic flops / length of the UNION of the launch intervals (time during which >= 1 conv kernel
@@ -559,7 +595,7 @@ def main_worker(args):
             roof = {"sparse": sp_frac}
         # the P16 tensors of the last step (outside the timed region): nothing at the encode's clamp, largest |half| per group
         # (Engine.p16_stats / pp_planes_stats: the format saturates and underflows silently, this is where it would show)
-        if rank == 0 and mode_used in ("mixed", "f16c8"):
+        if rank == 0 and args.full and mode_used in ("mixed", "f16c8"):
             try:
                 P16_AUDIT.clear()
                 P16_AUDIT.update(eng.p16_stats())
@@ -569,7 +605,8 @@ def main_worker(args):
         torch.cuda.empty_cache()
         return dt, steps * B * world, losses, roof, mode_used
 
-    dt, images_total, losses, roof, mode = run(args.conv_mode, args.steps, args.warmup, not args.no_kernel_events, args.dump_ops)
+    dt, images_total, losses, roof, mode = run(args.conv_mode, args.steps, args.warmup, args.full and not args.no_kernel_events, args.dump_ops,
+                                               dump_dir=args.dump_outputs)
     P16_AUDIT_HEADLINE.update(P16_AUDIT)
     prefetch_used = pf_flags[0]
 
@@ -636,7 +673,7 @@ def main_worker(args):
                     "per_kernel": roof["per_kernel"]}
 
     other = None
-    if world == 1 and not args.no_alt_mode:
+    if world == 1 and args.full and not args.no_alt_mode:
         # the other arithmetics on the same box, same process (short runs): the exact f32 MFMA path, and -- when the step ran mixed --
         # the all-bf16x3 step it replaced (3 MFMA units per product everywhere)
         other = []
@@ -671,16 +708,16 @@ def main_worker(args):
                     sparse["sparse_forward_opt_in"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(weights, x, anns, (y_box, y_cls, y_mask), C, H, W)
 
     inference = None
-    if world == 1 and not args.no_inference:
+    if world == 1 and args.full and not args.no_inference:
         inference = inference_leg(ctx, mode)
 
     out = {
         "metric": "images/sec 640x480 fwd+bwd (train step: fwd + losses + bwd + clipnorm-Adam)",
-        "value": value, "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "value": value, "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
         "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "rccl_ranks": (world if backend == "nccl" else 0), "dist_backend": backend,
         "value_dense_backward": ((sparse or {}).get("dense_backward") or {}).get("value"),

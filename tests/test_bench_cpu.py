@@ -85,6 +85,15 @@ def test_spawn_has_a_default_timeout():
     assert bench.parse_args(["--gpus", "2", "--rank-timeout", "60"]).rank_timeout == 60.0
 
 
+def test_full_is_opt_in_and_steps_are_checked():
+    a = bench.parse_args(["--steps", "7", "--warmup", "2", "--dump-outputs", "d"])
+    assert (a.full, a.steps, a.warmup, a.dump_outputs) == (False, 7, 2, "d")
+    assert bench.parse_args(["--full", "--dump-ops", "ops.csv"]).full
+    for bad in (["--dump-ops", "ops.csv"], ["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
 def test_spawn_rejects_a_line_with_another_world_size(tmp_path, capsys):
     rc, io = _run(tmp_path, "lie", 2, capsys)
     assert rc != 0 and io.out.strip() == ""

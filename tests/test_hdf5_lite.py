@@ -84,23 +84,15 @@ def test_other_dtypes_and_big_endian_and_refusals(tmp_path):
         H5.File(bad)
 
 
-def _matlab_hdf5_file():
-    import os
-    try:
-        import scipy
-    except ImportError:
-        return None
-    p = os.path.join(os.path.dirname(scipy.__file__), "io", "matlab", "tests", "data", "testhdf5_7.4_GLNX86.mat")
-    return p if os.path.exists(p) else None
-
-
-@pytest.mark.skipif(_matlab_hdf5_file() is None, reason="scipy's testhdf5_7.4_GLNX86.mat is not installed")
 def test_reads_a_file_written_by_libhdf5_behind_a_user_block():
-    """Third-party evidence for the reader: the one libhdf5-written file of this image.  MATLAB 7.4 '-v7.3' = HDF5 1.6 behind a
-    512-byte user block.  Its content is MATLAB's `testdouble` variable, which scipy documents as
+    """Third-party evidence for the reader: a libhdf5-written file, tests/golden/testhdf5_7.4_GLNX86.mat -- scipy's test file
+    scipy/io/matlab/tests/data/testhdf5_7.4_GLNX86.mat (BSD-3-Clause; Copyright (c) 2001-2002 Enthought, Inc.,
+    2003-2024 SciPy Developers), stored unchanged.  MATLAB 7.4 '-v7.3' = HDF5 1.6 behind a 512-byte user block.  Its content
+    is MATLAB's `testdouble` variable, which scipy documents as
     theta = pi/4 * arange(9) (scipy/io/matlab/tests/test_mio.py: `theta`, case_table4 'double'; class 'double'), stored
     column-major, i.e. as a (9, 1) HDF5 dataset."""
-    path = _matlab_hdf5_file()
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "testhdf5_7.4_GLNX86.mat")
     with open(path, "rb") as fh:
         raw = fh.read()
     assert raw[:6] == b"MATLAB" and H5.find_superblock(raw) == 512           # user block first, superblock at the second probe offset

@@ -6,7 +6,7 @@ mkdir -p "$(dirname "$out")"
 for rep in 1 2; do
   for e in "$@"; do
     echo "== rep $rep $e" >> $out
-    env $e timeout -k 10 500 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-inference --no-alt-mode 2>>$out.err | tail -1 | python -c "
+    env $e timeout -k 10 500 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-inference --no-alt-mode 2>>$out.err | tail -1 | python -c "
 import json,sys
 r=json.loads(sys.stdin.read())
 sb=r.get('sparse_backward') or {}

@@ -6,7 +6,7 @@ mkdir -p $out
 for i in $(seq 1 $n); do
   for tag in A B; do
     if [ $tag = A ]; then e="$a"; else e="$b"; fi
-    env $e python bench.py --no-cpu-baseline --no-inference --no-alt-mode --steps 20 --warmup 5 > $out/ab_${tag}_$i.json 2>/dev/null || exit 1
+    env $e python bench.py --full --no-cpu-baseline --no-inference --no-alt-mode --steps 20 --warmup 5 > $out/ab_${tag}_$i.json 2>/dev/null || exit 1
     python - <<PY
 import json
 d = json.load(open("$out/ab_${tag}_$i.json"))

@@ -3,7 +3,7 @@
 out=${1:-gpurun_out/density_sweep.jsonl}
 : > $out
 for k in 1 3 8 15; do
-  timeout -k 10 400 python bench.py --steps 20 --warmup 3 --boxes-per-image $k --no-cpu-baseline --no-inference 2>gpurun_out/density_$k.err | tail -1 >> $out || exit 1
+  timeout -k 10 400 python bench.py --full --steps 20 --warmup 3 --boxes-per-image $k --no-cpu-baseline --no-inference 2>"${out%.jsonl}_$k.err" | tail -1 >> $out || exit 1
   echo "K=$k done"
 done
 python - <<'PY'
