@@ -425,6 +425,36 @@ int pp_pose_add_f64(pp_ctx* ctx, int n_pose, int n_pts, const double* pts, const
 int pp_pose_adi_f64(pp_ctx* ctx, int n_pose, int n_pts, const double* pts, const double* R_est, const double* t_est,
                     const double* R_gt, const double* t_gt, void* workspace, double* out);
 
+/* ---- depth renderer and the VSD / reprojection pose errors (tless_eval.py:470-471, 651-662) -------------------------
+ * Depth pass of utils/hodan_renderer.py (mode='depth', :121-143, :185-225, :548-553) as called by pose_error.py:124-128:
+ * n_pose poses of ONE mesh, verts [n_vert,3] float64 (model units, the unit of t and of the output depth), faces [n_tri,3]
+ * int32 (indices out of range skip the triangle), R row-major [n_pose,3,3], t [n_pose,3], K4 [n_pose,4] = (fx, fy, cx, cy)
+ * float64 (skew ignored).  Out depth [n_pose,height,width] float32: camera-frame Z of the nearest surface point, interpolated
+ * perspective-correctly, at pixel (r, c) sampled at (u, v) = (c + 0.5, r + 0.5); 0 = empty; fragments with Z outside
+ * [clip_near, clip_far] dropped.  Deviations: a triangle with a vertex at Z <= 0 is skipped (not clipped); pixel centres on an
+ * edge follow the top-left rule.  Bit-identical run to run.  workspace_bytes >= pp_render_workspace_bytes (0: bad shape). */
+size_t pp_render_workspace_bytes(int n_pose, int n_vert, int n_tri, int width, int height);
+int pp_render_depth_f32(pp_ctx* ctx, int n_pose, int n_vert, const double* verts, int n_tri, const int* faces, const double* R,
+                        const double* t, const double* K4, int width, int height, double clip_near, double clip_far, void* workspace,
+                        size_t workspace_bytes, float* depth);
+/* vsd() of pose_error.py:105-176 (with depth_im_to_dist_im :43-61 and the visibility masks :15-40) on rendered depth images:
+ * n problems, depth_est / depth_gt [n,height,width] float32, depth_test float32 (uint16 sensor depth converts exactly) at
+ * depth_test + i * test_stride (0: one scene depth shared by all problems, or width * height), K4 [n,4] = (fx, fy, cx, cy)
+ * float64, delta (visibility tolerance, compared in float32 as there) and tau (misalignment tolerance) in depth units,
+ * cost_type 0 = 'step' (cost = |d_gt - d_est| >= tau), 1 = 'tlinear' (min(|d_gt - d_est| / tau, 1)).
+ * Out e [n] float64 (1.0 when the union is empty), and, when not null, the intersection / union pixel counts [n] int64.
+ * Fixed-order reductions.  workspace >= pp_vsd_workspace_bytes. */
+size_t pp_vsd_workspace_bytes(int n, int width, int height);
+int pp_vsd_f64(pp_ctx* ctx, int n, int width, int height, const float* depth_test, long long test_stride, const float* depth_est,
+               const float* depth_gt, const double* K4, double delta, double tau, int cost_type, void* workspace, double* e,
+               long long* inter, long long* uni);
+/* reproj() of pose_error.py:179-207: mean over pts [n_pts,3] of the distance in pixels between K (R_est p + t_est) and
+ * K (R_gt p + t_gt), each projection rounded to float32 and the norm taken in float32 as there (the mean is summed in float64:
+ * within 1e-5 relative of the reference's float32 mean).  K9 [n_pose,3,3] row-major float64, the rest as pp_pose_add_f64;
+ * out [n_pose] pixels.  workspace >= pp_pose_error_workspace_bytes(n_pose, n_pts). */
+int pp_pose_reproj_f64(pp_ctx* ctx, int n_pose, int n_pts, const double* pts, const double* K9, const double* R_est,
+                       const double* t_est, const double* R_gt, const double* t_gt, void* workspace, double* out);
+
 /* ---- RANSAC-PnP of the evaluation tail ----------------------------------------------------------------
  * In place of cv2.solvePnPRansac(obj_points, est_points, K, None, iterationsCount=300, reprojectionError=5.0,
  * confidence=0.99, flags=cv2.SOLVEPNP_ITERATIVE) + cv2.Rodrigues at utils/linemod_eval.py:479-485 (same call in the

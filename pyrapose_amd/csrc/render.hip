@@ -1,0 +1,535 @@
+// Depth renderer and the VSD / reprojection pose errors of the evaluation tail (tless_eval.py:470-471, 651-662 and the
+// same calls in occlusion_eval.py / ycbv_eval.py / homebrewed_eval.py / linemod_eval.py).
+//
+// Renderer: the depth pass of utils/hodan_renderer.py (mode='depth'), which the reference's vsd() (utils/pose_error.py:105-176)
+// calls twice per detection.  Per pixel the value is the eye depth Z (camera-frame z of the nearest surface point,
+// hodan_renderer.py:121-143), interpolated perspective-correctly (Z = 1 / sum_i b_i / Z_i, b_i screen-space barycentrics),
+// 0 where nothing is drawn.  With the projection of _calc_calib_proj(..., 'y_down') (:185-225) window x = fx X/Z + cx and
+// window y = h - (fy Y/Z + cy); GL samples pixel centres at window (j + 0.5) and _draw_depth flips the rows (:548-553), so
+// image pixel (row r, column c) samples (u, v) = (c + 0.5, r + 0.5) in OpenCV pixel coordinates.  Fragments with Z outside
+// [clip_near, clip_far] are dropped.  Skew is ignored (the reference's K has none).
+// Deviations: a triangle with a vertex at Z <= 0 (or projecting to a non-finite point) is skipped, not clipped; a pixel centre
+// exactly on an edge belongs to the triangle only if the edge is a top or left edge (edge functions are evaluated in one
+// canonical direction per edge, so a shared edge gives exactly opposite values and is drawn exactly once).
+//
+// Passes, one set of launches for n poses of one mesh:
+//   1. vertex:  R p + t in float64 per (pose, vertex) -> float32 screen x / y and float64 1/Z
+//   2. count:   per (pose, triangle) the 32x32-pixel screen tiles its pixel bounding box touches; a triangle on at most 4 tiles
+//               adds one entry per tile to that (pose, tile)'s list, a larger one goes to the pose's list of big triangles
+//   3. scan:    exclusive prefix sum of the per-(pose, tile) counts
+//   4. scatter: fill the lists (arrival order -- the result does not depend on it, see below)
+//   5. raster:  one workgroup per (pose, tile): the tile's z-buffer in LDS, min with LDS integer atomics on the bits of positive
+//               float32 depths (which order like the floats), one vectorised store of the tile.  A triangle whose box covers
+//               more than RASTER_SMALL_PX pixels of the tile, and every big triangle, is spread over the whole workgroup.
+// Every fragment's depth is a pure function of (triangle, pixel) and the z-buffer keeps the minimum, so the image is the same
+// bits whatever order the lists and the atomics run in.
+//
+// VSD: pose_error.py:15-61 + 105-176 per problem on the rendered depth images, float64 where the reference is; per-block
+// partial counts / sums, then one ordered pass per problem.  reproj: pose_error.py:179-207 like pose.hip's ADD.
+// Compiled with -ffp-contract=off: the host restatements (tests/render_np.py, utils/pose_error.py) evaluate the same
+// expressions in the same order.
+#include <math.h>
+#include "pp_internal.h"
+
+#define RT 32                  // screen tile edge (pixels)
+#define RASTER_THREADS 256
+#define RASTER_SMALL_PX 64     // larger per-tile boxes are rasterised by the whole workgroup
+#define BIN_MAX_TILES 4        // triangles on more tiles go to the pose's big list
+#define VSD_THREADS 256
+#define VSD_PER_THREAD 4
+#define VSD_BLOCK (VSD_THREADS * VSD_PER_THREAD)
+#define REPROJ_TILE 256
+
+struct __align__(16) rvtx {
+  float x, y;   // screen position (OpenCV pixel coordinates)
+  double iz;    // 1 / Z, 0 when Z <= 0 or the projection is not finite
+};
+
+__global__ void render_vertex_kernel(int n_vert, const double* __restrict__ verts, const double* __restrict__ R,
+                                     const double* __restrict__ t, const double* __restrict__ K4, rvtx* __restrict__ vtx) {
+  const int pose = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_vert) return;
+  const double* r = R + 9 * pose;
+  const double* tt = t + 3 * pose;
+  const double* k = K4 + 4 * pose;
+  const double px = verts[3 * i], py = verts[3 * i + 1], pz = verts[3 * i + 2];
+  const double X = r[0] * px + r[1] * py + r[2] * pz + tt[0];
+  const double Y = r[3] * px + r[4] * py + r[5] * pz + tt[1];
+  const double Z = r[6] * px + r[7] * py + r[8] * pz + tt[2];
+  rvtx v;
+  v.x = 0.0f;
+  v.y = 0.0f;
+  v.iz = 0.0;
+  if (Z > 0.0) {
+    const float x = (float)(k[0] * X / Z + k[2]);
+    const float y = (float)(k[1] * Y / Z + k[3]);
+    if (isfinite(x) && isfinite(y)) {
+      v.x = x;
+      v.y = y;
+      v.iz = 1.0 / Z;
+    }
+  }
+  vtx[(size_t)pose * n_vert + i] = v;
+}
+
+// Edge function of the directed edge a -> b at p, evaluated in the canonical direction of the edge and negated when (a, b) is
+// the other one, so that two triangles sharing an edge get exactly opposite values.
+__device__ __forceinline__ double edge_fn(float ax, float ay, float bx, float by, double px, double py) {
+  const bool sw = (ax > bx) || (ax == bx && ay > by);
+  const double x0 = sw ? bx : ax, y0 = sw ? by : ay, x1 = sw ? ax : bx, y1 = sw ? ay : by;
+  const double e = (x1 - x0) * (py - y0) - (y1 - y0) * (px - x0);
+  return sw ? -e : e;
+}
+
+// top-left rule: the inward normal (A, B) of an edge with w = A x + B y + C > 0 inside (image y points down)
+__device__ __forceinline__ bool top_left(float ax, float ay, float bx, float by, double s) {
+  const double A = -s * ((double)by - ay), B = s * ((double)bx - ax);
+  return A > 0.0 || (A == 0.0 && B > 0.0);
+}
+
+struct tri_setup {
+  float x[3], y[3];
+  double iz[3];
+  double s;            // orientation sign (w_i = s * e_i > 0 inside)
+  bool tl[3];          // top-left flag of the edge opposite vertex i
+  int c0, c1, r0, r1;  // pixel box (inclusive), clamped to the image; empty when c0 > c1 or r0 > r1
+};
+
+// false: the triangle draws nothing (bad index, vertex behind the camera, zero area, off-screen)
+__device__ bool setup_triangle(const rvtx* __restrict__ vtx, int n_vert, const int* __restrict__ faces, int tri, int width,
+                               int height, tri_setup* T) {
+  const int i0 = faces[3 * tri], i1 = faces[3 * tri + 1], i2 = faces[3 * tri + 2];
+  if (i0 < 0 || i0 >= n_vert || i1 < 0 || i1 >= n_vert || i2 < 0 || i2 >= n_vert) return false;
+  const rvtx a = vtx[i0], b = vtx[i1], c = vtx[i2];
+  if (!(a.iz > 0.0 && b.iz > 0.0 && c.iz > 0.0)) return false;
+  T->x[0] = a.x; T->y[0] = a.y; T->iz[0] = a.iz;
+  T->x[1] = b.x; T->y[1] = b.y; T->iz[1] = b.iz;
+  T->x[2] = c.x; T->y[2] = c.y; T->iz[2] = c.iz;
+  const double area2 = edge_fn(b.x, b.y, c.x, c.y, a.x, a.y);
+  if (area2 == 0.0) return false;
+  T->s = area2 > 0.0 ? 1.0 : -1.0;
+  T->tl[0] = top_left(b.x, b.y, c.x, c.y, T->s);
+  T->tl[1] = top_left(c.x, c.y, a.x, a.y, T->s);
+  T->tl[2] = top_left(a.x, a.y, b.x, b.y, T->s);
+  // pixel centres c + 0.5 in [min x, max x]; clamp in float before converting (coordinates may be huge)
+  const double lo_x = fmin(fmin((double)a.x, (double)b.x), (double)c.x), hi_x = fmax(fmax((double)a.x, (double)b.x), (double)c.x);
+  const double lo_y = fmin(fmin((double)a.y, (double)b.y), (double)c.y), hi_y = fmax(fmax((double)a.y, (double)b.y), (double)c.y);
+  const double cl = ceil(fmin(fmax(lo_x - 0.5, -1.0), (double)width)), ch = floor(fmin(fmax(hi_x - 0.5, -1.0), (double)width));
+  const double rl = ceil(fmin(fmax(lo_y - 0.5, -1.0), (double)height)), rh = floor(fmin(fmax(hi_y - 0.5, -1.0), (double)height));
+  T->c0 = max((int)cl, 0);
+  T->c1 = min((int)ch, width - 1);
+  T->r0 = max((int)rl, 0);
+  T->r1 = min((int)rh, height - 1);
+  return T->c0 <= T->c1 && T->r0 <= T->r1;
+}
+
+// depth of the triangle at pixel (r, c), or 0 when the pixel centre is outside it or the depth is clipped
+__device__ __forceinline__ float shade(const tri_setup& T, int r, int c, double zn, double zf) {
+  const double px = c + 0.5, py = r + 0.5;
+  const double w0 = T.s * edge_fn(T.x[1], T.y[1], T.x[2], T.y[2], px, py);
+  const double w1 = T.s * edge_fn(T.x[2], T.y[2], T.x[0], T.y[0], px, py);
+  const double w2 = T.s * edge_fn(T.x[0], T.y[0], T.x[1], T.y[1], px, py);
+  const bool in0 = w0 > 0.0 || (w0 == 0.0 && T.tl[0]);
+  const bool in1 = w1 > 0.0 || (w1 == 0.0 && T.tl[1]);
+  const bool in2 = w2 > 0.0 || (w2 == 0.0 && T.tl[2]);
+  if (!(in0 && in1 && in2)) return 0.0f;
+  const double den = (w0 + w1) + w2;
+  const double num = (w0 * T.iz[0] + w1 * T.iz[1]) + w2 * T.iz[2];
+  const double Z = den / num;
+  if (!(Z >= zn && Z <= zf)) return 0.0f;
+  return (float)Z;
+}
+
+__device__ __forceinline__ void tri_tiles(const tri_setup& T, int* tc0, int* tc1, int* tr0, int* tr1) {
+  *tc0 = T.c0 / RT;
+  *tc1 = T.c1 / RT;
+  *tr0 = T.r0 / RT;
+  *tr1 = T.r1 / RT;
+}
+
+// mode 0: count entries per (pose, tile); mode 1: scatter triangle ids into the lists / the pose's big list
+__global__ void render_bin_kernel(int mode, int n_vert, int n_tri, const int* __restrict__ faces, const rvtx* __restrict__ vtx_all,
+                                  int width, int height, int tiles_x, int n_tiles, int* __restrict__ counts, int* __restrict__ cursor,
+                                  int* __restrict__ list, int* __restrict__ big_n, int* __restrict__ big) {
+  const int pose = blockIdx.y, tri = blockIdx.x * blockDim.x + threadIdx.x;
+  if (tri >= n_tri) return;
+  tri_setup T;
+  if (!setup_triangle(vtx_all + (size_t)pose * n_vert, n_vert, faces, tri, width, height, &T)) return;
+  int tc0, tc1, tr0, tr1;
+  tri_tiles(T, &tc0, &tc1, &tr0, &tr1);
+  const int nt = (tc1 - tc0 + 1) * (tr1 - tr0 + 1);
+  if (nt > BIN_MAX_TILES) {
+    if (mode == 1) big[(size_t)pose * n_tri + atomicAdd(&big_n[pose], 1)] = tri;
+    return;
+  }
+  for (int ty = tr0; ty <= tr1; ++ty)
+    for (int tx = tc0; tx <= tc1; ++tx) {
+      const size_t b = (size_t)pose * n_tiles + ty * tiles_x + tx;
+      if (mode == 0)
+        atomicAdd(&counts[b], 1);
+      else
+        list[atomicAdd(&cursor[b], 1)] = tri;
+    }
+}
+
+// one workgroup: offsets[i] = sum of counts[0..i), offsets[n] = total; cursor = offsets
+__global__ void render_scan_kernel(int n, const int* __restrict__ counts, int* __restrict__ offsets, int* __restrict__ cursor) {
+  __shared__ int s[1024];
+  __shared__ int carry;
+  const int tid = threadIdx.x;
+  if (tid == 0) carry = 0;
+  __syncthreads();
+  for (int base = 0; base < n; base += 1024) {
+    const int v = base + tid < n ? counts[base + tid] : 0;
+    s[tid] = v;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {
+      const int u = tid >= off ? s[tid - off] : 0;
+      __syncthreads();
+      s[tid] += u;
+      __syncthreads();
+    }
+    const int excl = carry + s[tid] - v;
+    if (base + tid < n) {
+      offsets[base + tid] = excl;
+      cursor[base + tid] = excl;
+    }
+    __syncthreads();
+    if (tid == 1023) carry += s[1023];
+    __syncthreads();
+  }
+  if (tid == 0) offsets[n] = carry;
+}
+
+__device__ __forceinline__ void raster_px(unsigned* zb, const tri_setup& T, int r, int c, int r0, int c0, double zn, double zf) {
+  const float z = shade(T, r, c, zn, zf);
+  if (z > 0.0f) atomicMin(&zb[(r - r0) * RT + (c - c0)], __float_as_uint(z));
+}
+
+// the queued triangles, each spread over the whole workgroup
+__device__ void raster_queue(unsigned* zb, const int* queue, int qn, const rvtx* vtx, int n_vert, const int* faces, int width,
+                             int height, int r0, int c0, double zn, double zf) {
+  for (int q = 0; q < qn; ++q) {
+    tri_setup T;
+    setup_triangle(vtx, n_vert, faces, queue[q], width, height, &T);  // queued triangles passed it already
+    const int a0 = max(T.c0, c0), a1 = min(T.c1, c0 + RT - 1), b0 = max(T.r0, r0), b1 = min(T.r1, r0 + RT - 1);
+    const int bw = a1 - a0 + 1, n = bw * (b1 - b0 + 1);
+    for (int k = threadIdx.x; k < n; k += RASTER_THREADS) raster_px(zb, T, b0 + k / bw, a0 + k % bw, r0, c0, zn, zf);
+  }
+}
+
+__global__ void __launch_bounds__(RASTER_THREADS)
+render_raster_kernel(int n_vert, const int* __restrict__ faces, const rvtx* __restrict__ vtx_all, int n_tri, int width, int height,
+                     int tiles_x, int n_tiles, const int* __restrict__ offsets, const int* __restrict__ list, const int* __restrict__ big_n,
+                     const int* __restrict__ big, double zn, double zf, float* __restrict__ depth) {
+  __shared__ unsigned zb[RT * RT];
+  __shared__ int queue[RASTER_THREADS];
+  __shared__ int qn;
+  const int pose = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+  const int r0 = (tile / tiles_x) * RT, c0 = (tile % tiles_x) * RT;
+  const rvtx* vtx = vtx_all + (size_t)pose * n_vert;
+  for (int k = tid; k < RT * RT; k += RASTER_THREADS) zb[k] = 0x7F800000u;  // +inf
+  if (tid == 0) qn = 0;
+  __syncthreads();
+  const size_t b = (size_t)pose * n_tiles + tile;
+  const int l0 = offsets[b], l1 = offsets[b + 1];
+  for (int base = l0; base < l1; base += RASTER_THREADS) {
+    if (base + tid < l1) {
+      const int tri = list[base + tid];
+      tri_setup T;
+      if (setup_triangle(vtx, n_vert, faces, tri, width, height, &T)) {
+        const int a0 = max(T.c0, c0), a1 = min(T.c1, c0 + RT - 1), b0 = max(T.r0, r0), b1 = min(T.r1, r0 + RT - 1);
+        const int area = (a1 - a0 + 1) * (b1 - b0 + 1);
+        if (a0 <= a1 && b0 <= b1) {
+          if (area <= RASTER_SMALL_PX) {
+            for (int r = b0; r <= b1; ++r)
+              for (int c = a0; c <= a1; ++c) raster_px(zb, T, r, c, r0, c0, zn, zf);
+          } else {
+            queue[atomicAdd(&qn, 1)] = tri;
+          }
+        }
+      }
+    }
+    __syncthreads();
+    raster_queue(zb, queue, qn, vtx, n_vert, faces, width, height, r0, c0, zn, zf);
+    __syncthreads();
+    if (tid == 0) qn = 0;
+    __syncthreads();
+  }
+  const int nb = big_n[pose];
+  for (int base = 0; base < nb; base += RASTER_THREADS) {
+    if (base + tid < nb) {
+      const int tri = big[(size_t)pose * n_tri + base + tid];
+      tri_setup T;
+      if (setup_triangle(vtx, n_vert, faces, tri, width, height, &T) && T.c0 < c0 + RT && T.c1 >= c0 && T.r0 < r0 + RT && T.r1 >= r0)
+        queue[atomicAdd(&qn, 1)] = tri;
+    }
+    __syncthreads();
+    raster_queue(zb, queue, qn, vtx, n_vert, faces, width, height, r0, c0, zn, zf);
+    __syncthreads();
+    if (tid == 0) qn = 0;
+    __syncthreads();
+  }
+  // the tile, 4 pixels of one row per thread
+  const int r = r0 + tid / (RT / 4), c = c0 + (tid % (RT / 4)) * 4;
+  if (r >= height) return;
+  float v[4];
+  for (int k = 0; k < 4; ++k) {
+    const unsigned u = zb[(tid / (RT / 4)) * RT + (tid % (RT / 4)) * 4 + k];
+    v[k] = u == 0x7F800000u ? 0.0f : __uint_as_float(u);
+  }
+  float* row = depth + ((size_t)pose * height + r) * width;
+  if ((width & 3) == 0 && c + 3 < width) {
+    *(float4*)(row + c) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+    for (int k = 0; k < 4; ++k)
+      if (c + k < width) row[c + k] = v[k];
+  }
+}
+
+struct render_ws {
+  rvtx* vtx;
+  int *counts, *offsets, *cursor, *list, *big_n, *big;
+};
+
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+static size_t render_layout(int n_pose, int n_vert, int n_tri, int width, int height, char* base, render_ws* w) {
+  const size_t tiles = (size_t)((width + RT - 1) / RT) * ((height + RT - 1) / RT);
+  const size_t nb = (size_t)n_pose * tiles;
+  const size_t sizes[7] = {(size_t)n_pose * n_vert * sizeof(rvtx), nb * sizeof(int), (nb + 1) * sizeof(int), nb * sizeof(int),
+                           (size_t)n_pose * n_tri * BIN_MAX_TILES * sizeof(int), (size_t)n_pose * sizeof(int),
+                           (size_t)n_pose * n_tri * sizeof(int)};
+  size_t off[7], total = 0;
+  for (int i = 0; i < 7; ++i) {
+    off[i] = total;
+    total += align256(sizes[i]);
+  }
+  if (w) {
+    w->vtx = (rvtx*)(base + off[0]);
+    w->counts = (int*)(base + off[1]);
+    w->offsets = (int*)(base + off[2]);
+    w->cursor = (int*)(base + off[3]);
+    w->list = (int*)(base + off[4]);
+    w->big_n = (int*)(base + off[5]);
+    w->big = (int*)(base + off[6]);
+  }
+  return total;
+}
+
+static bool render_shape_ok(int n_pose, int n_vert, int n_tri, int width, int height) {
+  return n_pose > 0 && n_pose <= 65535 && n_vert > 0 && n_tri > 0 && width > 0 && height > 0 && width <= 16384 && height <= 16384 &&
+         (long long)n_pose * n_tri * BIN_MAX_TILES <= 0x7FFFFFFFLL && (long long)n_pose * n_vert <= 0x7FFFFFFFLL;
+}
+
+extern "C" size_t pp_render_workspace_bytes(int n_pose, int n_vert, int n_tri, int width, int height) {
+  if (!render_shape_ok(n_pose, n_vert, n_tri, width, height)) return 0;
+  return render_layout(n_pose, n_vert, n_tri, width, height, nullptr, nullptr);
+}
+
+extern "C" int pp_render_depth_f32(pp_ctx* ctx, int n_pose, int n_vert, const double* verts, int n_tri, const int* faces,
+                                   const double* R, const double* t, const double* K4, int width, int height, double clip_near,
+                                   double clip_far, void* workspace, size_t workspace_bytes, float* depth) {
+  PP_REQUIRE_CTX(ctx);
+  PP_CHECK_ARG(ctx, render_shape_ok(n_pose, n_vert, n_tri, width, height), PP_ERR_SHAPE,
+               "pp_render_depth_f32: need 1..65535 poses, vertices, triangles, a 1..16384 image and n_pose * n_tri * 4 < 2^31");
+  PP_CHECK_ARG(ctx, verts && faces && R && t && K4 && workspace && depth, PP_ERR_ARG, "pp_render_depth_f32: null argument");
+  PP_CHECK_ARG(ctx, clip_near >= 0.0 && clip_far >= clip_near, PP_ERR_ARG, "pp_render_depth_f32: need 0 <= clip_near <= clip_far");
+  render_ws w;
+  const size_t need = render_layout(n_pose, n_vert, n_tri, width, height, (char*)workspace, &w);
+  PP_CHECK_ARG(ctx, workspace_bytes >= need, PP_ERR_ARG, "pp_render_depth_f32: workspace of %zu bytes, need %zu", workspace_bytes, need);
+  const int tiles_x = (width + RT - 1) / RT, n_tiles = tiles_x * ((height + RT - 1) / RT);
+  const size_t nb = (size_t)n_pose * n_tiles;
+  hipMemsetAsync(w.counts, 0, nb * sizeof(int), ctx->stream);
+  hipMemsetAsync(w.big_n, 0, (size_t)n_pose * sizeof(int), ctx->stream);
+  hipLaunchKernelGGL(render_vertex_kernel, dim3((n_vert + 255) / 256, n_pose), dim3(256), 0, ctx->stream, n_vert, verts, R, t, K4, w.vtx);
+  const dim3 tg((n_tri + 255) / 256, n_pose);
+  hipLaunchKernelGGL(render_bin_kernel, tg, dim3(256), 0, ctx->stream, 0, n_vert, n_tri, faces, (const rvtx*)w.vtx, width, height,
+                     tiles_x, n_tiles, w.counts, w.cursor, w.list, w.big_n, w.big);
+  hipLaunchKernelGGL(render_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, (int)nb, (const int*)w.counts, w.offsets, w.cursor);
+  hipLaunchKernelGGL(render_bin_kernel, tg, dim3(256), 0, ctx->stream, 1, n_vert, n_tri, faces, (const rvtx*)w.vtx, width, height,
+                     tiles_x, n_tiles, w.counts, w.cursor, w.list, w.big_n, w.big);
+  hipLaunchKernelGGL(render_raster_kernel, dim3(n_tiles, n_pose), dim3(RASTER_THREADS), 0, ctx->stream, n_vert, faces,
+                     (const rvtx*)w.vtx, n_tri, width, height, tiles_x, n_tiles, (const int*)w.offsets, (const int*)w.list,
+                     (const int*)w.big_n, (const int*)w.big, clip_near, clip_far, depth);
+  PP_CHECK_LAUNCH(ctx, "pp_render_depth_f32");
+  return PP_OK;
+}
+
+// ---- VSD ----------------------------------------------------------------------------------------------------------------
+
+// depth_im_to_dist_im (pose_error.py:43-61) at one pixel: || ((c - cx) d / fx, (r - cy) d / fy, d) ||, summed x, y, z in order
+__device__ __forceinline__ double dist_px(float d, int r, int c, double cx, double cy, double rfx, double rfy) {
+  const double dd = (double)d;
+  const double X = (((double)c - cx) * dd) * rfx;
+  const double Y = (((double)r - cy) * dd) * rfy;
+  return sqrt((X * X + Y * Y) + dd * dd);
+}
+
+// estimate_visib_mask (pose_error.py:15-29): both valid and float32(d_model) - float32(d_test) <= delta (in float32)
+__device__ __forceinline__ bool visib(double d_test, double d_model, float delta) {
+  return d_test > 0.0 && d_model > 0.0 && ((float)d_model - (float)d_test) <= delta;
+}
+
+__device__ void block_reduce3(double c, int inter, int uni, double* rd, int* ri, int* ru) {
+  const int tid = threadIdx.x;
+  rd[tid] = c;
+  ri[tid] = inter;
+  ru[tid] = uni;
+  __syncthreads();
+  for (int s = VSD_THREADS / 2; s > 0; s >>= 1) {
+    if (tid < s) {
+      rd[tid] += rd[tid + s];
+      ri[tid] += ri[tid + s];
+      ru[tid] += ru[tid + s];
+    }
+    __syncthreads();
+  }
+}
+
+// grid (blocks of VSD_BLOCK pixels, problems): per block the cost sum over the intersection, |inter| and |union|
+__global__ void __launch_bounds__(VSD_THREADS)
+vsd_partial_kernel(int width, int hw, const float* __restrict__ depth_test, long long test_stride, const float* __restrict__ depth_est,
+                   const float* __restrict__ depth_gt, const double* __restrict__ K4, float delta, double tau, int cost_type,
+                   double* __restrict__ part_cost, int* __restrict__ part_cnt) {
+  __shared__ double rd[VSD_THREADS];
+  __shared__ int ri[VSD_THREADS], ru[VSD_THREADS];
+  const int prob = blockIdx.y;
+  const double* k = K4 + 4 * prob;
+  const double cx = k[2], cy = k[3], rfx = 1.0 / k[0], rfy = 1.0 / k[1], rtau = 1.0 / tau;
+  const float* dt = depth_test + (size_t)prob * test_stride;
+  const float* de = depth_est + (size_t)prob * hw;
+  const float* dg = depth_gt + (size_t)prob * hw;
+  double cost = 0.0;
+  int inter = 0, uni = 0;
+  for (int j = 0; j < VSD_PER_THREAD; ++j) {
+    const int p = blockIdx.x * VSD_BLOCK + j * VSD_THREADS + threadIdx.x;
+    if (p >= hw) break;
+    const int r = p / width, c = p - r * width;
+    const double t_ = dist_px(dt[p], r, c, cx, cy, rfx, rfy);
+    const double e_ = dist_px(de[p], r, c, cx, cy, rfx, rfy);
+    const double g_ = dist_px(dg[p], r, c, cx, cy, rfx, rfy);
+    const bool vg = visib(t_, g_, delta);
+    const bool ve = visib(t_, e_, delta) || (vg && e_ > 0.0);
+    if (vg && ve) {
+      ++inter;
+      const double d = fabs(g_ - e_);
+      if (cost_type == 0) {
+        cost += d >= tau ? 1.0 : 0.0;
+      } else {
+        const double q = d * rtau;
+        cost += q > 1.0 ? 1.0 : q;
+      }
+    }
+    uni += (vg || ve) ? 1 : 0;
+  }
+  block_reduce3(cost, inter, uni, rd, ri, ru);
+  if (threadIdx.x == 0) {
+    const size_t o = (size_t)prob * gridDim.x + blockIdx.x;
+    part_cost[o] = rd[0];
+    part_cnt[2 * o] = ri[0];
+    part_cnt[2 * o + 1] = ru[0];
+  }
+}
+
+__global__ void vsd_final_kernel(int n, int nblk, const double* __restrict__ part_cost, const int* __restrict__ part_cnt,
+                                 double* __restrict__ e, long long* __restrict__ inter_out, long long* __restrict__ union_out) {
+  const int prob = blockIdx.x * blockDim.x + threadIdx.x;
+  if (prob >= n) return;
+  double cost = 0.0;
+  long long inter = 0, uni = 0;
+  for (int b = 0; b < nblk; ++b) {
+    const size_t o = (size_t)prob * nblk + b;
+    cost += part_cost[o];
+    inter += part_cnt[2 * o];
+    uni += part_cnt[2 * o + 1];
+  }
+  e[prob] = uni > 0 ? (cost + (double)(uni - inter)) / (double)uni : 1.0;
+  if (inter_out) inter_out[prob] = inter;
+  if (union_out) union_out[prob] = uni;
+}
+
+extern "C" size_t pp_vsd_workspace_bytes(int n, int width, int height) {
+  if (n <= 0 || width <= 0 || height <= 0) return 0;
+  const size_t nblk = ((size_t)width * height + VSD_BLOCK - 1) / VSD_BLOCK;
+  return align256((size_t)n * nblk * sizeof(double)) + (size_t)n * nblk * 2 * sizeof(int);
+}
+
+extern "C" int pp_vsd_f64(pp_ctx* ctx, int n, int width, int height, const float* depth_test, long long test_stride,
+                          const float* depth_est, const float* depth_gt, const double* K4, double delta, double tau, int cost_type,
+                          void* workspace, double* e, long long* inter, long long* uni) {
+  PP_REQUIRE_CTX(ctx);
+  PP_CHECK_ARG(ctx, n > 0 && n <= 65535 && width > 0 && height > 0 && (long long)width * height <= 0x7FFFFFFFLL, PP_ERR_SHAPE,
+               "pp_vsd_f64: need 1..65535 problems and a non-empty image");
+  PP_CHECK_ARG(ctx, depth_test && depth_est && depth_gt && K4 && workspace && e, PP_ERR_ARG, "pp_vsd_f64: null argument");
+  PP_CHECK_ARG(ctx, test_stride == 0 || test_stride == (long long)width * height, PP_ERR_ARG,
+               "pp_vsd_f64: test_stride must be 0 (one shared scene depth) or width * height");
+  PP_CHECK_ARG(ctx, cost_type == 0 || cost_type == 1, PP_ERR_ARG, "pp_vsd_f64: cost_type must be 0 (step) or 1 (tlinear)");
+  PP_CHECK_ARG(ctx, tau > 0.0, PP_ERR_ARG, "pp_vsd_f64: tau must be positive");
+  const int hw = width * height, nblk = (hw + VSD_BLOCK - 1) / VSD_BLOCK;
+  double* part_cost = (double*)workspace;
+  int* part_cnt = (int*)((char*)workspace + align256((size_t)n * nblk * sizeof(double)));
+  hipLaunchKernelGGL(vsd_partial_kernel, dim3(nblk, n), dim3(VSD_THREADS), 0, ctx->stream, width, hw, depth_test, test_stride,
+                     depth_est, depth_gt, K4, (float)delta, tau, cost_type, part_cost, part_cnt);
+  hipLaunchKernelGGL(vsd_final_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, n, nblk, (const double*)part_cost,
+                     (const int*)part_cnt, e, inter, uni);
+  PP_CHECK_LAUNCH(ctx, "pp_vsd_f64");
+  return PP_OK;
+}
+
+// ---- reprojection error ---------------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ void project_f32(const double* __restrict__ K, const double* __restrict__ R, const double* __restrict__ t,
+                                            double x, double y, double z, float* u, float* v) {
+  const double X = R[0] * x + R[1] * y + R[2] * z + t[0];
+  const double Y = R[3] * x + R[4] * y + R[5] * z + t[1];
+  const double Z = R[6] * x + R[7] * y + R[8] * z + t[2];
+  const double a = K[0] * X + K[1] * Y + K[2] * Z, b = K[3] * X + K[4] * Y + K[5] * Z, w = K[6] * X + K[7] * Y + K[8] * Z;
+  *u = (float)(a / w);
+  *v = (float)(b / w);
+}
+
+// grid (tiles, poses): partial[pose][tile] = sum over the tile's points of || est_px - gt_px || (float32 pixels, float32 norm)
+__global__ void pose_reproj_kernel(int n_pts, const double* __restrict__ pts, const double* __restrict__ K9, const double* __restrict__ R_est,
+                                   const double* __restrict__ t_est, const double* __restrict__ R_gt, const double* __restrict__ t_gt,
+                                   double* __restrict__ partial) {
+  __shared__ double red[REPROJ_TILE];
+  const int pose = blockIdx.y, i = blockIdx.x * REPROJ_TILE + threadIdx.x, tid = threadIdx.x;
+  double d = 0.0;
+  if (i < n_pts) {
+    const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+    float ue, ve, ug, vg;
+    project_f32(K9 + 9 * pose, R_est + 9 * pose, t_est + 3 * pose, x, y, z, &ue, &ve);
+    project_f32(K9 + 9 * pose, R_gt + 9 * pose, t_gt + 3 * pose, x, y, z, &ug, &vg);
+    const float du = ue - ug, dv = ve - vg;
+    d = (double)sqrtf(du * du + dv * dv);
+  }
+  red[tid] = d;
+  __syncthreads();
+  for (int s = REPROJ_TILE / 2; s > 0; s >>= 1) {
+    if (tid < s) red[tid] += red[tid + s];
+    __syncthreads();
+  }
+  if (tid == 0) partial[(size_t)pose * gridDim.x + blockIdx.x] = red[0];
+}
+
+__global__ void pose_reproj_mean_kernel(int n_pose, int n_tiles, int n_pts, const double* __restrict__ partial, double* __restrict__ out) {
+  const int pose = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pose >= n_pose) return;
+  double s = 0.0;
+  for (int t = 0; t < n_tiles; ++t) s += partial[(size_t)pose * n_tiles + t];
+  out[pose] = s / (double)n_pts;
+}
+
+extern "C" int pp_pose_reproj_f64(pp_ctx* ctx, int n_pose, int n_pts, const double* pts, const double* K9, const double* R_est,
+                                  const double* t_est, const double* R_gt, const double* t_gt, void* workspace, double* out) {
+  PP_REQUIRE_CTX(ctx);
+  PP_CHECK_ARG(ctx, n_pose > 0 && n_pose <= 65535 && n_pts > 0, PP_ERR_SHAPE, "pp_pose_reproj_f64: need 1..65535 poses and at least one model point");
+  PP_CHECK_ARG(ctx, pts && K9 && R_est && t_est && R_gt && t_gt && workspace && out, PP_ERR_ARG, "pp_pose_reproj_f64: null argument");
+  const int tiles = (n_pts + REPROJ_TILE - 1) / REPROJ_TILE;
+  double* partial = (double*)workspace;
+  hipLaunchKernelGGL(pose_reproj_kernel, dim3(tiles, n_pose), dim3(REPROJ_TILE), 0, ctx->stream, n_pts, pts, K9, R_est, t_est, R_gt, t_gt, partial);
+  hipLaunchKernelGGL(pose_reproj_mean_kernel, dim3((n_pose + 63) / 64), dim3(64), 0, ctx->stream, n_pose, tiles, n_pts, (const double*)partial, out);
+  PP_CHECK_LAUNCH(ctx, "pp_pose_reproj_f64");
+  return PP_OK;
+}

@@ -651,3 +651,63 @@ def pnp_ransac(ctx, offsets, obj, img, K4, iterations=300, reproj_error=5.0, see
                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(points_per_vote), _ptr(ws), _ptr(R), _ptr(t), _ptr(n_in), _ptr(mask),
                                 _ptr(ok)), ctx.handle, "pp_pnp_ransac_f64")
     return R, t, n_in, mask[:N], ok
+
+
+def render_depth(ctx, verts, faces, R, t, K4, width, height, clip_near=100.0, clip_far=10000.0):
+    """Depth images of one mesh at n poses (pp_render_depth_f32): cuda tensors verts float64 [n_vert,3], faces int32
+    [n_tri,3], R float64 [n,3,3], t [n,3], K4 [n,4] = (fx, fy, cx, cy) -> float32 [n, height, width], 0 = empty."""
+    n, nv, nt = int(R.shape[0]), int(verts.shape[0]), int(faces.shape[0])
+    assert verts.dtype == torch.float64 and R.dtype == torch.float64 and t.dtype == torch.float64 and K4.dtype == torch.float64
+    assert faces.dtype == torch.int32 and verts.shape == (nv, 3) and faces.shape == (nt, 3)
+    assert R.shape == (n, 3, 3) and t.shape == (n, 3) and K4.shape == (n, 4)
+    args = [a.contiguous() for a in (verts, faces, R, t, K4)]
+    nbytes = lib.pp_render_workspace_bytes(n, nv, nt, int(width), int(height))
+    if nbytes == 0:
+        raise ValueError("render_depth: unsupported shape (n=%d, vertices=%d, triangles=%d, %dx%d)" % (n, nv, nt, width, height))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device="cuda")
+    out = torch.empty((n, int(height), int(width)), dtype=torch.float32, device="cuda")
+    check(lib.pp_render_depth_f32(ctx.handle, n, nv, _ptr(args[0]), nt, _ptr(args[1]), _ptr(args[2]), _ptr(args[3]), _ptr(args[4]),
+                                  int(width), int(height), float(clip_near), float(clip_far), _ptr(ws), nbytes, _ptr(out)),
+          ctx.handle, "pp_render_depth_f32")
+    return out
+
+
+VSD_COSTS = {"step": 0, "tlinear": 1}
+
+
+def vsd(ctx, depth_test, depth_est, depth_gt, K4, delta, tau, cost_type="step"):
+    """Visible Surface Discrepancy of n problems (pp_vsd_f64): cuda float32 depth_est / depth_gt [n,h,w], depth_test [h,w]
+    (shared by all problems) or [n,h,w], K4 float64 [n,4] -> (e float64 [n], intersection int64 [n], union int64 [n])."""
+    if cost_type not in VSD_COSTS:
+        raise ValueError("vsd: unknown pixel matching cost %r (step | tlinear)" % (cost_type,))
+    n, h, w = (int(s) for s in depth_est.shape)
+    assert depth_gt.shape == depth_est.shape and K4.shape == (n, 4) and K4.dtype == torch.float64
+    for d in (depth_test, depth_est, depth_gt):
+        assert d.dtype == torch.float32 and d.is_cuda
+    if tuple(depth_test.shape) == (h, w):
+        stride = 0
+    elif tuple(depth_test.shape) == (n, h, w):
+        stride = h * w
+    else:
+        raise ValueError("vsd: depth_test must be [h,w] or [n,h,w], got %s" % (tuple(depth_test.shape),))
+    dt, de, dg, K4 = depth_test.contiguous(), depth_est.contiguous(), depth_gt.contiguous(), K4.contiguous()
+    ws = torch.empty((max(1, lib.pp_vsd_workspace_bytes(n, w, h)),), dtype=torch.uint8, device="cuda")
+    e = torch.empty((n,), dtype=torch.float64, device="cuda")
+    inter = torch.empty((n,), dtype=torch.int64, device="cuda")
+    uni = torch.empty((n,), dtype=torch.int64, device="cuda")
+    check(lib.pp_vsd_f64(ctx.handle, n, w, h, _ptr(dt), stride, _ptr(de), _ptr(dg), _ptr(K4), float(delta), float(tau),
+                         VSD_COSTS[cost_type], _ptr(ws), _ptr(e), _ptr(inter), _ptr(uni)), ctx.handle, "pp_vsd_f64")
+    return e, inter, uni
+
+
+def pose_reproj(ctx, pts, K9, R_est, t_est, R_gt, t_gt):
+    """Mean 2-D reprojection error of n poses against one model (pp_pose_reproj_f64): cuda float64 tensors pts [n_pts,3],
+    K9 [n,3,3], R_* [n,3,3], t_* [n,3] -> float64 [n] (pixels)."""
+    n, n_pts = R_est.shape[0], pts.shape[0]
+    args = [a.contiguous() for a in (pts, K9, R_est, t_est, R_gt, t_gt)]
+    for a in args:
+        assert a.dtype == torch.float64 and a.is_cuda
+    ws = torch.empty((max(1, lib.pp_pose_error_workspace_bytes(n, n_pts)),), dtype=torch.uint8, device="cuda")
+    out = torch.empty((n,), dtype=torch.float64, device="cuda")
+    check(lib.pp_pose_reproj_f64(ctx.handle, n, n_pts, *[_ptr(a) for a in args], _ptr(ws), _ptr(out)), ctx.handle, "pp_pose_reproj_f64")
+    return out

@@ -66,3 +66,76 @@ def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_
     seen = max(int((allPoses[1:] > 0).sum()), 1)
     return dict(allPoses=allPoses, trueDets=trueDets, truePoses=truePoses, recall=recall, detections=detections,
                 recall_all=float(recall[1:].sum() / seen), detections_all=float(detections[1:].sum() / seen), errors=errors)
+
+
+ADD_FRACTIONS = tuple(round(0.05 * k, 2) for k in range(1, 20))  # tless_eval.py:665-725: 0.05 ... 0.95 x diameter
+
+
+def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, model_diameters, load_depth, K, threshold=0.5, min_votes=10,
+                          delta=0.3, tau=20.0, vsd_threshold=0.3, cost_type="step", symmetric_classes=(), gt_translation_scale=0.001,
+                          depth_scale=1000.0, seed=0):
+    """The metric block of tless_eval.py:470-725 (also in occlusion_eval.py / ycbv_eval.py / homebrewed_eval.py) on top of the
+    loop of evaluate_add: per detected, annotated class, the rotation / translation errors re / te (correct when re < 5 deg
+    and te < 0.05), the reprojection error (< 5 px), VSD against the image's depth (< vsd_threshold) and ADD (ADI for
+    symmetric_classes) against 0.05 ... 0.95 x the model diameter.
+
+    models: per class a load_ply dict ('pts' [n,3] and 'faces' [m,3]) in the unit of the estimated translation (metres, as
+    model_vsd at tless_eval.py:77); load_depth(index): the scene's depth image [h,w] in millimetres (uint16 or float);
+    K: 3x3 intrinsics or a callable index -> 3x3; depth_scale: model / translation unit -> depth unit (VSD runs in
+    millimetres with delta / tau as the reference passes them, 0.3 / 20).  One launch per metric per (image, class).
+    Returns dict(allPoses, trueDets, less5, rep_less5, vsd_less_t, add_less [len(ADD_FRACTIONS), C+1], add_fractions, the
+    matching rates (counter / allPoses) and errors: one dict per scored detection); index = class id + 1 as in evaluate_add."""
+    C = len(model_diameters)
+    counters = ("allPoses", "trueDets", "less5", "rep_less5", "vsd_less_t")
+    out = {k: np.zeros((C + 1,), np.uint32) for k in counters}
+    add_less = np.zeros((len(ADD_FRACTIONS), C + 1), np.uint32)
+    errors = []
+    for index in range(generator.size()):
+        image = generator.preprocess_image(generator.load_image(index))
+        image, _scale = generator.resize_image(image)
+        anno = generator.load_annotations(index)
+        if len(anno["labels"]) < 1:
+            continue
+        labels = [int(l) for l in anno["labels"]]
+        for lab in labels:
+            out["allPoses"][lab + 1] += 1
+        Kc = np.asarray(K(index) if callable(K) else K, np.float64).reshape(3, 3)
+        boxes3D, scores, _mask = predict_on_batch(np.expand_dims(image, axis=0))
+        poses = pose_decode.poses_from_outputs(boxes3D, scores, threeD_boxes, Kc, threshold=threshold, min_votes=min_votes, seed=seed + index)
+        dets = [d for d in poses if d["cls"] in labels]  # the reference only scores the annotated classes
+        if not dets:
+            continue
+        depth = np.asarray(load_depth(index))
+        for cls in sorted(set(d["cls"] for d in dets)):
+            group = [d for d in dets if d["cls"] == cls]
+            pose = np.asarray(anno["poses"][labels.index(cls)], np.float64)
+            R_gt, t_gt = quat2mat(pose[3:]), pose[:3] * gt_translation_scale
+            n = len(group)
+            R_est = np.stack([d["R"] for d in group])
+            t_est = np.stack([np.asarray(d["t"], np.float64).reshape(3) for d in group])
+            R_g, t_g = np.repeat(R_gt[None], n, 0), np.repeat(t_gt[None], n, 0)
+            model = models[cls]
+            rd = pose_error.re_batch(R_g, R_est)                                 # re(R_gt, R_est) as at tless_eval.py:470
+            xyz = pose_error.te_batch(t_g, t_est)
+            rep = pose_error.reproj_batch(Kc, R_est, t_est, R_g, t_g, model["pts"])
+            mm = dict(model, pts=np.asarray(model["pts"], np.float64) * depth_scale)
+            e_vsd = pose_error.vsd_batch(R_est, t_est * depth_scale, R_g, t_g * depth_scale, mm, depth, Kc, delta, tau, cost_type)
+            e_add = pose_error.add_batch(R_est, t_est, R_g, t_g, model["pts"], symmetric=cls in symmetric_classes)
+            for k, d in enumerate(group):
+                out["trueDets"][cls + 1] += 1
+                errors.append(dict(image=index, cls=cls, ok=d["ok"], re=float(rd[k]), te=float(xyz[k]), reproj=float(rep[k]),
+                                   vsd=float(e_vsd[k]), add=float(e_add[k])))
+                if not d["ok"]:
+                    continue
+                out["less5"][cls + 1] += bool(rd[k] < 5.0 and xyz[k] < 0.05)
+                out["rep_less5"][cls + 1] += bool(rep[k] < 5.0)
+                out["vsd_less_t"][cls + 1] += bool(e_vsd[k] < vsd_threshold)
+                for j, f in enumerate(ADD_FRACTIONS):
+                    add_less[j, cls + 1] += bool(e_add[k] < model_diameters[cls] * f)
+    all_f = out["allPoses"].astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for k in counters[1:]:
+            out[k + "_rate"] = np.nan_to_num(out[k] / all_f)
+        out["add_less_rate"] = np.nan_to_num(add_less / all_f[None])
+    out.update(add_less=add_less, add_fractions=np.array(ADD_FRACTIONS), errors=errors)
+    return out

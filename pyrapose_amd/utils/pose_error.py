@@ -1,5 +1,9 @@
-"""Mirror of the pose-error functions the evaluation loops call (utils/pose_error.py:64-75, 210-246;
-utils/linemod_eval.py:525-531): same names, arguments and float return values, computed by the HIP kernels."""
+"""Mirror of the pose-error functions the evaluation loops call (utils/pose_error.py:43-75, 105-275;
+utils/linemod_eval.py:525-531, tless_eval.py:470-471, 651-662): same names, arguments and float return values, computed by the
+HIP kernels (ADD / ADI / reproj in csrc/pose.hip and csrc/render.hip, VSD on depth images from utils.renderer); re / te and
+depth_im_to_dist_im stay on the host in numpy."""
+import math
+
 import numpy as np
 import torch
 
@@ -39,3 +43,127 @@ def add_batch(R_est, t_est, R_gt, t_gt, pts, symmetric=False):
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64))).cuda()
     return ops.pose_errors(default_context(), dev(pts), dev(R_est), dev(np.reshape(t_est, (-1, 3))), dev(R_gt),
                            dev(np.reshape(t_gt, (-1, 3))), symmetric).cpu().numpy()
+
+
+def _dev(a, shape=None):
+    a = np.array(a, np.float64)  # a copy: broadcast views are read-only
+    return torch.from_numpy(a if shape is None else np.ascontiguousarray(a.reshape(shape))).cuda()
+
+
+def _stack(a, n, shape):
+    """one array per pose, or one shared by all n poses -> float64 [n, *shape]"""
+    a = np.asarray(a, np.float64)
+    if a.size == int(np.prod(shape)):
+        return np.broadcast_to(a.reshape(shape), (n,) + shape)
+    return a.reshape((n,) + shape)
+
+
+def _poses(R_est, t_est, R_gt, t_gt):
+    R_est = np.asarray(R_est, np.float64).reshape(-1, 3, 3)
+    n = R_est.shape[0]
+    return (R_est, np.asarray(t_est, np.float64).reshape(n, 3), np.asarray(R_gt, np.float64).reshape(n, 3, 3),
+            np.asarray(t_gt, np.float64).reshape(n, 3))
+
+
+def reproj_batch(K, R_est, t_est, R_gt, t_gt, pts):
+    """reproj() of n poses of one object in one launch: K 3x3 or [n,3,3], R_* [n,3,3], t_* [n,3] -> float64 [n] (pixels).
+    Projections are rounded to float32 and the norm is taken in float32 as the reference does; the mean is summed in float64,
+    so values agree with the reference's float32 mean within 1e-5 relative."""
+    pts = np.asarray(pts, np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+        raise ValueError("pts must be n x 3")
+    R_est, t_est, R_gt, t_gt = _poses(R_est, t_est, R_gt, t_gt)
+    n = R_est.shape[0]
+    K9 = _stack(K, n, (3, 3))
+    return ops.pose_reproj(default_context(), _dev(pts), _dev(K9), _dev(R_est), _dev(t_est), _dev(R_gt), _dev(t_gt)).cpu().numpy()
+
+
+def reproj(K, R_est, t_est, R_gt, t_gt, pts):
+    """Mean 2-D reprojection error in pixels (pose_error.py:179-207)."""
+    return float(reproj_batch(K, R_est, t_est, R_gt, t_gt, pts)[0])
+
+
+def re(R_est, R_gt):
+    """Rotational error in degrees (pose_error.py:249-262): the angle of R_est inv(R_gt), its cosine clipped to [-1, 1]."""
+    R_est, R_gt = np.asarray(R_est), np.asarray(R_gt)
+    if not R_est.shape == R_gt.shape == (3, 3):
+        raise ValueError("re: R_est and R_gt must be 3 x 3")
+    c = 0.5 * (np.trace(R_est.dot(np.linalg.inv(R_gt))) - 1.0)
+    c = min(1.0, max(-1.0, c))
+    return 180.0 * math.acos(c) / np.pi
+
+
+def te(t_est, t_gt):
+    """Translational error (pose_error.py:265-275), in the unit of t."""
+    t_est, t_gt = np.asarray(t_est), np.asarray(t_gt)
+    if not t_est.size == t_gt.size == 3:
+        raise ValueError("te: t_est and t_gt must hold 3 values")
+    return float(np.linalg.norm(t_gt.reshape(3) - t_est.reshape(3)))
+
+
+def re_batch(R_est, R_gt):
+    """re() of n pose pairs: [n,3,3] x2 -> float64 [n] degrees (each value is what re() returns for that pair)."""
+    R_est, R_gt = np.asarray(R_est).reshape(-1, 3, 3), np.asarray(R_gt).reshape(-1, 3, 3)
+    return np.array([re(a, b) for a, b in zip(R_est, R_gt)], np.float64)
+
+
+def te_batch(t_est, t_gt):
+    """te() of n pose pairs: [n,3] x2 -> float64 [n]."""
+    t_est, t_gt = np.asarray(t_est).reshape(-1, 3), np.asarray(t_gt).reshape(-1, 3)
+    return np.array([te(a, b) for a, b in zip(t_est, t_gt)], np.float64)
+
+
+def depth_im_to_dist_im(depth_im, K):
+    """Depth image -> distance image (pose_error.py:43-61), host numpy: per pixel (x, y) the length of
+    ((x - cx) d / fx, (y - cy) d / fy, d), 0 where d is 0."""
+    d = np.asarray(depth_im)
+    K = np.asarray(K, np.float64)
+    h, w = d.shape
+    xs = np.tile(np.arange(w), [h, 1])
+    ys = np.tile(np.arange(h), [w, 1]).T
+    X = np.multiply(xs - K[0, 2], d) * (1.0 / K[0, 0])
+    Y = np.multiply(ys - K[1, 2], d) * (1.0 / K[1, 1])
+    return np.linalg.norm(np.dstack((X, Y, d)), axis=2)
+
+
+def _K4(K, n):
+    K = _stack(K, n, (3, 3))
+    return np.ascontiguousarray(np.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], axis=1))
+
+
+def vsd_from_depth(depth_test, depth_est, depth_gt, K, delta, tau, cost_type="step", return_counts=False):
+    """VSD of n problems from depth images already rendered: depth_est / depth_gt [n,h,w] (numpy or cuda tensors),
+    depth_test [h,w] shared by all of them or [n,h,w] (float32 or uint16), K 3x3 or [n,3,3] -> float64 [n]; with
+    return_counts also the intersection and union pixel counts."""
+    dev32 = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.float32)))).cuda().float()
+    de, dg, dt = dev32(depth_est), dev32(depth_gt), dev32(depth_test)
+    if de.dim() == 2:
+        de, dg = de[None], dg[None]
+    if de.dim() != 3 or dg.shape != de.shape:
+        raise ValueError("vsd: depth_est and depth_gt must be [n,h,w] of one shape")
+    e, inter, uni = ops.vsd(default_context(), dt, de, dg, _dev(_K4(K, de.shape[0])), delta, tau, cost_type)
+    e = e.cpu().numpy()
+    return (e, inter.cpu().numpy(), uni.cpu().numpy()) if return_counts else e
+
+
+def vsd_batch(R_est, t_est, R_gt, t_gt, model, depth_test, K, delta, tau, cost_type="step", clip_near=100, clip_far=10000,
+              return_counts=False):
+    """vsd() of n poses of one object: both depth renderings of every pose in one launch, then one VSD launch.  depth_test
+    [h,w] (one scene) or [n,h,w]; K 3x3 or [n,3,3]; R_* [n,3,3], t_* [n,3] -> float64 [n]."""
+    from .renderer import render_depth_batch
+    if cost_type not in ops.VSD_COSTS:
+        raise ValueError("vsd: unknown pixel matching cost %r (step | tlinear)" % (cost_type,))
+    R_est, t_est, R_gt, t_gt = _poses(R_est, t_est, R_gt, t_gt)
+    n = R_est.shape[0]
+    h, w = np.shape(depth_test)[-2:]
+    Ks = _stack(K, n, (3, 3))
+    depth = render_depth_batch(model, (w, h), np.concatenate([Ks, Ks]), np.concatenate([R_est, R_gt]), np.concatenate([t_est, t_gt]),
+                               clip_near=clip_near, clip_far=clip_far)
+    return vsd_from_depth(depth_test, depth[:n], depth[n:], Ks, delta, tau, cost_type, return_counts)
+
+
+def vsd(R_est, t_est, R_gt, t_gt, model, depth_test, K, delta, tau, cost_type="step"):
+    """Visible Surface Discrepancy (pose_error.py:105-176).  model: dict with 'pts' [n,3] and 'faces' [m,3] (utils.ply_loader);
+    depth_test: the scene's depth image [h,w]; delta, tau in its unit (the reference calls it with 0.3 and 20, millimetres,
+    and renders with clip_near=100, clip_far=10000)."""
+    return float(vsd_batch(R_est, t_est, R_gt, t_gt, model, depth_test, K, delta, tau, cost_type)[0])
