@@ -473,6 +473,65 @@ int pp_pnp_ransac_f64(pp_ctx* ctx, int n_problems, const int* offsets_dev, int n
                       int points_per_vote, void* workspace, double* R_out, double* t_out, int* n_inliers,
                       unsigned char* inlier_mask, int* ok);
 
+/* ---- ICP refinement of estimated poses against scene depth (csrc/icp.hip) -------------------------------------------
+ * The block of PyraPose_ROS_wrapper/scripts/pyrapose_node.py:run_estimation (:662-756; the same block at
+ * utils/ycbv_eval.py:424-526, 812-896 and the get_evaluation* helpers of tless_eval.py:23-65), which runs on the CPU through
+ * Open3D / OpenCV there.  float64 throughout, fixed-order reductions: every result is bitwise independent of the batch it runs
+ * in and of the run. */
+#define PP_ICP_POINT_TO_POINT 0
+#define PP_ICP_POINT_TO_PLANE 1
+#define PP_ICP_OK 0
+#define PP_ICP_TOO_FEW 1   /* fewer than 6 (plane) / 3 (point) correspondences: the last pose is kept */
+#define PP_ICP_SINGULAR 2  /* the update's linear system is singular: the last pose is kept */
+/* create_point_cloud (pyrapose_node.py:170-189) with the class mask of :602-604 applied.  depth float32 [height,width]
+ * (device); point (r, c) = (((c - cx) z) / fx, ((r - cy) z) / fy, z) with z = depth * ds in float64.
+ * dense != 0: every pixel at index r * width + c of pts [height*width,3], an all-NaN row where z == 0 (as :186); mask,
+ * workspace and row_offsets unused.  dense == 0: only pixels with a finite, non-zero z whose mask cell
+ * mask[row_idx[r] * mask_w + col_idx[c]] (uint8 [mask_h,mask_w], NULL = no mask; row_idx / col_idx from
+ * pp_pil_nearest_index_host, device int32) is non-zero, compacted in row-major pixel order (count per row, scan, scatter);
+ * row_offsets [height+1] (device) gets each row's first output index and the total.
+ * workspace >= pp_cloud_from_depth_workspace_bytes. */
+size_t pp_cloud_from_depth_workspace_bytes(int height, int width);
+int pp_cloud_from_depth_f64(pp_ctx* ctx, int height, int width, const float* depth, const unsigned char* mask, int mask_h, int mask_w,
+                            const int* row_idx, const int* col_idx, double fx, double fy, double cx, double cy, double ds, int dense,
+                            void* workspace, double* pts, int* row_offsets);
+/* Open3D voxel_down_sample (pyrapose_node.py:679-680), in two device steps around a stable sort of the keys by the caller:
+ * pp_voxel_keys_f64: keys [n] int64 of floor((p - (min_bound - voxel/2)) / voxel) per axis packed as ix << 42 | iy << 21 | iz
+ * (-1 when an index leaves [0, 2^21)); workspace >= pp_voxel_workspace_bytes (holds min_bound).
+ * pp_voxel_means_f64: perm [n] int64 (the stable sort order of the keys), seg [n_vox+1] int64 (the first sorted position of
+ * each distinct key and n): out_pts [n_vox,3] the mean of each voxel's points summed in original point order; normals
+ * (optional) are summed the same way and renormalised into out_normals (0 when they cancel).  Output order = ascending key
+ * (Open3D's hash order is not reproducible). */
+size_t pp_voxel_workspace_bytes(int n);
+int pp_voxel_keys_f64(pp_ctx* ctx, int n, const double* pts, double voxel, void* workspace, long long* keys);
+int pp_voxel_means_f64(pp_ctx* ctx, int n, const double* pts, const double* normals, const long long* perm, int n_vox,
+                       const long long* seg, double* out_pts, double* out_normals);
+/* Open3D estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) (pyrapose_node.py:681-682, 694, 731): per point the
+ * max_nn (<= 32) nearest points within radius (itself included, |d|^2 <= radius^2, equal distances to the lower index), the
+ * float64 covariance about their mean, the eigenvector of its smallest eigenvalue (6 cyclic Jacobi sweeps), oriented toward
+ * the camera at the origin (n . p <= 0).  Fewer than 3 neighbours: zero normal.  normals [n,3]; neighbors (optional)
+ * [n,max_nn] int32, nearest first, -1 padded.  workspace >= pp_estimate_normals_workspace_bytes (0 today). */
+size_t pp_estimate_normals_workspace_bytes(int n, int max_nn);
+int pp_estimate_normals_f64(pp_ctx* ctx, int n, const double* pts, double radius, int max_nn, void* workspace, double* normals,
+                            int* neighbors);
+/* Open3D registration_icp (pyrapose_node.py:734-735, tless_eval.py:23-65) for n_problems independent problems: problem p owns
+ * source points src_offsets[p] .. src_offsets[p+1] and target points tgt_offsets[p] .. (device int32 offsets into src / tgt
+ * [.,3]); max_source_points >= the largest source count; init [P,4,4] row-major.  Per pass: each source point under the
+ * current pose takes its nearest target (strict <, lowest index wins; in point-to-plane mode targets with a zero normal are
+ * skipped) when |d| <= max_correspondence_distance; fitness = n_corr / n_source, inlier_rmse = sqrt(SSE / n_corr) (0 without
+ * correspondences).  Update: point-to-plane (Open3D's linearisation: J = [(s x n)^T, n^T], r = (s - q) . n, JTJ x = -JTr by
+ * LDL^T, R = Rz(x2) Ry(x1) Rx(x0), t = x[3:]) or point-to-point (Kabsch without scale, proper rotation), applied on the left.
+ * Stop when |d fitness| < relative_fitness and |d rmse| < relative_rmse against the previous pass, or after max_iteration
+ * updates.  Out: R [P,3,3], t [P,3], fitness, inlier_rmse [P] at the final pose, iterations [P] (updates applied),
+ * status [P] (PP_ICP_*), corr [n_source_total] the target index (relative to tgt_offsets[p]) of each source point's
+ * correspondence at the final pose, -1 for none (left untouched for a problem without source or target points).
+ * workspace_bytes >= pp_icp_workspace_bytes. */
+size_t pp_icp_workspace_bytes(int n_problems, int max_source_points);
+int pp_icp_f64(pp_ctx* ctx, int n_problems, const int* src_offsets, const int* tgt_offsets, int max_source_points, const double* src,
+               const double* tgt, const double* tgt_normals, const double* init, double max_correspondence_distance, int max_iteration,
+               double relative_fitness, double relative_rmse, int mode, void* workspace, size_t workspace_bytes, double* R_out,
+               double* t_out, double* fitness, double* inlier_rmse, int* iterations, int* status, int* corr);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,15 @@ _SIGS = {
     "pp_pose_reproj_f64": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pp_pnp_ransac_workspace_bytes": (_sz, [_i, _i]),
     "pp_pnp_ransac_f64": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _d, C.c_ulonglong, _i, _p, _p, _p, _p, _p, _p]),
+    "pp_cloud_from_depth_workspace_bytes": (_sz, [_i, _i]),
+    "pp_cloud_from_depth_f64": (_i, [_p, _i, _i, _p, _p, _i, _i, _p, _p, _d, _d, _d, _d, _d, _i, _p, _p, _p]),
+    "pp_voxel_workspace_bytes": (_sz, [_i]),
+    "pp_voxel_keys_f64": (_i, [_p, _i, _p, _d, _p, _p]),
+    "pp_voxel_means_f64": (_i, [_p, _i, _p, _p, _p, _i, _p, _p, _p]),
+    "pp_estimate_normals_workspace_bytes": (_sz, [_i, _i]),
+    "pp_estimate_normals_f64": (_i, [_p, _i, _p, _d, _i, _p, _p, _p]),
+    "pp_icp_workspace_bytes": (_sz, [_i, _i]),
+    "pp_icp_f64": (_i, [_p, _i, _p, _p, _i, _p, _p, _p, _p, _d, _i, _d, _d, _i, _p, _sz, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 EXPORTS = sorted(_SIGS)

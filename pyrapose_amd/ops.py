@@ -711,3 +711,118 @@ def pose_reproj(ctx, pts, K9, R_est, t_est, R_gt, t_gt):
     out = torch.empty((n,), dtype=torch.float64, device="cuda")
     check(lib.pp_pose_reproj_f64(ctx.handle, n, n_pts, *[_ptr(a) for a in args], _ptr(ws), _ptr(out)), ctx.handle, "pp_pose_reproj_f64")
     return out
+
+
+ICP_MODES = {"point_to_point": 0, "point_to_plane": 1}
+ICP_STATUS = {0: "ok", 1: "too_few_correspondences", 2: "singular"}
+
+
+def cloud_from_depth(ctx, depth, fx, fy, cx, cy, ds=1.0, mask=None, row_idx=None, col_idx=None, dense=False):
+    """Back-projection of a depth image (pp_cloud_from_depth_f64): cuda float32 depth [h,w]; mask cuda uint8 [mh,mw] with cuda
+    int32 row_idx [h] / col_idx [w] into it (None = every pixel).  dense: float64 [h*w,3] with all-NaN rows where z == 0;
+    otherwise the valid masked pixels compacted in row-major order -> (float64 [n,3], row offsets int32 [h+1])."""
+    h, w = (int(s) for s in depth.shape)
+    if depth.dtype != torch.float32 or not depth.is_cuda:
+        raise ValueError("cloud_from_depth: depth must be a cuda float32 [h,w] tensor")
+    depth = depth.contiguous()
+    mh = mw = 0
+    if mask is not None:
+        if mask.dtype != torch.uint8 or mask.dim() != 2 or row_idx is None or col_idx is None:
+            raise ValueError("cloud_from_depth: the mask must be uint8 [mh,mw] with row and column index maps")
+        mh, mw = (int(s) for s in mask.shape)
+        if tuple(row_idx.shape) != (h,) or tuple(col_idx.shape) != (w,) or row_idx.dtype != torch.int32 or col_idx.dtype != torch.int32:
+            raise ValueError("cloud_from_depth: row_idx / col_idx must be int32 [h] / [w]")
+        mask, row_idx, col_idx = mask.contiguous(), row_idx.contiguous(), col_idx.contiguous()
+    pts = torch.empty((h * w, 3), dtype=torch.float64, device=depth.device)
+    offs = torch.empty((h + 1,), dtype=torch.int32, device=depth.device)
+    ws = torch.empty((max(1, lib.pp_cloud_from_depth_workspace_bytes(h, w)),), dtype=torch.uint8, device=depth.device)
+    check(lib.pp_cloud_from_depth_f64(ctx.handle, h, w, _ptr(depth), _ptr(mask), mh, mw, _ptr(row_idx), _ptr(col_idx), float(fx), float(fy),
+                                      float(cx), float(cy), float(ds), int(bool(dense)), _ptr(ws), _ptr(pts), _ptr(offs)),
+          ctx.handle, "pp_cloud_from_depth_f64")
+    if dense:
+        return pts
+    n = int(offs[h].item())
+    return pts[:n], offs
+
+
+def voxel_down_sample(ctx, pts, voxel, normals=None):
+    """Open3D voxel_down_sample (pp_voxel_keys_f64, a stable torch sort, pp_voxel_means_f64): cuda float64 pts [n,3] (and
+    normals [n,3]) -> (means [m,3], renormalised mean normals [m,3] or None), ascending voxel key order."""
+    n = int(pts.shape[0])
+    if pts.dtype != torch.float64 or pts.dim() != 2 or pts.shape[1] != 3 or n < 1:
+        raise ValueError("voxel_down_sample: points must be a non-empty cuda float64 [n,3] tensor")
+    if normals is not None and (normals.dtype != torch.float64 or tuple(normals.shape) != (n, 3)):
+        raise ValueError("voxel_down_sample: normals must be float64 [n,3] like the points")
+    pts = pts.contiguous()
+    normals = normals.contiguous() if normals is not None else None
+    keys = torch.empty((n,), dtype=torch.int64, device=pts.device)
+    ws = torch.empty((max(1, lib.pp_voxel_workspace_bytes(n)),), dtype=torch.uint8, device=pts.device)
+    check(lib.pp_voxel_keys_f64(ctx.handle, n, _ptr(pts), float(voxel), _ptr(ws), _ptr(keys)), ctx.handle, "pp_voxel_keys_f64")
+    sk, perm = torch.sort(keys, stable=True)
+    if bool((sk[:1] < 0).any()):
+        raise ValueError("voxel_down_sample: non-finite points, or more than 2^21 voxels along an axis")
+    _, counts = torch.unique_consecutive(sk, return_counts=True)
+    m = int(counts.numel())
+    seg = torch.zeros((m + 1,), dtype=torch.int64, device=pts.device)
+    seg[1:] = torch.cumsum(counts, 0)
+    out = torch.empty((m, 3), dtype=torch.float64, device=pts.device)
+    out_n = torch.empty((m, 3), dtype=torch.float64, device=pts.device) if normals is not None else None
+    check(lib.pp_voxel_means_f64(ctx.handle, n, _ptr(pts), _ptr(normals), _ptr(perm.contiguous()), m, _ptr(seg), _ptr(out), _ptr(out_n)),
+          ctx.handle, "pp_voxel_means_f64")
+    return out, out_n
+
+
+def estimate_normals(ctx, pts, radius, max_nn, return_neighbors=False):
+    """Open3D estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) (pp_estimate_normals_f64): cuda float64 pts [n,3]
+    -> normals [n,3] toward the camera, zero with fewer than 3 neighbours (and the neighbour lists int32 [n,max_nn])."""
+    n = int(pts.shape[0])
+    if pts.dtype != torch.float64 or pts.dim() != 2 or pts.shape[1] != 3 or n < 1:
+        raise ValueError("estimate_normals: points must be a non-empty cuda float64 [n,3] tensor")
+    pts = pts.contiguous()
+    out = torch.empty((n, 3), dtype=torch.float64, device=pts.device)
+    nbr = torch.empty((n, int(max_nn)), dtype=torch.int32, device=pts.device) if return_neighbors and int(max_nn) > 0 else None
+    check(lib.pp_estimate_normals_f64(ctx.handle, n, _ptr(pts), float(radius), int(max_nn), None, _ptr(out), _ptr(nbr)), ctx.handle,
+          "pp_estimate_normals_f64")
+    return (out, nbr) if return_neighbors else out
+
+
+def icp(ctx, src_offsets, tgt_offsets, src, tgt, init, max_correspondence_distance, max_iteration=30, relative_fitness=1e-6,
+        relative_rmse=1e-6, mode="point_to_plane", tgt_normals=None):
+    """Batched ICP (pp_icp_f64): cuda int32 offsets [P+1] into src [Ns,3] / tgt [Nt,3] (float64, checked on the host), init
+    float64 [P,4,4], tgt_normals [Nt,3] for point_to_plane.
+    -> (R [P,3,3], t [P,3], fitness [P], inlier_rmse [P], iterations int32 [P], status int32 [P], corr int32 [Ns])."""
+    if mode not in ICP_MODES:
+        raise ValueError("icp: unknown estimation %r (point_to_point | point_to_plane)" % (mode,))
+    P = int(src_offsets.numel()) - 1
+    Ns, Nt = int(src.shape[0]), int(tgt.shape[0])
+    for name, a in (("src", src), ("tgt", tgt), ("init", init)) + ((("tgt_normals", tgt_normals),) if tgt_normals is not None else ()):
+        if a.dtype != torch.float64 or not a.is_cuda:
+            raise ValueError("icp: %s must be a cuda float64 tensor" % name)
+    if src.shape != (Ns, 3) or tgt.shape != (Nt, 3) or tuple(init.shape) != (P, 4, 4) or P < 1:
+        raise ValueError("icp: need src [Ns,3], tgt [Nt,3], init [P,4,4] with P >= 1")
+    if tgt_offsets.numel() != P + 1 or src_offsets.dtype != torch.int32 or tgt_offsets.dtype != torch.int32:
+        raise ValueError("icp: offsets must be int32 [P+1]")
+    if mode == "point_to_plane" and (tgt_normals is None or tgt_normals.shape != (Nt, 3)):
+        raise ValueError("icp: point_to_plane needs target normals [Nt,3]")
+    so, to = src_offsets.cpu().numpy(), tgt_offsets.cpu().numpy()
+    if so[0] != 0 or to[0] != 0 or so[-1] != Ns or to[-1] != Nt or (np.diff(so) < 0).any() or (np.diff(to) < 0).any():
+        raise ValueError("icp: offsets must rise from 0 to the number of source / target points")
+    max_source_points = max(int(np.diff(so).max()), 1)
+    dev = src.device
+    args = [a.contiguous() if a is not None else None for a in (src_offsets, tgt_offsets, src, tgt, tgt_normals, init)]
+    nbytes = lib.pp_icp_workspace_bytes(P, max_source_points)
+    if nbytes == 0:
+        raise ValueError("icp: unsupported shape (%d problems)" % P)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    R = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
+    t = torch.empty((P, 3), dtype=torch.float64, device=dev)
+    fit = torch.empty((P,), dtype=torch.float64, device=dev)
+    rmse = torch.empty((P,), dtype=torch.float64, device=dev)
+    iters = torch.empty((P,), dtype=torch.int32, device=dev)
+    status = torch.empty((P,), dtype=torch.int32, device=dev)
+    corr = torch.full((max(Ns, 1),), -1, dtype=torch.int32, device=dev)
+    check(lib.pp_icp_f64(ctx.handle, P, _ptr(args[0]), _ptr(args[1]), max_source_points, _ptr(args[2]), _ptr(args[3]), _ptr(args[4]),
+                         _ptr(args[5]), float(max_correspondence_distance), int(max_iteration), float(relative_fitness), float(relative_rmse),
+                         ICP_MODES[mode], _ptr(ws), nbytes, _ptr(R), _ptr(t), _ptr(fit), _ptr(rmse), _ptr(iters), _ptr(status), _ptr(corr)),
+          ctx.handle, "pp_icp_f64")
+    return R, t, fit, rmse, iters, status, corr[:Ns]

@@ -22,15 +22,29 @@ def quat2mat(q):
     return np.array([[1.0 - (yY + zZ), xY - wZ, xZ + wY], [xY + wZ, 1.0 - (xX + zZ), yZ - wX], [xZ - wY, yZ + wX, 1.0 - (xX + yY)]])
 
 
+def _refine(dets, refine, load_depth, index, mask_out, K, models):
+    """the opt-in ICP step (utils.icp.refine_poses with the keyword arguments in `refine`) on the detections of one image"""
+    from . import icp
+    if load_depth is None:
+        raise ValueError("refine needs load_depth")
+    kw = dict(refine)
+    models = kw.pop("models", models)
+    m = mask_out.cpu().numpy() if hasattr(mask_out, "cpu") else np.asarray(mask_out)
+    return icp.refine_poses(dets, np.asarray(load_depth(index)), m[0], K, models, **kw)
+
+
 def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_diameters, K=None, threshold=0.5, min_votes=10,
-                 symmetric_classes=(), gt_translation_scale=0.001, seed=0):
+                 symmetric_classes=(), gt_translation_scale=0.001, seed=0, refine=None, load_depth=None):
     """generator: load_image / preprocess_image / resize_image / load_annotations / size() (preprocessing/generator.py);
     predict_on_batch: the prediction model's method (x [1,H,W,3] -> [boxes3D, scores, mask]);
     threeD_boxes [C,8,3], model_points: list of [n_c,3], model_diameters [C] -- all in the unit of the estimated translation
     (the reference works in metres and scales the annotation's millimetres by 0.001, :516);
     K: 3x3 intrinsics (default: LineMOD, :423); symmetric_classes: 0-based class ids scored with ADD-S (the reference's
-    cls == 10 or 11, 1-based, :525).  Returns dict(allPoses, trueDets, truePoses, recall, detections, recall_all,
-    detections_all, errors) with the reference's 1-based class indexing."""
+    cls == 10 or 11, 1-based, :525).  refine: None, or the keyword arguments of utils.icp.refine_poses (plus optionally
+    'models': meshes to refine against, default model_points): the detections of each image are then refined against
+    load_depth(index) (millimetres) inside the network's mask output before scoring, and each error tuple gains (refined,
+    fitness).  Returns dict(allPoses, trueDets, truePoses, recall, detections, recall_all, detections_all, errors) with the
+    reference's 1-based class indexing."""
     C = len(model_diameters)
     if K is None:
         K = np.array([[572.4114, 0.0, 325.2611], [0.0, 573.57043, 242.04899], [0.0, 0.0, 1.0]])
@@ -47,6 +61,8 @@ def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_
             allPoses[lab + 1] += 1
         boxes3D, scores, _mask = predict_on_batch(np.expand_dims(image, axis=0))
         poses = pose_decode.poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=threshold, min_votes=min_votes, seed=seed + index)
+        if refine is not None:
+            poses = _refine([d for d in poses if d["cls"] in labels], refine, load_depth, index, _mask, K, model_points)
         for det in poses:
             cls = det["cls"]
             if cls not in labels:  # the reference only scores the annotated class (:327-329)
@@ -57,7 +73,7 @@ def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_
             R_gt, t_gt = quat2mat(pose[3:]), pose[:3] * gt_translation_scale
             fn = pose_error.adi if cls in symmetric_classes else pose_error.add
             err = fn(det["R"], det["t"].reshape(3, 1), R_gt, t_gt.reshape(3, 1), model_points[cls])
-            errors.append((index, cls, float(err)))
+            errors.append((index, cls, float(err)) if refine is None else (index, cls, float(err), det["refined"], det["fitness"]))
             if det["ok"] and err < model_diameters[cls] * 0.1:
                 truePoses[cls + 1] += 1
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -73,7 +89,7 @@ ADD_FRACTIONS = tuple(round(0.05 * k, 2) for k in range(1, 20))  # tless_eval.py
 
 def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, model_diameters, load_depth, K, threshold=0.5, min_votes=10,
                           delta=0.3, tau=20.0, vsd_threshold=0.3, cost_type="step", symmetric_classes=(), gt_translation_scale=0.001,
-                          depth_scale=1000.0, seed=0):
+                          depth_scale=1000.0, seed=0, refine=None):
     """The metric block of tless_eval.py:470-725 (also in occlusion_eval.py / ycbv_eval.py / homebrewed_eval.py) on top of the
     loop of evaluate_add: per detected, annotated class, the rotation / translation errors re / te (correct when re < 5 deg
     and te < 0.05), the reprojection error (< 5 px), VSD against the image's depth (< vsd_threshold) and ADD (ADI for
@@ -83,6 +99,8 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
     model_vsd at tless_eval.py:77); load_depth(index): the scene's depth image [h,w] in millimetres (uint16 or float);
     K: 3x3 intrinsics or a callable index -> 3x3; depth_scale: model / translation unit -> depth unit (VSD runs in
     millimetres with delta / tau as the reference passes them, 0.3 / 20).  One launch per metric per (image, class).
+    refine: None, or the keyword arguments of utils.icp.refine_poses: the detections of each image are then refined against
+    its depth inside the network's mask output before scoring, and each error dict gains 'refined' and 'fitness'.
     Returns dict(allPoses, trueDets, less5, rep_less5, vsd_less_t, add_less [len(ADD_FRACTIONS), C+1], add_fractions, the
     matching rates (counter / allPoses) and errors: one dict per scored detection); index = class id + 1 as in evaluate_add."""
     C = len(model_diameters)
@@ -106,6 +124,8 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
         if not dets:
             continue
         depth = np.asarray(load_depth(index))
+        if refine is not None:
+            dets = _refine(dets, dict(refine, depth_scale=depth_scale), lambda _i: depth, index, _mask, Kc, models)
         for cls in sorted(set(d["cls"] for d in dets)):
             group = [d for d in dets if d["cls"] == cls]
             pose = np.asarray(anno["poses"][labels.index(cls)], np.float64)
@@ -125,6 +145,8 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
                 out["trueDets"][cls + 1] += 1
                 errors.append(dict(image=index, cls=cls, ok=d["ok"], re=float(rd[k]), te=float(xyz[k]), reproj=float(rep[k]),
                                    vsd=float(e_vsd[k]), add=float(e_add[k])))
+                if refine is not None:
+                    errors[-1].update(refined=d["refined"], fitness=d["fitness"])
                 if not d["ok"]:
                     continue
                 out["less5"][cls + 1] += bool(rd[k] < 5.0 and xyz[k] < 0.05)
