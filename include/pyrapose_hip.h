@@ -532,6 +532,55 @@ int pp_icp_f64(pp_ctx* ctx, int n_problems, const int* src_offsets, const int* t
                double relative_fitness, double relative_rmse, int mode, void* workspace, size_t workspace_bytes, double* R_out,
                double* t_out, double* fitness, double* inlier_rmse, int* iterations, int* status, int* corr);
 
+/* ---- uncertainty-weighted PnP refinement of voted poses (csrc/wpnp.hip) ---------------------------------------------
+ * The reference's uncertainty_pnp/ (src/uncertainty_pnp.cpp:7-92, a Ceres problem; wrapped by un_pnp_utils.py:6-121 and
+ * prepared, switched off, at utils/linemod_eval.py:488-496 and utils/occlusion_eval.py:493), batched on the device.  Ceres,
+ * glog, SuiteSparse, cffi and cv2 are not in the reference tree: the minimiser is this library's own Levenberg-Marquardt
+ * (header comment of csrc/wpnp.hip, restated in tests/wpnp_np.py) -- parity with Ceres is unpinned.  Pinned: the cost function
+ * (the functor of uncertainty_pnp.cpp:17-33) and its minimum.  float64, fixed-order reductions: every result is bitwise
+ * independent of the batch it runs in and of the run. */
+#define PP_WPNP_FULL 0       /* W = (cov / n_eff + sigma_floor^2 I)^(-1/2): whitening by the covariance of the mean */
+#define PP_WPNP_ISO 1        /* un_pnp_utils.py:75-83, 103-104: wxx = wyy = 1 / lambda_max(cov), wxy = 0; 0 where cov_xx < 1e-5 */
+#define PP_WPNP_CONVERGED 0
+#define PP_WPNP_MAX_ITER 1
+#define PP_WPNP_TOO_FEW 2    /* fewer than 3 correspondences with a non-zero weight: the start pose is returned */
+#define PP_WPNP_SINGULAR 3   /* a pivot of the damped 6x6 system is not positive and finite: the start pose is returned */
+#define PP_WPNP_BEHIND 4     /* a weighted point behind the camera at the start: the start pose is returned */
+/* From votes to per-corner statistics.  Problem p owns the correspondences offsets[p] .. offsets[p+1] (device int32, multiples
+ * of points_per_vote) of img [N,2], laid out as k_p votes x points_per_vote corners (linemod_eval.py:421-431).  vote_weight
+ * [N / points_per_vote] (the class score of each vote; NULL = 1; votes with a weight <= 0 are left out), inlier_mask [N] uint8
+ * (what pp_pnp_ransac_f64 returns; NULL = all).  Per problem and corner, over the votes left in: wsum [P,ppv], count [P,ppv]
+ * (int32), the weighted mean mu [P,ppv,2], the weighted population covariance about it cov [P,ppv,3] = (xx, xy, yy) (two
+ * passes), n_eff = (sum w)^2 / sum w^2, and wgt [P,ppv,3] = (wxx, wxy, wyy) by `mode` (PP_WPNP_FULL takes sigma_floor, pixels;
+ * lambda_min <= 0, possible only with sigma_floor = 0, gives W = 0).  count < 2: W = 0; count = 0: every output 0.
+ * Deviation: the reference has no such step on the device -- it aggregates votes in numpy where it does at all.
+ * workspace >= pp_vote_stats_workspace_bytes (0 today). */
+size_t pp_vote_stats_workspace_bytes(int n_problems, int points_per_vote);
+int pp_vote_stats_f64(pp_ctx* ctx, int n_problems, const int* offsets_dev, int n_points_total, const double* img,
+                      int points_per_vote, const double* vote_weight, const unsigned char* inlier_mask, int mode,
+                      double sigma_floor, void* workspace, double* wsum, int* count, double* mu, double* cov, double* n_eff,
+                      double* wgt);
+/* uncertainty_pnp() of uncertainty_pnp.cpp:61-92 for n_problems independent problems in one call: problem p owns the
+ * correspondences offsets[p] .. offsets[p+1] of obj [N,3], img [N,2], wgt [N,3] = (wxx, wxy, wyy); K4 [P,4] = (fx, fy, cx,
+ * cy); start R_init [P,3,3] row-major, t_init [P,3] (device; the kernel takes the rotation's logarithm).  Cost: 1/2 sum |W (proj(
+ * Rodrigues(w) x + t) - u)|^2 over the correspondences with a non-zero weight, parameters (w, t) as there.  Minimiser:
+ * Levenberg-Marquardt with Marquardt scaling (diagonal clamped to [1e-6, 1e32], lambda0 = 1e-4, step accepted when the gain ratio
+ * exceeds 1e-3: Ceres' defaults), lambda by Nielsen's rule; a trial pose with a weighted point at p_z <= 0 is rejected.  Stops on
+ * max |g| < gradient_tol, |delta| <= parameter_tol (|x| + parameter_tol), cost decrease <= function_tol * cost, or after
+ * max_iterations trial poses (Ceres' defaults: 1e-10, 1e-8, 1e-6, 50).  Deviations: Ceres' DENSE_SCHUR / trust-region bookkeeping
+ * is not reproduced (same minimum, other iterates); the seed pose is an argument, not cv2.solvePnP(P3P).
+ * Out: R [P,3,3], t [P,3], rvec [P,3]; cost_init, cost_final [P] (cost_final <= cost_init exactly); iterations [P] (passes over
+ * the correspondences); status [P] (PP_WPNP_*); pose_cov [P,6,6] (NULL = skip) = (J^T J)^-1 at the final pose in (w, t) order,
+ * zeros when not invertible or when the start pose is returned.  Problems of at most 64 correspondences run one per wave,
+ * larger ones one per workgroup; the choice depends on the problem alone.
+ * workspace >= pp_pnp_refine_weighted_workspace_bytes (0 today). */
+size_t pp_pnp_refine_weighted_workspace_bytes(int n_problems, int n_points_total);
+int pp_pnp_refine_weighted_f64(pp_ctx* ctx, int n_problems, const int* offsets_dev, int n_points_total, const double* obj,
+                               const double* img, const double* wgt, const double* K4, const double* R_init, const double* t_init,
+                               int max_iterations, double gradient_tol, double parameter_tol, double function_tol, void* workspace,
+                               double* R_out, double* t_out, double* rvec_out, double* cost_init, double* cost_final,
+                               int* iterations, int* status, double* pose_cov);
+
 #ifdef __cplusplus
 }
 #endif

@@ -826,3 +826,89 @@ def icp(ctx, src_offsets, tgt_offsets, src, tgt, init, max_correspondence_distan
                          ICP_MODES[mode], _ptr(ws), nbytes, _ptr(R), _ptr(t), _ptr(fit), _ptr(rmse), _ptr(iters), _ptr(status), _ptr(corr)),
           ctx.handle, "pp_icp_f64")
     return R, t, fit, rmse, iters, status, corr[:Ns]
+
+
+WPNP_MODES = {"full": 0, "iso": 1}
+WPNP_CONVERGED, WPNP_MAX_ITER, WPNP_TOO_FEW, WPNP_SINGULAR, WPNP_BEHIND = 0, 1, 2, 3, 4
+
+
+def _check_offsets(what, offsets, n_total, check, multiple=1):
+    if offsets.dtype != torch.int32 or not offsets.is_cuda or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("%s: offsets must be a cuda int32 tensor [P+1]" % what)
+    if check:
+        o = offsets.cpu().numpy()
+        if o[0] != 0 or o[-1] != n_total or (np.diff(o) < 0).any() or (o % multiple != 0).any():
+            raise ValueError("%s: offsets must rise from 0 to the number of points%s" %
+                             (what, " in multiples of points_per_vote" if multiple > 1 else ""))
+
+
+def vote_stats(ctx, offsets, img, points_per_vote=8, vote_weight=None, inlier_mask=None, mode="full", sigma_floor=0.5,
+               check_offsets=True):
+    """Per-corner statistics of corner votes (pp_vote_stats_f64): cuda tensors offsets int32 [P+1] (multiples of
+    points_per_vote), img float64 [N,2] laid out as votes x points_per_vote, vote_weight float64 [N / points_per_vote] or
+    None, inlier_mask uint8 [N] or None; mode 'full' (W = (cov / n_eff + sigma_floor^2 I)^(-1/2)) or 'iso' (1 / lambda_max).
+    -> dict(wsum [P,ppv], count int32 [P,ppv], mu [P,ppv,2], cov [P,ppv,3], n_eff [P,ppv], wgt [P,ppv,3]).
+    check_offsets=False skips the host-side look at the offsets (for callers that built them on the device)."""
+    if mode not in WPNP_MODES:
+        raise ValueError("vote_stats: unknown mode %r (full | iso)" % (mode,))
+    ppv = int(points_per_vote)
+    if not torch.is_tensor(img) or img.dtype != torch.float64 or not img.is_cuda or img.dim() != 2 or img.shape[1] != 2:
+        raise ValueError("vote_stats: img must be a cuda float64 tensor [N,2]")
+    N = int(img.shape[0])
+    if ppv < 1 or ppv > 64 or N % ppv != 0:
+        raise ValueError("vote_stats: points_per_vote must be 1..64 and divide the number of points")
+    if vote_weight is not None and (vote_weight.dtype != torch.float64 or not vote_weight.is_cuda or tuple(vote_weight.shape) != (N // ppv,)):
+        raise ValueError("vote_stats: vote_weight must be a cuda float64 tensor [N / points_per_vote]")
+    if inlier_mask is not None and (inlier_mask.dtype != torch.uint8 or not inlier_mask.is_cuda or tuple(inlier_mask.shape) != (N,)):
+        raise ValueError("vote_stats: inlier_mask must be a cuda uint8 tensor [N]")
+    if not (0.0 <= float(sigma_floor) < 1e150):
+        raise ValueError("vote_stats: sigma_floor must be finite and >= 0")
+    _check_offsets("vote_stats", offsets, N, check_offsets, ppv)
+    P = int(offsets.numel()) - 1
+    dev = img.device
+    img, offsets = img.contiguous(), offsets.contiguous()
+    vw = vote_weight.contiguous() if vote_weight is not None else None
+    mk = inlier_mask.contiguous() if inlier_mask is not None else None
+    ws = torch.empty((max(1, lib.pp_vote_stats_workspace_bytes(P, ppv)),), dtype=torch.uint8, device=dev)
+    f = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
+    out = dict(wsum=f(P, ppv), count=torch.zeros((P, ppv), dtype=torch.int32, device=dev), mu=f(P, ppv, 2), cov=f(P, ppv, 3),
+               n_eff=f(P, ppv), wgt=f(P, ppv, 3))
+    check(lib.pp_vote_stats_f64(ctx.handle, P, _ptr(offsets), N, _ptr(img), ppv, _ptr(vw), _ptr(mk), WPNP_MODES[mode], float(sigma_floor),
+                                _ptr(ws), _ptr(out["wsum"]), _ptr(out["count"]), _ptr(out["mu"]), _ptr(out["cov"]), _ptr(out["n_eff"]),
+                                _ptr(out["wgt"])), ctx.handle, "pp_vote_stats_f64")
+    return out
+
+
+def pnp_refine_weighted(ctx, offsets, obj, img, wgt, K4, R_init, t_init, max_iterations=50, gradient_tol=1e-10, parameter_tol=1e-8,
+                        function_tol=1e-6, pose_cov=True, check_offsets=True):
+    """Batched weighted Levenberg-Marquardt PnP refinement (pp_pnp_refine_weighted_f64): cuda tensors offsets int32 [P+1],
+    obj float64 [N,3], img [N,2], wgt [N,3] = (wxx, wxy, wyy), K4 [P,4], R_init [P,3,3], t_init [P,3].
+    -> dict(R [P,3,3], t [P,3], rvec [P,3], cost_init [P], cost_final [P], iterations int32 [P], status int32 [P],
+    pose_cov [P,6,6] or None).  Tolerances default to Ceres' (parity with Ceres unpinned: same cost, own minimiser)."""
+    shapes = (("obj", obj, 3), ("img", img, 2), ("wgt", wgt, 3))
+    for name, a, _ in shapes + (("K4", K4, 4), ("R_init", R_init, 3), ("t_init", t_init, 3)):
+        if not torch.is_tensor(a) or a.dtype != torch.float64 or not a.is_cuda:
+            raise ValueError("pnp_refine_weighted: %s must be a cuda float64 tensor" % name)
+    N = int(obj.shape[0]) if obj.dim() == 2 else -1
+    for name, a, w in shapes:
+        if a.dim() != 2 or tuple(a.shape) != (N, w):
+            raise ValueError("pnp_refine_weighted: need obj [N,3], img [N,2], wgt [N,3]")
+    _check_offsets("pnp_refine_weighted", offsets, N, check_offsets)
+    P = int(offsets.numel()) - 1
+    if tuple(K4.shape) != (P, 4) or tuple(R_init.shape) != (P, 3, 3) or tuple(t_init.shape) != (P, 3):
+        raise ValueError("pnp_refine_weighted: need K4 [P,4], R_init [P,3,3], t_init [P,3]")
+    if int(max_iterations) < 0 or not all(float(v) >= 0.0 for v in (gradient_tol, parameter_tol, function_tol)):
+        raise ValueError("pnp_refine_weighted: max_iterations and the tolerances must be >= 0")
+    dev = obj.device
+    args = [a.contiguous() for a in (offsets, obj, img, wgt, K4, R_init, t_init)]
+    ws = torch.empty((max(1, lib.pp_pnp_refine_weighted_workspace_bytes(P, N)),), dtype=torch.uint8, device=dev)
+    f = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
+    out = dict(R=f(P, 3, 3), t=f(P, 3), rvec=f(P, 3), cost_init=f(P), cost_final=f(P),
+               iterations=torch.zeros((P,), dtype=torch.int32, device=dev), status=torch.zeros((P,), dtype=torch.int32, device=dev),
+               pose_cov=f(P, 6, 6) if pose_cov else None)
+    check(lib.pp_pnp_refine_weighted_f64(ctx.handle, P, _ptr(args[0]), N, _ptr(args[1]), _ptr(args[2]), _ptr(args[3]), _ptr(args[4]),
+                                         _ptr(args[5]), _ptr(args[6]), int(max_iterations), float(gradient_tol), float(parameter_tol),
+                                         float(function_tol), _ptr(ws), _ptr(out["R"]), _ptr(out["t"]), _ptr(out["rvec"]),
+                                         _ptr(out["cost_init"]), _ptr(out["cost_final"]), _ptr(out["iterations"]), _ptr(out["status"]),
+                                         _ptr(out["pose_cov"])), ctx.handle, "pp_pnp_refine_weighted_f64")
+    return out

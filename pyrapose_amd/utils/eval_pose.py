@@ -34,7 +34,7 @@ def _refine(dets, refine, load_depth, index, mask_out, K, models):
 
 
 def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_diameters, K=None, threshold=0.5, min_votes=10,
-                 symmetric_classes=(), gt_translation_scale=0.001, seed=0, refine=None, load_depth=None):
+                 symmetric_classes=(), gt_translation_scale=0.001, seed=0, refine=None, load_depth=None, weighting=None):
     """generator: load_image / preprocess_image / resize_image / load_annotations / size() (preprocessing/generator.py);
     predict_on_batch: the prediction model's method (x [1,H,W,3] -> [boxes3D, scores, mask]);
     threeD_boxes [C,8,3], model_points: list of [n_c,3], model_diameters [C] -- all in the unit of the estimated translation
@@ -43,7 +43,8 @@ def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_
     cls == 10 or 11, 1-based, :525).  refine: None, or the keyword arguments of utils.icp.refine_poses (plus optionally
     'models': meshes to refine against, default model_points): the detections of each image are then refined against
     load_depth(index) (millimetres) inside the network's mask output before scoring, and each error tuple gains (refined,
-    fitness).  Returns dict(allPoses, trueDets, truePoses, recall, detections, recall_all, detections_all, errors) with the
+    fitness).  weighting: None, 'corners' or 'scores' -- the uncertainty-weighted refinement of
+    pose_decode.poses_from_outputs on every RANSAC pose (before the optional ICP).  Returns dict(allPoses, trueDets, truePoses, recall, detections, recall_all, detections_all, errors) with the
     reference's 1-based class indexing."""
     C = len(model_diameters)
     if K is None:
@@ -60,7 +61,7 @@ def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_
         for lab in labels:
             allPoses[lab + 1] += 1
         boxes3D, scores, _mask = predict_on_batch(np.expand_dims(image, axis=0))
-        poses = pose_decode.poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=threshold, min_votes=min_votes, seed=seed + index)
+        poses = pose_decode.poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=threshold, min_votes=min_votes, seed=seed + index, weighting=weighting)
         if refine is not None:
             poses = _refine([d for d in poses if d["cls"] in labels], refine, load_depth, index, _mask, K, model_points)
         for det in poses:
@@ -89,7 +90,7 @@ ADD_FRACTIONS = tuple(round(0.05 * k, 2) for k in range(1, 20))  # tless_eval.py
 
 def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, model_diameters, load_depth, K, threshold=0.5, min_votes=10,
                           delta=0.3, tau=20.0, vsd_threshold=0.3, cost_type="step", symmetric_classes=(), gt_translation_scale=0.001,
-                          depth_scale=1000.0, seed=0, refine=None):
+                          depth_scale=1000.0, seed=0, refine=None, weighting=None):
     """The metric block of tless_eval.py:470-725 (also in occlusion_eval.py / ycbv_eval.py / homebrewed_eval.py) on top of the
     loop of evaluate_add: per detected, annotated class, the rotation / translation errors re / te (correct when re < 5 deg
     and te < 0.05), the reprojection error (< 5 px), VSD against the image's depth (< vsd_threshold) and ADD (ADI for
@@ -101,6 +102,7 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
     millimetres with delta / tau as the reference passes them, 0.3 / 20).  One launch per metric per (image, class).
     refine: None, or the keyword arguments of utils.icp.refine_poses: the detections of each image are then refined against
     its depth inside the network's mask output before scoring, and each error dict gains 'refined' and 'fitness'.
+    weighting: as in evaluate_add.
     Returns dict(allPoses, trueDets, less5, rep_less5, vsd_less_t, add_less [len(ADD_FRACTIONS), C+1], add_fractions, the
     matching rates (counter / allPoses) and errors: one dict per scored detection); index = class id + 1 as in evaluate_add."""
     C = len(model_diameters)
@@ -119,7 +121,7 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
             out["allPoses"][lab + 1] += 1
         Kc = np.asarray(K(index) if callable(K) else K, np.float64).reshape(3, 3)
         boxes3D, scores, _mask = predict_on_batch(np.expand_dims(image, axis=0))
-        poses = pose_decode.poses_from_outputs(boxes3D, scores, threeD_boxes, Kc, threshold=threshold, min_votes=min_votes, seed=seed + index)
+        poses = pose_decode.poses_from_outputs(boxes3D, scores, threeD_boxes, Kc, threshold=threshold, min_votes=min_votes, seed=seed + index, weighting=weighting)
         dets = [d for d in poses if d["cls"] in labels]  # the reference only scores the annotated classes
         if not dets:
             continue

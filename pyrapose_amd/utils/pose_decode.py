@@ -15,11 +15,22 @@ from ..runtime import default_context
 
 
 def poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=0.5, min_votes=10, iterations=300, reproj_error=5.0, seed=0,
-                       ctx=None):
+                       ctx=None, weighting=None, sigma_floor=0.5):
     """boxes3D [B,N,16], scores [B,N,C] (numpy or cuda float32 tensors: predict_on_batch outputs); threeD_boxes [C,8,3]
     cuboid corners per class (model units); K 3x3 or [B,3,3].  Returns one dict per (image, class) that reached
     `min_votes` votes, image-major then class ascending like the reference loop:
-    {image, cls (0-based), votes (ascending anchor indices), ok, R [3,3], t [3], inliers (indices into votes x 8 corners)}."""
+    {image, cls (0-based), votes (ascending anchor indices), ok, R [3,3], t [3], inliers (indices into votes x 8 corners)}.
+
+    weighting: None (the RANSAC pose, as above), or an uncertainty-weighted refinement of it on the device (csrc/wpnp.hip; the
+    call the reference prepares at linemod_eval.py:488-496):
+      'corners': per corner the score-weighted mean of the RANSAC-inlier votes and W = (cov / n_eff + sigma_floor^2 I)^(-1/2)
+                 (ops.vote_stats), then the solver on the 8 (corner, mean, W) correspondences;
+      'scores':  every inlier vote stays a correspondence with wxx = wyy = its class score, wxy = 0 (pose_weights there).
+    The dicts then gain R_ransac, t_ransac, cost (of the returned pose), cost_ransac (of the RANSAC pose under the same
+    weights), pose_cov [6,6] and refine_status (ops.WPNP_*); a problem whose RANSAC failed or whose refinement did not end
+    converged / at max_iterations keeps the RANSAC pose."""
+    if weighting not in (None, "corners", "scores"):
+        raise ValueError("weighting must be None, 'corners' or 'scores'")
     ctx = ctx or default_context()
     dev = lambda a: a.cuda() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
     boxes3D, scores = dev(boxes3D).float().contiguous(), dev(scores).float().contiguous()
@@ -46,6 +57,25 @@ def poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=0.5, min_vote
     pb, pc = torch.nonzero(sel, as_tuple=True)
     K_all = torch.as_tensor(np.stack([[Kb[0, 0], Kb[1, 1], Kb[0, 2], Kb[1, 2]] for Kb in Ks]), dtype=torch.float64, device="cuda")
     R, t, n_in, mask, ok = ops.pnp_ransac(ctx, offs, obj.contiguous(), img.contiguous(), K_all[pb].contiguous(), iterations, reproj_error, seed, 8)
+    extra = None
+    if weighting is not None:
+        P = int(k.numel())
+        score = scores[b_of, anchor, c_of].double().contiguous()               # one per vote, (b, c, vote) order
+        K_p = K_all[pb].contiguous()
+        if weighting == "corners":
+            st = ops.vote_stats(ctx, offs, img.contiguous(), 8, score, mask, "full", float(sigma_floor), check_offsets=False)
+            o8 = (8 * torch.arange(P + 1, device="cuda")).to(torch.int32)
+            ref = ops.pnp_refine_weighted(ctx, o8, corners[pc].reshape(-1, 3).contiguous(), st["mu"].reshape(-1, 2), st["wgt"].reshape(-1, 3),
+                                          K_p, R, t, check_offsets=False)
+        else:
+            w = score.repeat_interleave(8) * mask.double()
+            wgt = torch.stack([w, torch.zeros_like(w), w], 1).contiguous()
+            ref = ops.pnp_refine_weighted(ctx, offs, obj.contiguous(), img.contiguous(), wgt, K_p, R, t, check_offsets=False)
+        use = (ok != 0) & (ref["status"] <= ops.WPNP_MAX_ITER)
+        extra = dict(R_ransac=R.cpu().numpy(), t_ransac=t.cpu().numpy(), cost_ransac=ref["cost_init"].cpu().numpy(),
+                     cost=torch.where(use, ref["cost_final"], ref["cost_init"]).cpu().numpy(), pose_cov=ref["pose_cov"].cpu().numpy(),
+                     refine_status=ref["status"].cpu().numpy())
+        R, t = torch.where(use[:, None, None], ref["R"], R), torch.where(use[:, None], ref["t"], t)
     R, t, mask, ok = R.cpu().numpy(), t.cpu().numpy(), mask.cpu().numpy(), ok.cpu().numpy()
     offs_h, anchor_h, k_h = offs.cpu().numpy(), anchor.cpu().numpy(), k.cpu().numpy()
     pb, pc = pb.cpu().numpy(), pc.cpu().numpy()
@@ -53,5 +83,8 @@ def poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=0.5, min_vote
     for p in range(len(k_h)):
         out.append(dict(image=int(pb[p]), cls=int(pc[p]), votes=anchor_h[v0: v0 + k_h[p]], ok=bool(ok[p]), R=R[p], t=t[p],
                         inliers=np.nonzero(mask[offs_h[p]:offs_h[p + 1]])[0]))
+        if extra is not None:
+            out[-1].update(R_ransac=extra["R_ransac"][p], t_ransac=extra["t_ransac"][p], cost=float(extra["cost"][p]),
+                           cost_ransac=float(extra["cost_ransac"][p]), pose_cov=extra["pose_cov"][p], refine_status=int(extra["refine_status"][p]))
         v0 += int(k_h[p])
     return out
