@@ -47,12 +47,6 @@ int pp_ctx_set_stream(pp_ctx* ctx, void* hip_stream);
  * finishing pass adds the slices in a fixed order and applies bias / residual / mask / ReLU (deterministic, no
  * atomics).  A launch uses S * rows * ld_out * 4 bytes.  One buffer per context (= per stream); NULL, 0 removes it. */
 int pp_ctx_set_workspace(pp_ctx* ctx, void* device_buffer, size_t bytes);
-/* One-shot: the NEXT pp_conv2d_nhwc_fwd_bf16x3 / pp_conv2d_nhwc_bwd_data_bf16x3 call on this context, which must be given
- * its gathered operand (x / dy) as float32, also writes that operand's bf16 (hi, lo) split into these planes -- the
- * output of pp_split_planes_bf16x3 on it ([rows][ld] geometry; columns past the channels the conv reads are left
- * untouched).  The kernel has the converted values in registers anyway; the weight-gradient launch of the same layer
- * (pp_conv2d_nhwc_bwd_weight_bf16x3 with all four planes) then skips its own conversion.  NULL, NULL cancels. */
-int pp_ctx_set_split_capture(pp_ctx* ctx, void* hi, void* lo);
 /* Row-block skip for sparse gradients.  The 3D-box loss (losses.py:321-408, orthogonal_l1) keeps only the rows with anchor
  * state 1, so the gradient that flows back through the 3D-box head is exactly zero away from the positive anchors (and
  * stays so layer after layer, dilated by one pixel per 3x3 conv).  pp_row_block_list scans a gradient tensor x [rows][ld]
@@ -61,13 +55,7 @@ int pp_ctx_set_split_capture(pp_ctx* ctx, void* hi, void* lo);
  * the first halves are the result, the second halves scratch of the bwd-data launch that takes the hint (after that launch the
  * second nb bytes of `flags` flag every block of dx that may hold a non-zero: the dilated blocks, or all of them when the
  * launch ran dense; without an addend dx is zero in the others -- pp_row_block_list_planes_within takes that as `within`).
- * pp_ctx_set_row_block_skip is one-shot: the NEXT pp_conv2d_nhwc_bwd_weight_bf16x3 call on this context (float32 operands)
- * reduces over the listed blocks of dy only; the NEXT pp_conv2d_nhwc_bwd_data_bf16x3 call (3x3, stride 1, pad 1) computes
- * only the 32-row blocks of dx that a flagged block of dy can reach (dilated by one pixel in 2-D, compacted four to a tile)
- * and writes mask?(addend or 0) to the others.  A
- * block of zero rows contributes exactly 0.0 to every sum: the results are those of the dense launch (up to the order of
- * the float32 atomics between reduction splits; the one exception is an Inf / NaN operand opposite an exact zero, which the
- * dense launch turns into NaN and this one into 0).  Launches that cannot use the hint run dense.  NULL, NULL cancels. */
+ * The pair goes to a backward launch as the skip_flags / skip_list fields of its pp_conv_opts (below). */
 int pp_row_block_list(pp_ctx* ctx, const float* x, int rows, int ld, int cols, unsigned char* flags, int* list);
 /* the same scan of a tensor stored as bf16 (hi, lo) planes ([rows][ld] each) */
 int pp_row_block_list_planes(pp_ctx* ctx, const void* x_hi, const void* x_lo, int rows, int ld, int cols, unsigned char* flags, int* list);
@@ -76,22 +64,6 @@ int pp_row_block_list_planes(pp_ctx* ctx, const void* x_hi, const void* x_lo, in
  * second n_blocks bytes of ITS flags buffer), so the scan for the next layer reads 10-25 % of the tensor instead of all of it. */
 int pp_row_block_list_planes_within(pp_ctx* ctx, const void* x_hi, const void* x_lo, int rows, int ld, int cols, const unsigned char* within,
                                     unsigned char* flags, int* list);
-/* One-shot: the NEXT pp_conv2d_nhwc_fwd_bf16x3 (residual) / pp_conv2d_nhwc_bwd_data_bf16x3 (addend, relu_src) call on this
- * context reads those epilogue operands from bf16 (hi, lo) planes instead of float32 tensors -- the storage format of every
- * activation and gradient a bf16x3 conv produces when its output is requested as planes only (value = hi + lo, 4 bytes per
- * element like float32, so no conv ever converts inside its loop).  The call's ld_res / ld_add / ld_rs arguments give the
- * row pitch of the planes; its float32 residual / addend / relu_src argument must then be NULL.  Of the ReLU source only the
- * hi plane is read (hi > 0 <=> value > 0).  Any of the three may be NULL (add_hi and add_lo go together). */
-int pp_ctx_set_epilogue_planes(pp_ctx* ctx, const void* add_hi, const void* add_lo, const void* mask_hi);
-int pp_ctx_set_row_block_skip(pp_ctx* ctx, const unsigned char* flags, const int* list);
-/* Lazy sparse gradients (one-shot, for the NEXT bwd-data / bwd-weight call on this context, beside pp_ctx_set_row_block_skip).
- * lazy_out: a bwd-data call that runs the listed-block launch leaves the rows of dx outside the blocks it computes UNTOUCHED instead
- * of writing mask?(addend or 0) to them -- legitimate when every reader of that dx goes by flags: a scan restricted to the computed
- * blocks (pp_row_block_list_planes_within with the second half of this call's flags), a listed-block bwd-weight, a listed-block
- * bwd-data (whose gather never fetches a row outside the flagged blocks of its dy).  lazy_in: the dy of the call is such a tensor;
- * the call FAILS (PP_ERR_ARG) instead of running a launch that would read the unwritten rows.  The 3D-box head's backward uses
- * both: four fill passes of 103 MB per training step are not made. */
-int pp_ctx_set_row_block_lazy(pp_ctx* ctx, int lazy_out, int lazy_in);
 const char* pp_last_error_string(pp_ctx* ctx);
 const char* pp_version(void);
 /* number of compute units / name of the device the ctx is bound to (for bench metadata) */
@@ -168,13 +140,11 @@ int pp_conv_split_weights_bf16x3_batch(pp_ctx* ctx, int n_jobs, const pp_split_j
  * pp_positive_row_blocks: flags[b] = 1 when the 32-row block b of the head's row space holds an anchor whose last target column
  * (state, column stride - 1 of y_true [n_img][cells][A][stride]) is 1.  pp_row_block_dilate: the blocks within one pixel of a
  * flagged block (what a 3x3 stride-1 conv d reads to produce the flagged blocks): applied once per layer from the head's output
- * back to its first conv.  pp_ctx_set_row_block_out is one-shot: the NEXT pp_conv2d_nhwc_fwd_bf16x3 call on this context (3x3,
- * stride 1, pad 1, plane-stored input, no residual) computes the flagged 32-row output blocks only (compacted four to a tile;
- * list = scratch of n_blocks + 1 ints) and leaves every other output row as it is.  Exact for the loss, its gradient and the
- * weight gradients (the backward reads those activations only where its own row-block skip goes); the caller opts in. */
+ * back to its first conv.  The flags of a layer go to its forward launch as the
+ * out_flags field of its pp_conv_opts (below).  Exact for the loss, its gradient and the weight gradients (the backward reads
+ * those activations only where its own row-block skip goes); the caller opts in. */
 int pp_positive_row_blocks(pp_ctx* ctx, const pp_rowspace* rs, int A, int stride, const float* y_true, unsigned char* flags);
 int pp_row_block_dilate(pp_ctx* ctx, const pp_conv_desc* d, const unsigned char* in_flags, unsigned char* out_flags);
-int pp_ctx_set_row_block_out(pp_ctx* ctx, const unsigned char* flags, int* list);
 /* f32 tensor of n elements (n % 8 == 0) -> bf16 (hi, lo) planes with the same [rows][ld] geometry.  Convs that are
  * given planes for their gathered operand skip the conversion inside the kernel (the f32 pointer may then be NULL). */
 int pp_split_planes_bf16x3(pp_ctx* ctx, size_t n, const float* src, void* hi, void* lo);
@@ -203,21 +173,69 @@ int pp_grad_scale_from_counts_adj(pp_ctx* ctx, const int* counts_dev, int n_coun
 int pp_split_planes_scaled_bf16x3(pp_ctx* ctx, size_t n, const float* src, void* hi, void* lo, const float* scale_dev);
 int pp_ctx_set_grad_scale(pp_ctx* ctx, const float* scale2_dev);
 
+/* Per-launch options of the three *_bf16x3 convolution entry points below: passed with the call (NULL = all zero), read
+ * before anything is launched, never kept.  A field the entry point does not consume must be NULL / 0: PP_ERR_ARG. */
+typedef struct pp_conv_opts {
+  /* Split capture (fwd, bwd-data): the call, which must be given its gathered operand (x / dy) as float32, also writes that
+   * operand's bf16 (hi, lo) split into these planes -- the output of pp_split_planes_bf16x3 on it ([rows][ld] geometry; columns
+   * past the channels the conv reads are left untouched).  The kernel has the converted values in registers anyway; the
+   * weight-gradient launch of the same layer (all four planes) then skips its own conversion.  hi and lo go together. */
+  void* capture_hi;
+  void* capture_lo;
+  /* Epilogue planes (fwd: residual; bwd-data: addend, relu_src): the call reads those epilogue operands from bf16 (hi, lo)
+   * planes instead of float32 tensors -- the storage format of every activation and gradient a bf16x3 conv produces when its
+   * output is requested as planes only (value = hi + lo, 4 bytes per element like float32, so no conv ever converts inside its
+   * loop).  The call's ld_res / ld_add / ld_rs arguments give the row pitch of the planes; its float32 residual / addend /
+   * relu_src argument must then be NULL.  Of the ReLU source only the hi plane is read (hi > 0 <=> value > 0; bwd-data only).
+   * Any of the three may be NULL (add_hi and add_lo go together). */
+  const void* add_hi;
+  const void* add_lo;
+  const void* mask_hi;
+  /* Row-block skip (bwd-data, bwd-weight): the (flags, list) pair pp_row_block_list wrote for the call's dy.  The bwd-weight
+   * call reduces over the listed blocks of dy only; the bwd-data call (3x3, stride 1, pad 1) computes only the 32-row blocks of
+   * dx that a flagged block of dy can reach (dilated by one pixel in 2-D, compacted four to a tile) and writes mask?(addend or
+   * 0) to the others -- and WRITES the second halves of both buffers (not const).  A block of zero rows contributes exactly 0.0
+   * to every sum: the results are those of the dense launch (up to the order of the float32 atomics between reduction splits;
+   * the one exception is an Inf / NaN operand opposite an exact zero, which the dense launch turns into NaN and this one into
+   * 0).  Launches that cannot use the pair run dense. */
+  unsigned char* skip_flags;
+  int* skip_list;
+  /* Sparse forward (fwd; 3x3, stride 1, pad 1, plane-stored input, no residual): the call computes the flagged 32-row output
+   * blocks only (compacted four to a tile; out_list = scratch of n_blocks + 1 ints) and leaves every other output row as it is.
+   * flags and list go together. */
+  const unsigned char* out_flags;
+  int* out_list;
+  /* Lazy sparse gradients (beside skip_flags and skip_list; without them: PP_ERR_ARG).  lazy_out (bwd-data): a call that runs
+   * the listed-block launch leaves the rows of dx outside the blocks it computes UNTOUCHED instead of writing mask?(addend or 0)
+   * to them -- legitimate when every reader of that dx goes by flags: a scan restricted to the computed blocks
+   * (pp_row_block_list_planes_within with the second half of this call's flags), a listed-block bwd-weight, a listed-block
+   * bwd-data (whose gather never fetches a row outside the flagged blocks of its dy).  lazy_in (bwd-data, bwd-weight): the dy of
+   * the call is such a tensor; the call FAILS (PP_ERR_ARG) instead of running a launch that would read the unwritten rows.  The
+   * 3D-box head's backward uses both: four fill passes of 103 MB per training step are not made. */
+  int lazy_out;
+  int lazy_in;
+} pp_conv_opts;
+#ifdef __cplusplus
+static_assert(sizeof(pp_conv_opts) == 9 * sizeof(void*) + 2 * sizeof(int), "pp_conv_opts: pointers, then ints, no padding");
+#else
+_Static_assert(sizeof(pp_conv_opts) == 9 * sizeof(void*) + 2 * sizeof(int), "pp_conv_opts: pointers, then ints, no padding");
+#endif
+
 int pp_conv2d_nhwc_fwd_bf16x3(pp_ctx* ctx, const pp_conv_desc* d, const float* x, const void* x_hi, const void* x_lo,
                               const void* w_fwd_hi, const void* w_fwd_lo, const float* bias, const float* residual,
-                              int ld_res, int relu, float* y, void* y_hi, void* y_lo);
+                              int ld_res, int relu, float* y, void* y_hi, void* y_lo, const pp_conv_opts* opts);
 /* y_hi / y_lo (may be NULL): the epilogue also writes the output pre-split, so that the consumer convs skip the split.
  * With planes given, y (fwd) / dx (bwd_data) may be NULL: the output then exists only as planes. */
 /* dy rows need ld_y >= cout rounded up to 32 with zero padding. */
 int pp_conv2d_nhwc_bwd_data_bf16x3(pp_ctx* ctx, const pp_conv_desc* d, const float* dy, const void* dy_hi,
                                    const void* dy_lo, const void* w_dgrad_hi, const void* w_dgrad_lo,
                                    const float* addend, int ld_add, const float* relu_src, int ld_rs, float* dx,
-                                   void* dx_hi, void* dx_lo);
+                                   void* dx_hi, void* dx_lo, const pp_conv_opts* opts);
 /* dw += x^T (*) dy; operands either f32 (split on the fly) or all four planes; same contract as
  * pp_conv2d_nhwc_bwd_weight, cin % 64 == 0. */
 int pp_conv2d_nhwc_bwd_weight_bf16x3(pp_ctx* ctx, const pp_conv_desc* d, const float* x, const float* dy,
                                      const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo,
-                                     float* dw, float* dbias);
+                                     float* dw, float* dbias, const pp_conv_opts* opts);
 
 /* ---- data-parallel gradient exchange on RCCL -----------------------------------------------------------
  * The reference trains on one device (bin/train.py:82-89: the multi_gpu_model branch is disabled); what its single-device

@@ -58,6 +58,13 @@ class TView(C.Structure):
     _fields_ = [("f32", C.c_void_p), ("hi", C.c_void_p), ("lo", C.c_void_p)]
 
 
+class ConvOpts(C.Structure):
+    """pp_conv_opts: the per-launch options of the three *_bf16x3 convolution entry points"""
+    _fields_ = [("capture_hi", C.c_void_p), ("capture_lo", C.c_void_p), ("add_hi", C.c_void_p), ("add_lo", C.c_void_p),
+                ("mask_hi", C.c_void_p), ("skip_flags", C.c_void_p), ("skip_list", C.c_void_p), ("out_flags", C.c_void_p),
+                ("out_list", C.c_void_p), ("lazy_out", C.c_int), ("lazy_in", C.c_int)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -70,6 +77,8 @@ def _load():
 
 
 lib = _load()
+if hasattr(lib, "pp_ctx_set_split_capture"):  # (such a build would take the new conv calls and silently ignore their options)
+    raise ImportError("pyrapose_amd: %s predates pp_conv_opts (it still exports pp_ctx_set_split_capture): rebuild it" % LIB_PATH)
 
 _p = C.c_void_p
 _i = C.c_int
@@ -104,16 +113,11 @@ _SIGS = {
     "pp_allreduce_bucket": (_i, [_p, _p, _p, C.c_size_t]),
     "pp_allreduce_counts": (_i, [_p, _p, _p, _i]),
     "pp_ctx_set_workspace": (_i, [_p, _p, C.c_size_t]),
-    "pp_ctx_set_split_capture": (_i, [_p, _p, _p]),
     "pp_row_block_list": (_i, [_p, _p, _i, _i, _i, _p, _p]),
-    "pp_ctx_set_row_block_skip": (_i, [_p, _p, _p]),
-    "pp_ctx_set_row_block_out": (_i, [_p, _p, _p]),
-    "pp_ctx_set_row_block_lazy": (_i, [_p, _i, _i]),
     "pp_positive_row_blocks": (_i, [_p, _p, _i, _i, _p, _p]),
     "pp_row_block_dilate": (_i, [_p, _p, _p, _p]),
     "pp_row_block_list_planes": (_i, [_p, _p, _p, _i, _i, _i, _p, _p]),
     "pp_row_block_list_planes_within": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
-    "pp_ctx_set_epilogue_planes": (_i, [_p, _p, _p, _p]),
     "pp_add_n_v": (_i, [_p, _sz, C.POINTER(TView), C.POINTER(TView), C.POINTER(TView), C.POINTER(TView)]),
     "pp_relu_fwd_v": (_i, [_p, _sz, C.POINTER(TView), C.POINTER(TView)]),
     "pp_upsample_nearest_add_fwd_v": (_i, [_p, _i, _i, _i, _i, _i, _i, C.POINTER(TView), C.POINTER(TView), C.POINTER(TView)]),
@@ -123,9 +127,9 @@ _SIGS = {
     "pp_resize_scale": (_i, [_i, _i, _i, _i, C.POINTER(_d)]),
     "pp_resize_linear_u8": (_i, [_p, _i, _i, _i, _i, _d, _i, _i, _p, _p]),
     "pp_conv_split_weights_bf16x3_batch": (_i, [_p, _i, _p, _i]),
-    "pp_conv2d_nhwc_fwd_bf16x3": (_i, [_p, C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
-    "pp_conv2d_nhwc_bwd_data_bf16x3": (_i, [_p, C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p]),
-    "pp_conv2d_nhwc_bwd_weight_bf16x3": (_i, [_p, C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _p, _p]),
+    "pp_conv2d_nhwc_fwd_bf16x3": (_i, [_p, C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, C.POINTER(ConvOpts)]),
+    "pp_conv2d_nhwc_bwd_data_bf16x3": (_i, [_p, C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, C.POINTER(ConvOpts)]),
+    "pp_conv2d_nhwc_bwd_weight_bf16x3": (_i, [_p, C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _p, _p, C.POINTER(ConvOpts)]),
     "pp_maxpool3x3s2_fwd": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p]),
     "pp_upsample_nearest_add_fwd": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     "pp_upsample_nearest_add_bwd": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),

@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 8) ? 2 : ((TM * TN == 4) ? 3 : 4))
 // Measured and NOT kept: the same loop on v_mfma_f32_16x16x32_bf16 (48 instead of 24 MFMAs per step, lane = (row, octet)
 // staging map, un-rotated image): bit-identical results, 20 % slower on every head shape (255-295 vs 325-355 TFLOP/s).
 // RL (row list): the launch computes only the 32-row output blocks of a list (g_rl[0] = count, g_rl[1 ..] ascending block
-// indices; pp_ctx_set_row_block_skip: the blocks of the data gradient that a non-zero of dy can reach), four (two) blocks
+// indices; pp_conv_opts.skip_flags: the blocks of the data gradient that a non-zero of dy can reach), four (two) blocks
 // to a tile; the grid is sized for the dense case and workgroups past the end of the list leave at once.  Rows keep their
 // own gather offsets (this loop never assumed that the rows of a tile are consecutive); rl_fill_kernel writes the rest.
 template <int TM, int TN, bool AP, bool OP, bool SC = false, bool RL = false>
@@ -269,7 +269,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 8) ? 2 : ((TM * TN == 4) ? 3 : 4))
         const int sy = r.ybase + ty * p.tsign, sx = r.xbase + tx * p.tsign;
         bool ok = r.ok && (unsigned)sy < (unsigned)r.SH && (unsigned)sx < (unsigned)r.SW;
         // RL with the flags of the gathered tensor (sparse bwd-data): a source row outside the flagged 32-row blocks IS zero by
-        // the meaning of the flags -- it is not fetched, so a producer may leave such rows unwritten (pp_ctx_set_row_block_lazy)
+        // the meaning of the flags -- it is not fetched, so a producer may leave such rows unwritten (pp_conv_opts.lazy_out)
         if (RL && g_srcflags && ok) ok = g_srcflags[(r.rowbase + sy * r.SW + sx) >> 5] != 0;
         if (ok) v |= 1u << t;
       }
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 8) ? 2 : ((TM * TN == 4) ? 3 : 4))
 // CAP: the bf16 (hi, lo) split of the gathered f32 operand is also written out ([rows][ld_src] planes, the geometry of
 // pp_split_planes_bf16x3): for the centre kernel row (dy = 0: the staged rows are the tile's own rows; the BM - 2 inner
 // rows of all tiles cover every row once) the workgroups store the registers they have just converted, the output-channel
-// tiles of one row tile taking turns over the channel chunks.  The weight-gradient launch of the same layer then reads both operands pre-split (pp_ctx_set_split_capture).
+// tiles of one row tile taking turns over the channel chunks.  The weight-gradient launch of the same layer then reads both operands pre-split (pp_conv_opts.capture_hi / capture_lo).
 // AP: the gathered operand is stored as bf16 (hi, lo) planes (g_a = hi, g_a1 = lo; ld_src % 8 == 0): the staging threads move
 // 16 B of each plane per row and chunk -- the same bytes as the two f32 quads -- and nothing is converted in the loop.
 // OP: the output tile is written as planes (g_ohi / g_olo; also as f32 when g_out != NULL).
@@ -451,7 +451,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 8) ? 2 : ((TM * TN == 4) ? 3 : 4))
   const int g_begin = (int)((long long)all_groups * split / splits);
   int g_end = (int)((long long)all_groups * (split + 1) / splits);
   if (g_flags) {
-    // row-block skip (pp_ctx_set_row_block_skip): when none of the 32-row blocks of the gathered tensor that this tile can
+    // row-block skip (pp_conv_opts.skip_flags): when none of the 32-row blocks of the gathered tensor that this tile can
     // reach (its rows +- one image row +- one pixel; skip_halo = widest level + 1) holds a non-zero, the sum is exactly
     // zero: no k-loop, the epilogue still writes bias / addend / mask.  Workgroup-uniform.
     int lo = m0 - skip_halo, hi = m0 + BM - 1 + skip_halo;
@@ -1358,7 +1358,7 @@ __global__ void row_block_compact_kernel(const unsigned char* __restrict__ flags
 // ws / ws_bytes: the split-K scratch (may be NULL).  The listed tiles are few (a fifth of the rows on the bench targets: ~320
 // workgroups of 144 k-steps each on 256 CUs, every one of them alone with its load latencies): with a scratch buffer the
 // reduction is split two ways (PP_SPARSE_DGRAD_SPLITS) and rl_splitk_finish_kernel adds the slices of the listed blocks.
-// dy_flags == NULL (forward, pp_ctx_set_row_block_out): out_flags are given -- no dilation, and the rows of the other blocks
+// dy_flags == NULL (forward, pp_conv_opts.out_flags): out_flags are given -- no dilation, and the rows of the other blocks
 // are left as they are (fill = false).
 template <int TM, int TN>
 static void launch_igemm3_rowlist(hipStream_t st, IgemmParams& p, const void* ahi, const void* alo, const void* whi, const void* wlo, int w_rows,
@@ -1413,7 +1413,7 @@ static void split_capture_pass(hipStream_t st, const IgemmParams& p, void* chi, 
   hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)blocks), dim3(256), 0, st, n8, (const float4*)p.src, (uint4*)chi, (uint4*)clo, (const float*)nullptr);
 }
 
-// chi / clo (may be NULL): also write the bf16 split of the gathered f32 operand (pp_ctx_set_split_capture) -- inside the
+// chi / clo (may be NULL): also write the bf16 split of the gathered f32 operand (pp_conv_opts.capture_hi / capture_lo) -- inside the
 // tap-row-reuse kernel where that one runs, by a separate pass over the operand otherwise
 template <int TM, int TN>
 static void launch_igemm3(hipStream_t st, IgemmParams& p, const void* ahi, const void* alo, const void* whi, const void* wlo, int w_rows,
@@ -1705,17 +1705,13 @@ static void dispatch3(pp_ctx* ctx, IgemmParams& p, const void* ahi, const void* 
 }  // namespace
 extern "C" int PP_API(pp_conv2d_nhwc_fwd_bf16x3)(pp_ctx* ctx, const pp_conv_desc* d, const float* x, const void* x_hi, const void* x_lo,
                                          const void* w_hi, const void* w_lo, const float* bias, const float* residual, int ld_res,
-                                         int relu, float* y, void* y_hi, void* y_lo) {
+                                         int relu, float* y, void* y_hi, void* y_lo, const pp_conv_opts* opts) {
   PP_REQUIRE_CTX(ctx);
-  void *chi = ctx->cap_hi, *clo = ctx->cap_lo;  // one-shot (pp_ctx_set_split_capture)
-  ctx->cap_hi = ctx->cap_lo = nullptr;
-  const void *ep_ah = ctx->ep_add_hi, *ep_al = ctx->ep_add_lo;  // one-shot (pp_ctx_set_epilogue_planes): the residual as planes
-  ctx->ep_add_hi = ctx->ep_add_lo = ctx->ep_mask_hi = nullptr;
-  const unsigned char* out_flags = ctx->out_flags;  // one-shot (pp_ctx_set_row_block_out)
-  int* out_list = ctx->out_list;
-  ctx->out_flags = nullptr;
-  ctx->out_list = nullptr;
-  int rc = check_desc(ctx, d, "pp_conv2d_nhwc_fwd_bf16x3");
+  int rc = pp_conv_opts_take(ctx, opts, PP_OPT_CAPTURE | PP_OPT_ADD | PP_OPT_OUT, "pp_conv2d_nhwc_fwd_bf16x3");
+  if (rc) return rc;
+  void *const chi = opts->capture_hi, *const clo = opts->capture_lo;
+  const void *const ep_ah = opts->add_hi, *const ep_al = opts->add_lo;  // the residual as planes
+  rc = check_desc(ctx, d, "pp_conv2d_nhwc_fwd_bf16x3");
   PP_CHECK_ARG(ctx, !(ep_ah && residual), PP_ERR_ARG, "pp_conv2d_nhwc_fwd_bf16x3: residual given both as f32 and as planes");
   PP_CHECK_ARG(ctx, !ep_ah || (ld_res % 4 == 0 && ld_res >= ((d->cout + 3) & ~3)), PP_ERR_SHAPE, "pp_conv2d_nhwc_fwd_bf16x3: residual planes");
   if (rc) return rc;
@@ -1723,7 +1719,7 @@ extern "C" int PP_API(pp_conv2d_nhwc_fwd_bf16x3)(pp_ctx* ctx, const pp_conv_desc
   PP_CHECK_ARG(ctx, (x || (x_hi && x_lo)) && w_hi && w_lo && (y || (y_hi && y_lo)), PP_ERR_ARG, "pp_conv2d_nhwc_fwd_bf16x3: null tensor");
   PP_CHECK_ARG(ctx, (x_hi == nullptr) == (x_lo == nullptr), PP_ERR_ARG, "pp_conv2d_nhwc_fwd_bf16x3: x_hi and x_lo go together");
   PP_CHECK_ARG(ctx, d->cin % 32 == 0 && d->ld_x % 8 == 0, PP_ERR_SHAPE, "pp_conv2d_nhwc_fwd_bf16x3: cin %d must be a multiple of 32, ld_x of 8", d->cin);
-  PP_CHECK_ARG(ctx, pp_is_packed(x_hi, x_lo) && pp_is_packed(y_hi, y_lo) && pp_is_packed(ep_ah, ep_al), PP_ERR_ALIGN,
+  PP_CHECK_ARG(ctx, pp_is_packed(x_hi, x_lo) && pp_is_packed(y_hi, y_lo), PP_ERR_ALIGN,
                "pp_conv2d_nhwc_fwd_bf16x3: planes must be packed (lo = hi + 16 bytes, 16-byte aligned)");
   PP_CHECK_ARG(ctx, !y_hi || (d->cout % 8 == 0 && d->ld_y % 8 == 0), PP_ERR_SHAPE, "pp_conv2d_nhwc_fwd_bf16x3: output planes need cout, ld_y %% 8 == 0");
   PP_CHECK_ARG(ctx, !ep_ah || (ld_res % 8 == 0 && d->cout % 8 == 0), PP_ERR_SHAPE, "pp_conv2d_nhwc_fwd_bf16x3: residual planes need cout, ld_res %% 8 == 0");
@@ -1746,16 +1742,17 @@ extern "C" int PP_API(pp_conv2d_nhwc_fwd_bf16x3)(pp_ctx* ctx, const pp_conv_desc
   p.w_ty0 = 0; p.w_tx0 = 0; p.w_tstep = 1; p.w_kw = d->kw; p.w_taps = d->kh * d->kw;
   PP_CHECK_ARG(ctx, (y_hi == nullptr) == (y_lo == nullptr) && (!y_hi || (d->ld_y % 4 == 0 && pp_is_aligned16(y_hi) && pp_is_aligned16(y_lo))),
                PP_ERR_ARG, "pp_conv2d_nhwc_fwd_bf16x3: output planes");
-  if (out_flags) {
+  if (opts->out_flags) {
     // only the flagged 32-row output blocks (the listed-block launch of the sparse data gradient, without dilation and fill):
     // plane-stored input, 3x3 stride 1 pad 1 on an unchanged grid, no residual
     bool ok = x_hi != nullptr && ((y != nullptr) != (y_hi != nullptr)) && !chi && !residual && !ep_ah && d->stride == 1 && d->kh == 3 && d->kw == 3 && d->pad_t == 1 &&
               d->pad_l == 1 && igemm3_fast_ok(p, true, d->cout, d->cin / 8);
     for (int i = 0; i < p.n_seg && ok; ++i)
       ok = p.seg[i].OH == p.seg[i].SH && p.seg[i].OW == p.seg[i].SW && p.seg[i].row_begin == p.seg[i].src_row_begin;
-    PP_CHECK_ARG(ctx, ok, PP_ERR_SHAPE, "pp_conv2d_nhwc_fwd_bf16x3: the row-block-out hint needs a 3x3 stride-1 'same' conv on plane-stored input");
-    launch_igemm3_rowlist<2, 2>(ctx->stream, p, x_hi, x_lo, w_hi, w_lo, d->cout, d->cin / 8, y_hi, y_lo, nullptr, const_cast<unsigned char*>(out_flags),
-                                out_list, ctx->ws, ctx->ws_bytes, false);
+    PP_CHECK_ARG(ctx, ok, PP_ERR_SHAPE, "pp_conv2d_nhwc_fwd_bf16x3: out_flags needs a 3x3 stride-1 'same' conv on plane-stored input");
+    launch_igemm3_rowlist<2, 2>(ctx->stream, p, x_hi, x_lo, w_hi, w_lo, d->cout, d->cin / 8, y_hi, y_lo, nullptr,
+                                const_cast<unsigned char*>(opts->out_flags) /* (only read: no dilation without dy_flags) */, opts->out_list, ctx->ws,
+                                ctx->ws_bytes, false);
     PP_CHECK_LAUNCH(ctx, "pp_conv2d_nhwc_fwd_bf16x3");
     return PP_OK;
   }
@@ -1826,20 +1823,17 @@ namespace {
 }  // namespace
 extern "C" int PP_API(pp_conv2d_nhwc_bwd_data_bf16x3)(pp_ctx* ctx, const pp_conv_desc* d, const float* dy, const void* dy_hi, const void* dy_lo,
                                               const void* w_hi, const void* w_lo, const float* addend, int ld_add,
-                                              const float* relu_src, int ld_rs, float* dx, void* dx_hi, void* dx_lo) {
+                                              const float* relu_src, int ld_rs, float* dx, void* dx_hi, void* dx_lo,
+                                              const pp_conv_opts* opts) {
   PP_REQUIRE_CTX(ctx);
-  void *chi = ctx->cap_hi, *clo = ctx->cap_lo;  // one-shot (pp_ctx_set_split_capture)
-  ctx->cap_hi = ctx->cap_lo = nullptr;
-  const unsigned char* skip_flags = ctx->skip_flags;  // one-shot (pp_ctx_set_row_block_skip)
-  const int* skip_list_in = ctx->skip_list;
-  const bool skip_scratch_ok = skip_flags != nullptr && skip_list_in != nullptr;
-  ctx->skip_flags = nullptr;
-  ctx->skip_list = nullptr;
-  const bool lazy_out = ctx->lazy_out != 0, lazy_in = ctx->lazy_in != 0;  // one-shot (pp_ctx_set_row_block_lazy)
-  ctx->lazy_out = ctx->lazy_in = 0;
-  const void *ep_ah = ctx->ep_add_hi, *ep_al = ctx->ep_add_lo, *ep_mh = ctx->ep_mask_hi;  // one-shot (pp_ctx_set_epilogue_planes)
-  ctx->ep_add_hi = ctx->ep_add_lo = ctx->ep_mask_hi = nullptr;
-  int rc = check_desc(ctx, d, "pp_conv2d_nhwc_bwd_data_bf16x3");
+  int rc = pp_conv_opts_take(ctx, opts, PP_OPT_CAPTURE | PP_OPT_ADD | PP_OPT_MASK | PP_OPT_SKIP | PP_OPT_LAZY_OUT | PP_OPT_LAZY_IN,
+                             "pp_conv2d_nhwc_bwd_data_bf16x3");
+  if (rc) return rc;
+  void *const chi = opts->capture_hi, *const clo = opts->capture_lo;
+  unsigned char* const skip_flags = opts->skip_flags;
+  const bool skip_scratch_ok = skip_flags != nullptr && opts->skip_list != nullptr;
+  const void *const ep_ah = opts->add_hi, *const ep_al = opts->add_lo, *const ep_mh = opts->mask_hi;
+  rc = check_desc(ctx, d, "pp_conv2d_nhwc_bwd_data_bf16x3");
   PP_CHECK_ARG(ctx, !(ep_ah && addend) && !(ep_mh && relu_src), PP_ERR_ARG,
                "pp_conv2d_nhwc_bwd_data_bf16x3: addend / relu_src given both as f32 and as planes");
   PP_CHECK_ARG(ctx, (!ep_ah || (ld_add >= d->cin && ld_add % 4 == 0)) && (!ep_mh || (ld_rs >= d->cin && ld_rs % 4 == 0)), PP_ERR_SHAPE,
@@ -1848,7 +1842,7 @@ extern "C" int PP_API(pp_conv2d_nhwc_bwd_data_bf16x3)(pp_ctx* ctx, const pp_conv
   PP_CHECK_ARG(ctx, !chi || (dy && !dy_hi && pp_is_packed(chi, clo)), PP_ERR_ARG, "pp_conv2d_nhwc_bwd_data_bf16x3: split capture needs the f32 operand");
   PP_CHECK_ARG(ctx, (dy || (dy_hi && dy_lo)) && w_hi && w_lo && (dx || (dx_hi && dx_lo)), PP_ERR_ARG, "pp_conv2d_nhwc_bwd_data_bf16x3: null tensor");
   PP_CHECK_ARG(ctx, (dy_hi == nullptr) == (dy_lo == nullptr) && d->ld_y % 8 == 0, PP_ERR_ARG, "pp_conv2d_nhwc_bwd_data_bf16x3: planes / ld_y");
-  PP_CHECK_ARG(ctx, pp_is_packed(dy_hi, dy_lo) && pp_is_packed(dx_hi, dx_lo) && pp_is_packed(ep_ah, ep_al) && pp_is_aligned16(ep_mh), PP_ERR_ALIGN,
+  PP_CHECK_ARG(ctx, pp_is_packed(dy_hi, dy_lo) && pp_is_packed(dx_hi, dx_lo), PP_ERR_ALIGN,
                "pp_conv2d_nhwc_bwd_data_bf16x3: planes must be packed (lo = hi + 16 bytes, 16-byte aligned)");
   PP_CHECK_ARG(ctx, (!dx_hi || (d->cin % 8 == 0 && d->ld_x % 8 == 0)) && (!ep_ah || ld_add % 8 == 0) && (!ep_mh || ld_rs % 8 == 0), PP_ERR_SHAPE,
                "pp_conv2d_nhwc_bwd_data_bf16x3: planes need channel counts and leading dimensions %% 8 == 0");
@@ -1887,11 +1881,11 @@ extern "C" int PP_API(pp_conv2d_nhwc_bwd_data_bf16x3)(pp_ctx* ctx, const pp_conv
   // Contract of the hint's scratch (pp_row_block_list_planes_within relies on it): after this call the second n_blocks bytes
   // of the flags buffer flag every 32-row block of dx that may hold a non-zero -- the dilated list when the listed launch
   // runs, everything otherwise.
-  PP_CHECK_ARG(ctx, !lazy_in || rl_ok, PP_ERR_ARG,
+  PP_CHECK_ARG(ctx, !opts->lazy_in || rl_ok, PP_ERR_ARG,
                "pp_conv2d_nhwc_bwd_data_bf16x3: dy was declared lazy (unwritten outside its flagged blocks) but the listed-block launch "
                "does not apply to this call");
   if (skip_scratch_ok && !rl_ok)
-    PP_HIP(ctx, hipMemsetAsync(const_cast<unsigned char*>(skip_flags) + (p.M + 31) / 32, 1, (size_t)((p.M + 31) / 32), ctx->stream));
+    PP_HIP(ctx, hipMemsetAsync(skip_flags + (p.M + 31) / 32, 1, (size_t)((p.M + 31) / 32), ctx->stream));
   if (d->stride == 2 && s2_classes && (all_f32 || all_planes) && d->in.n_seg == 1) {
     // Stride-2 bwd-data as four stride-1 launches, one per parity class (cy, cx) of the input grid: input cell
     // (2y'+cy, 2x'+cx) only receives the taps ty = ty0 + 2i with ty0 = (cy + pad_t) & 1 (x alike), from output cell
@@ -1939,14 +1933,14 @@ extern "C" int PP_API(pp_conv2d_nhwc_bwd_data_bf16x3)(pp_ctx* ctx, const pp_conv
   }
   if (rl_ok) {
     const int nb = (p.M + 31) / 32;
-    unsigned char* out_flags = const_cast<unsigned char*>(skip_flags) + nb;
-    int* out_list = const_cast<int*>(skip_list_in) + nb + 1;
+    unsigned char* out_flags = skip_flags + nb;
+    int* out_list = opts->skip_list + nb + 1;
     if (rl_mode == 22)
       launch_igemm3_rowlist<2, 2>(ctx->stream, p, dy_hi, dy_lo, w_hi, w_lo, d->cin, cred / 8, dx_hi, dx_lo, skip_flags, out_flags, out_list, ctx->ws,
-                                  ctx->ws_bytes, !lazy_out);
+                                  ctx->ws_bytes, !opts->lazy_out);
     else
       launch_igemm3_rowlist<1, 2>(ctx->stream, p, dy_hi, dy_lo, w_hi, w_lo, d->cin, cred / 8, dx_hi, dx_lo, skip_flags, out_flags, out_list, ctx->ws,
-                                  ctx->ws_bytes, !lazy_out);
+                                  ctx->ws_bytes, !opts->lazy_out);
     PP_CHECK_LAUNCH(ctx, "pp_conv2d_nhwc_bwd_data_bf16x3");
     return PP_OK;
   }
@@ -2588,14 +2582,14 @@ static bool launch_wgrad3(pp_ctx* ctx, Wgrad3Params& p, const float* x, const fl
 
 }  // namespace
 extern "C" int PP_API(pp_conv2d_nhwc_bwd_weight_bf16x3)(pp_ctx* ctx, const pp_conv_desc* d, const float* x, const float* dy, const void* x_hi,
-                                                const void* x_lo, const void* dy_hi, const void* dy_lo, float* dw, float* dbias) {
+                                                const void* x_lo, const void* dy_hi, const void* dy_lo, float* dw, float* dbias,
+                                                const pp_conv_opts* opts) {
   PP_REQUIRE_CTX(ctx);
-  const int* skip_list = ctx->skip_list;  // one-shot (pp_ctx_set_row_block_skip)
-  ctx->skip_list = nullptr;
-  ctx->skip_flags = nullptr;
-  const bool lazy_in = ctx->lazy_in != 0;  // one-shot (pp_ctx_set_row_block_lazy): dy may hold anything outside the listed blocks
-  ctx->lazy_out = ctx->lazy_in = 0;
-  int rc = check_desc(ctx, d, "pp_conv2d_nhwc_bwd_weight_bf16x3");
+  int rc = pp_conv_opts_take(ctx, opts, PP_OPT_SKIP | PP_OPT_LAZY_IN, "pp_conv2d_nhwc_bwd_weight_bf16x3");
+  if (rc) return rc;
+  const int* const skip_list = opts->skip_list;
+  const bool lazy_in = opts->lazy_in != 0;  // dy may hold anything outside the listed blocks
+  rc = check_desc(ctx, d, "pp_conv2d_nhwc_bwd_weight_bf16x3");
   if (rc) return rc;
   const bool planes = x_hi && x_lo && dy_hi && dy_lo;
   PP_CHECK_ARG(ctx, ((x && dy) || planes) && dw, PP_ERR_ARG, "pp_conv2d_nhwc_bwd_weight_bf16x3: null tensor");

@@ -40,7 +40,7 @@ struct IgemmParams {
   // stride-2 bwd-data by parity class: enumerated row (n, y', x') of the class grid seg[0].OH x OW is written to (and
   // reads addend / mask at) row (n*sc_H + 2y' + sc_cy) * sc_W + 2x' + sc_cx of the full tensor
   int sc_on, sc_H, sc_W, sc_cy, sc_cx;
-  // epilogue operands stored as bf16 (hi, lo) planes instead of f32 (pp_ctx_set_epilogue_planes): the addend / residual
+  // epilogue operands stored as bf16 (hi, lo) planes instead of f32 (pp_conv_opts.add_hi / add_lo / mask_hi): the addend / residual
   // (value = hi + lo, geometry [rows][ld_add]) and the ReLU source (only its hi plane is read: hi > 0 <=> value > 0,
   // geometry [rows][ld_mask]).  When set they replace `addend` / `mask_src`.
   const void* add_hi;

@@ -15,19 +15,8 @@ struct pp_ctx {
   char err[512];
   float* ws;        // caller-provided scratch for split-K partial sums (slices)
   size_t ws_bytes;
-  void* cap_hi;     // one-shot: the next bf16x3 fwd / bwd-data launch also writes the split of its gathered operand here
-  void* cap_lo;
-  const void* ep_add_hi;  // one-shot: the next bf16x3 fwd / bwd-data launch reads its addend (residual) and / or its ReLU source
-  const void* ep_add_lo;  // from bf16 (hi, lo) planes (pp_ctx_set_epilogue_planes)
-  const void* ep_mask_hi;
-  const int* skip_list;              // one-shot: row-block skip of the next bf16x3 bwd-weight (list) / bwd-data (flags) call
-  const unsigned char* skip_flags;
-  int lazy_out, lazy_in;             // one-shot (pp_ctx_set_row_block_lazy): the next sparse bwd-data leaves the rows of dx outside the
-                                     // blocks it computes untouched / the next bwd-data or bwd-weight's dy holds anything outside its flagged blocks
-  const unsigned char* out_flags;    // one-shot: the next bf16x3 forward call computes the flagged 32-row output blocks only
-  int* out_list;                     //           (pp_ctx_set_row_block_out; list = its scratch)
-  int planes_fmt;                    // format of every (hi, lo) plane pair this context sees: 0 = bf16 pairs (bf16x3), 1 = P16 (f16c8)
-  const float* grad_scale;           // device {2^G, 2^-G}: the gradient planes this context's weight gradients read carry the factor 2^G
+  int planes_fmt;          // format of every (hi, lo) plane pair this context sees: 0 = bf16 pairs (bf16x3), 1 = P16 (f16c8)
+  const float* grad_scale; // device {2^G, 2^-G}: the gradient planes this context's weight gradients read carry the factor 2^G
 };
 
 static inline int pp_fail(pp_ctx* ctx, int code, const char* fmt, ...) {
@@ -81,4 +70,29 @@ static inline int pp_is_aligned16(const void* p) { return (((uintptr_t)p) & 15u)
 // packed (hi, lo) planes: one buffer of 32-byte groups (8 channels: 16 bytes of hi, 16 bytes of lo); lo = hi + 16 bytes
 static inline int pp_is_packed(const void* hi, const void* lo) {
   return (hi == nullptr && lo == nullptr) || (hi != nullptr && (const char*)lo == (const char*)hi + 16 && pp_is_aligned16(hi));
+}
+
+// pp_conv_opts of a *_bf16x3 convolution call, checked before anything else: NULL becomes the all-zero struct, the field groups
+// outside `takes` (those the entry point `who` does not consume) must be null / zero, the others well formed.
+enum { PP_OPT_CAPTURE = 1, PP_OPT_ADD = 2, PP_OPT_MASK = 4, PP_OPT_SKIP = 8, PP_OPT_LAZY_OUT = 16, PP_OPT_LAZY_IN = 32, PP_OPT_OUT = 64 };
+static inline int pp_conv_opts_take(pp_ctx* ctx, const pp_conv_opts*& o, unsigned takes, const char* who) {
+  static const pp_conv_opts none = {};
+  if (!o) o = &none;
+  const struct { unsigned group; bool set; const char* name; } fields[] = {
+      {PP_OPT_CAPTURE, o->capture_hi != nullptr, "capture_hi"}, {PP_OPT_CAPTURE, o->capture_lo != nullptr, "capture_lo"},
+      {PP_OPT_ADD, o->add_hi != nullptr, "add_hi"},             {PP_OPT_ADD, o->add_lo != nullptr, "add_lo"},
+      {PP_OPT_MASK, o->mask_hi != nullptr, "mask_hi"},          {PP_OPT_SKIP, o->skip_flags != nullptr, "skip_flags"},
+      {PP_OPT_SKIP, o->skip_list != nullptr, "skip_list"},      {PP_OPT_OUT, o->out_flags != nullptr, "out_flags"},
+      {PP_OPT_OUT, o->out_list != nullptr, "out_list"},         {PP_OPT_LAZY_OUT, o->lazy_out != 0, "lazy_out"},
+      {PP_OPT_LAZY_IN, o->lazy_in != 0, "lazy_in"}};
+  for (const auto& f : fields) PP_CHECK_ARG(ctx, !f.set || (takes & f.group), PP_ERR_ARG, "%s: pp_conv_opts.%s is not an option of this call", who, f.name);
+  PP_CHECK_ARG(ctx, (o->capture_hi == nullptr) == (o->capture_lo == nullptr) && pp_is_aligned16(o->capture_hi) && pp_is_aligned16(o->capture_lo),
+               PP_ERR_ARG, "%s: pp_conv_opts.capture_hi and capture_lo go together, 16-byte aligned", who);
+  PP_CHECK_ARG(ctx, (o->add_hi == nullptr) == (o->add_lo == nullptr), PP_ERR_ARG, "%s: pp_conv_opts.add_hi and add_lo go together", who);
+  PP_CHECK_ARG(ctx, pp_is_packed(o->add_hi, o->add_lo) && pp_is_aligned16(o->mask_hi), PP_ERR_ALIGN,
+               "%s: pp_conv_opts epilogue planes must be packed (lo = hi + 16 bytes) and 16-byte aligned", who);
+  PP_CHECK_ARG(ctx, (o->out_flags == nullptr) == (o->out_list == nullptr), PP_ERR_ARG, "%s: pp_conv_opts.out_flags and out_list go together", who);
+  PP_CHECK_ARG(ctx, !(o->lazy_out || o->lazy_in) || (o->skip_flags && o->skip_list), PP_ERR_ARG,
+               "%s: pp_conv_opts.lazy_out / lazy_in go with skip_flags and skip_list", who);
+  return PP_OK;
 }

@@ -29,13 +29,14 @@ def tf_same_pad(n_in, k, s):
 
 class Op(object):
     """One C-ABI launch of the plan: `fn()` enqueues it on the ctx stream."""
-    __slots__ = ("fn", "kind", "name", "flops", "wrange", "lane", "reads", "waits", "done_ev")
+    __slots__ = ("fn", "kind", "name", "flops", "wrange", "lane", "reads", "waits", "done_ev", "out_blocks")
 
     def __init__(self, fn, kind, name="", flops=0.0, wrange=None, lane=0):
         self.fn, self.kind, self.name, self.flops, self.wrange, self.lane = fn, kind, name, flops, wrange, lane
         self.reads = ()      # forward plan: the activations this launch reads ...
         self.waits = ()      # ... -> events of their producers on OTHER lanes, awaited before the launch
         self.done_ev = None  # recorded after the launch when a consumer on another lane needs it
+        self.out_blocks = None  # conv_fwd of the sparse forward (_plan_sparse_forward): (flags, list) of the output blocks to compute
 
     def __call__(self):
         self.fn()
@@ -91,7 +92,7 @@ class Grad(object):
     def __init__(self, t, pl=None, fmt=0):
         self.t, self.pl, self.fmt = t, pl, int(fmt)  # fmt: plane format of `pl` (a P16 gradient also carries the factor 2^G)
         self.within = None  # uint8 flags of the only 32-row blocks that can hold a non-zero (a sparse data gradient without addend)
-        self.lazy = False   # the rows outside `within` were never written (pp_ctx_set_row_block_lazy): every reader goes by flags
+        self.lazy = False   # the rows outside `within` were never written (conv_bwd_data3's lazy_out): every reader goes by flags
 
     def rows(self, r0, r1):
         return Grad(None if self.t is None else self.t[r0:r1], None if self.pl is None else (self.pl[0][r0:r1], self.pl[1][r0:r1]), self.fmt)
@@ -328,6 +329,7 @@ class Engine(object):
             if self.conv_mode == "bf16x3" else ()
         # opt-in: the FORWARD of that head on the same blocks in training steps (_plan_sparse_forward)
         self.sparse_fwd = (self.train and self.po and "reg" in self.sparse_bwd and _os.environ.get("PP_SPARSE_FWD", "0") == "1")
+        self._sparse_fwd_now = False  # set by _train_forward around the forward of a training step
         self.capture_min_cin = int(_os.environ.get("PP_CAPTURE_MIN_CIN", "64"))
         self.capture_skip = tuple(t for t in _os.environ.get("PP_CAPTURE_SKIP", "").split(",") if t)
         self.planes = OrderedDict()  # spec name -> dict(desc, fwd_hi, fwd_lo, dg_hi, dg_lo)
@@ -560,8 +562,10 @@ class Engine(object):
             r_t = r_pl = None
             if residual is not None:
                 r_t, r_pl = (residual.t, None) if residual.t is not None else (None, residual.pl)
-            self._push(Op(lambda: ops.conv_fwd3(ctx, desc, x_t, fh, fl, b, r_t, relu, y.t, x_pl, y.pl, cap, r_pl), "conv_fwd", spec_name,
-                          flops, None, lane), (x, residual), y)
+            op = Op(None, "conv_fwd", spec_name, flops, None, lane)
+            op.fn = lambda: ops.conv_fwd3(ctx, desc, x_t, fh, fl, b, r_t, relu, y.t, x_pl, y.pl, cap, r_pl,
+                                          op.out_blocks if self._sparse_fwd_now else None)
+            self._push(op, (x, residual), y)
         else:
             assert x.t is not None and (residual is None or residual.t is not None), spec_name
             rt = residual.t if residual is not None else None
@@ -679,26 +683,18 @@ class Engine(object):
         at the anchors with state 1 only (losses.py:332-333), so the step needs reg_out on the 32-row blocks that hold a positive
         anchor, reg_conv3 on those within one pixel of them, ... reg_conv0 within four -- the same block sets the sparse
         backward finds in the gradient.  Per step: one scan of the targets + four dilations (train_step), then every conv of
-        the head runs the listed-block launch (pp_ctx_set_row_block_out).  The other rows of the head's tensors keep stale values
+        the head runs the listed-block launch (conv_fwd3's out_blocks).  The other rows of the head's tensors keep stale values
         that nothing reads: the loss masks them, the backward's row-block skip never goes there.  forward() / predict paths
-        are not affected (the hint is set inside train_step only)."""
+        are not affected (the ops pass their blocks only while train_step has _sparse_fwd_now set)."""
         names = ["reg_conv0", "reg_conv1", "reg_conv2", "reg_conv3", "reg_out"]
         nb = (self.pyr.rows + 31) // 32
         dev = dict(device="cuda")
         self._sf_flags = [torch.zeros((nb,), dtype=torch.uint8, **dev) for _ in names]
         self._sf_lists = [torch.zeros((nb + 1,), dtype=torch.int32, **dev) for _ in names]
         self._sf_desc = next(g["desc"] for g in self.graph_ops if g.get("kind") == "conv" and g["spec"].name == "reg_conv1")
-        self._sparse_fwd_now = False
         by_name = {o.name: o for o in self.fwd_ops}
         for k, name in enumerate(names):
-            op = by_name[name]
-            octx = self.ctxs[op.lane].twin(self._fmt(op.name))
-
-            def fn(inner=op.fn, k=k, octx=octx):
-                if self._sparse_fwd_now:
-                    ops.set_row_block_out(octx, self._sf_flags[k], self._sf_lists[k])
-                inner()
-            op.fn = fn
+            by_name[name].out_blocks = (self._sf_flags[k], self._sf_lists[k])
 
     def _sparse_forward_lists(self):
         """the block sets of this step's targets (lane 0; ~25 us)"""

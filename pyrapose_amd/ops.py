@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import ConvDesc, ParamDesc, RowSpace, TView, check, lib
+from ._lib import ConvDesc, ConvOpts, ParamDesc, RowSpace, TView, check, lib
 
 
 def _ptr(t):
@@ -209,11 +209,6 @@ def set_grad_scale(ctx, scale2):
     check(lib.pp_ctx_set_grad_scale(ctx.handle, _ptr(scale2)), ctx.handle, "pp_ctx_set_grad_scale")
 
 
-def _set_capture(ctx, planes):
-    if planes is not None:
-        check(lib.pp_ctx_set_split_capture(ctx.handle, _ptr(planes[0]), _ptr(planes[1])), ctx.handle, "pp_ctx_set_split_capture")
-
-
 def row_block_list(ctx, x, cols, flags=None, blocks=None):
     """pp_row_block_list: x float32 [rows, ld] -> (flags uint8 [2 nb], list int32 [2 (1 + nb)]) with nb = ceil(rows / 32);
     the first halves hold the result, the second halves are scratch of the bwd-data launch that takes the hint."""
@@ -240,12 +235,6 @@ def row_block_list_planes(ctx, planes, cols, flags, blocks, within=None):
         check(lib.pp_row_block_list_planes(ctx.handle, _ptr(hi), _ptr(lo), rows, planes_ld(planes), int(cols), _ptr(flags), _ptr(blocks)),
               ctx.handle, "pp_row_block_list_planes")
     return flags, blocks
-
-
-def _set_epilogue_planes(ctx, add_planes, mask_hi):
-    if add_planes is not None or mask_hi is not None:
-        ah, al = add_planes if add_planes is not None else (None, None)
-        check(lib.pp_ctx_set_epilogue_planes(ctx.handle, _ptr(ah), _ptr(al), _ptr(mask_hi)), ctx.handle, "pp_ctx_set_epilogue_planes")
 
 
 def tview(t=None, planes=None):
@@ -313,59 +302,59 @@ def row_block_dilate(ctx, d, in_flags, out_flags):
     return out_flags
 
 
-def set_row_block_out(ctx, flags, blocks):
-    """pp_ctx_set_row_block_out (one-shot): the next conv_fwd3 on ctx computes the flagged 32-row output blocks only"""
-    check(lib.pp_ctx_set_row_block_out(ctx.handle, _ptr(flags), _ptr(blocks)), ctx.handle, "pp_ctx_set_row_block_out")
+def _conv_opts(capture=None, add=None, mask_hi=None, skip=None, out=None, lazy_out=False, lazy_in=False):
+    """the pp_conv_opts of one launch (include/pyrapose_hip.h); NULL when no option is given.  The library checks the combination."""
+    if capture is None and add is None and mask_hi is None and skip is None and out is None and not (lazy_out or lazy_in):
+        return None
+    o = ConvOpts()
+    o.capture_hi, o.capture_lo = map(_ptr, capture or (None, None))
+    o.add_hi, o.add_lo = map(_ptr, add or (None, None))
+    o.mask_hi = _ptr(mask_hi)
+    o.skip_flags, o.skip_list = map(_ptr, skip or (None, None))
+    o.out_flags, o.out_list = map(_ptr, out or (None, None))
+    o.lazy_out, o.lazy_in = int(bool(lazy_out)), int(bool(lazy_in))
+    return C.byref(o)
 
 
-def _set_skip(ctx, skip, lazy_out=False, lazy_in=False):
-    if skip is not None:
-        check(lib.pp_ctx_set_row_block_skip(ctx.handle, _ptr(skip[0]), _ptr(skip[1])), ctx.handle, "pp_ctx_set_row_block_skip")
-    if lazy_out or lazy_in:
-        if skip is None:
-            raise ValueError("lazy sparse gradients go with a row-block skip hint (dy_skip)")
-        check(lib.pp_ctx_set_row_block_lazy(ctx.handle, int(bool(lazy_out)), int(bool(lazy_in))), ctx.handle, "pp_ctx_set_row_block_lazy")
-
-
-def conv_fwd3(ctx, d, x, w_hi, w_lo, bias, residual, relu, y, x_planes=None, y_planes=None, x_capture=None, res_planes=None):
-    """x_capture = (hi, lo): the launch also writes the bf16 split of x (pp_ctx_set_split_capture).
-    res_planes = (hi, lo): the residual as planes (pp_ctx_set_epilogue_planes; `residual` must then be None)."""
-    _set_capture(ctx, x_capture)
-    _set_epilogue_planes(ctx, res_planes, None)
+def conv_fwd3(ctx, d, x, w_hi, w_lo, bias, residual, relu, y, x_planes=None, y_planes=None, x_capture=None, res_planes=None,
+              out_blocks=None):
+    """x_capture = (hi, lo): the launch also writes the bf16 split of x (pp_conv_opts.capture_hi / capture_lo).
+    res_planes = (hi, lo): the residual as planes (pp_conv_opts.add_hi / add_lo; `residual` must then be None).
+    out_blocks = (flags, list): only the flagged 32-row output blocks are computed (pp_conv_opts.out_flags; list = scratch)."""
     ld_res = residual.stride(0) if residual is not None else (planes_ld(res_planes) if res_planes is not None else 0)
     xh, xl = x_planes if x_planes is not None else (None, None)
     yh, yl = y_planes if y_planes is not None else (None, None)
     check(lib.pp_conv2d_nhwc_fwd_bf16x3(ctx.handle, C.byref(d), _ptr(x), _ptr(xh), _ptr(xl), _ptr(w_hi), _ptr(w_lo), _ptr(bias),
-                                        _ptr(residual), ld_res, int(bool(relu)), _ptr(y), _ptr(yh), _ptr(yl)), ctx.handle,
+                                        _ptr(residual), ld_res, int(bool(relu)), _ptr(y), _ptr(yh), _ptr(yl),
+                                        _conv_opts(capture=x_capture, add=res_planes, out=out_blocks)), ctx.handle,
           "pp_conv2d_nhwc_fwd_bf16x3")
 
 
 def conv_bwd_data3(ctx, d, dy, w_hi, w_lo, addend, relu_src, dx, dy_planes=None, dx_planes=None, dy_capture=None, dy_skip=None,
                    addend_planes=None, relu_src_hi=None, lazy_out=False, lazy_in=False):
-    """dy_capture = (hi, lo): the launch also writes the bf16 split of dy (pp_ctx_set_split_capture).
+    """dy_capture = (hi, lo): the launch also writes the bf16 split of dy (pp_conv_opts.capture_hi / capture_lo).
     dy_skip = (flags, list) from row_block_list(dy): tiles that only see zero blocks of dy skip their reduction.
-    addend_planes = (hi, lo) / relu_src_hi = hi plane: those epilogue operands as planes (pp_ctx_set_epilogue_planes).
-    lazy_out / lazy_in: pp_ctx_set_row_block_lazy (dx is left unwritten outside the computed blocks / dy is such a tensor)."""
-    _set_capture(ctx, dy_capture)
-    _set_skip(ctx, dy_skip, lazy_out, lazy_in)
-    _set_epilogue_planes(ctx, addend_planes, relu_src_hi)
+    addend_planes = (hi, lo) / relu_src_hi = hi plane: those epilogue operands as planes (pp_conv_opts.add_hi / add_lo / mask_hi).
+    lazy_out / lazy_in: pp_conv_opts.lazy_out / lazy_in (dx is left unwritten outside the computed blocks / dy is such a tensor)."""
     ld_add = addend.stride(0) if addend is not None else (planes_ld(addend_planes) if addend_planes is not None else 0)
     ld_rs = relu_src.stride(0) if relu_src is not None else (relu_src_hi.stride(0) // 2 if relu_src_hi is not None else 0)
     dh, dl = dy_planes if dy_planes is not None else (None, None)
     xh, xl = dx_planes if dx_planes is not None else (None, None)
     check(lib.pp_conv2d_nhwc_bwd_data_bf16x3(ctx.handle, C.byref(d), _ptr(dy), _ptr(dh), _ptr(dl), _ptr(w_hi), _ptr(w_lo), _ptr(addend),
-                                             ld_add, _ptr(relu_src), ld_rs, _ptr(dx), _ptr(xh), _ptr(xl)), ctx.handle,
+                                             ld_add, _ptr(relu_src), ld_rs, _ptr(dx), _ptr(xh), _ptr(xl),
+                                             _conv_opts(capture=dy_capture, add=addend_planes, mask_hi=relu_src_hi, skip=dy_skip,
+                                                        lazy_out=lazy_out, lazy_in=lazy_in)), ctx.handle,
           "pp_conv2d_nhwc_bwd_data_bf16x3")
 
 
 def conv_bwd_weight3(ctx, d, x, dy, dw, dbias, x_planes=None, dy_planes=None, dy_skip=None, lazy_in=False):
     """dy_skip = (flags, list) from row_block_list(dy): the reduction walks the listed 32-row blocks only.
-    lazy_in: dy is unwritten outside those blocks (pp_ctx_set_row_block_lazy): fails unless the listed-block reduction runs."""
-    _set_skip(ctx, dy_skip, False, lazy_in)
+    lazy_in: dy is unwritten outside those blocks (pp_conv_opts.lazy_in): fails unless the listed-block reduction runs."""
     xh, xl = x_planes if x_planes is not None else (None, None)
     dh, dl = dy_planes if dy_planes is not None else (None, None)
     check(lib.pp_conv2d_nhwc_bwd_weight_bf16x3(ctx.handle, C.byref(d), _ptr(x), _ptr(dy), _ptr(xh), _ptr(xl), _ptr(dh), _ptr(dl),
-                                               _ptr(dw), _ptr(dbias)), ctx.handle, "pp_conv2d_nhwc_bwd_weight_bf16x3")
+                                               _ptr(dw), _ptr(dbias), _conv_opts(skip=dy_skip, lazy_in=lazy_in)), ctx.handle,
+          "pp_conv2d_nhwc_bwd_weight_bf16x3")
 
 
 def maxpool3x3s2(ctx, n_img, h, w, c, x, oh, ow, y):

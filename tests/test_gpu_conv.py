@@ -304,7 +304,7 @@ def test_conv_bf16x3_fwd_bwd_data(pctx, case):
     assert torch.equal(torch.nan_to_num(y3), torch.nan_to_num(y))
     assert torch.equal(ch, xh) and torch.equal(cl, xl)
     y3.fill_(float("nan"))
-    ops.conv_fwd3(ctx, d, x, fh, fl, bd.cuda(), _cat_rows(res, ld_y), True, y3)  # the capture is one-shot
+    ops.conv_fwd3(ctx, d, x, fh, fl, bd.cuda(), _cat_rows(res, ld_y), True, y3)  # the capture belongs to the call above alone
     assert torch.equal(torch.nan_to_num(y3), torch.nan_to_num(y))
     # ... and the epilogue's pre-split copy of the output is exactly what the split kernel makes of it
     wh, wl = ops.new_planes(y2.shape[0], y2.shape[1])
@@ -529,7 +529,7 @@ def test_row_block_skip_matches_dense(pctx, frac):
     assert float((dw0 - dw1).abs().max()) <= 2e-6 * scale and float((db0 - db1).abs().max()) <= 2e-6 * max(float(db0.abs().max()), 1e-30)
     if frac == 0.0:
         assert not dw1.any() and not db1.any() and torch.equal(dx1, torch.where(msk > 0, add, torch.zeros_like(add)))
-    # the hint is one-shot: the next call is dense again
+    # the skip travels with its call: the next call is dense again
     dw2 = torch.zeros_like(w)
     ops.conv_bwd_weight3(ctx, d, x, dy, dw2, None)
     assert float((dw0 - dw2).abs().max()) <= 2e-6 * scale

@@ -421,7 +421,7 @@ def test_weight_gradient_slices_are_deterministic_and_match_atomics(ctx, case, m
 
 
 def test_lazy_sparse_gradients(ctx):
-    """pp_ctx_set_row_block_lazy: a listed-block data gradient that leaves the rows outside its blocks UNWRITTEN, and consumers that
+    """pp_conv_opts.lazy_out / lazy_in: a listed-block data gradient that leaves the rows outside its blocks UNWRITTEN, and consumers that
     never look at them -- the restricted scan, the listed-block data gradient (its gather skips rows outside the flagged blocks of
     dy) and the listed-block weight gradient give what they give on the zero-filled tensor; a launch that would read the unwritten
     rows refuses the call."""
@@ -716,3 +716,114 @@ def test_tap_row_reuse_weight_gradient_matches_wgrad3f(ctx, monkeypatch, case):
     err = float((got - ref).abs().max() / ref.abs().max())
     assert err <= (1e-4 if FMT[0] == 1 else 2e-5), err
     assert float((out["1"][1][:cout].double() - gv.sum(0)).abs().max()) <= 1e-4 * float(gv.sum(0).abs().max())
+
+
+def _opts_case(ctx, cin=64, cout=64, seed=41):
+    """a small 3x3 stride-1 'same' layer with every operand of the three directions, f32 and planes"""
+    from pyrapose_amd import ops
+    rng = np.random.default_rng(seed)
+    B, shapes, k = 2, [(12, 16), (6, 7)], 3
+    rows = sum(B * h * w for h, w in shapes)
+    d = ops.make_conv_desc(B, shapes, shapes, cin, cout, k, 1, 1, 1, cin, cout, cout)
+    w = torch.as_tensor(rng.standard_normal((k * k * cin, cout)) * 0.05, dtype=torch.float32).cuda()
+    i16 = dict(dtype=torch.int16, device="cuda")
+    fh, fl = torch.zeros((k * k, cout, cin), **i16), torch.zeros((k * k, cout, cin), **i16)
+    dh, dl = torch.zeros((k * k, cin, cout), **i16), torch.zeros((k * k, cin, cout), **i16)
+    ops.conv_split_weights3(ctx, d, w, fh, fl, dh, dl)
+    x = torch.as_tensor(rng.standard_normal((rows, cin)), dtype=torch.float32).cuda()
+    dy = torch.as_tensor(rng.standard_normal((rows, cout)), dtype=torch.float32).cuda()
+    return d, rows, w, (fh, fl), (dh, dl), x, dy
+
+
+def test_refused_conv_call_leaves_nothing_behind(ctx):
+    """The options of a conv launch travel with the call (pp_conv_opts): a call that is refused -- here a data gradient with a split
+    capture and lazy_in but no row-block skip -- launches nothing and leaves nothing for a later call to pick up.  The capture
+    planes keep their sentinel through the refused call AND through the next forward on the same context, whose output is that of
+    the same call on a context that never saw the refused one."""
+    from pyrapose_amd import ops
+    d, rows, w, (fh, fl), (dh, dl), x, dy = _opts_case(ctx)
+    cap = ops.new_planes(rows, d.cout, fill=0x1234)
+    sentinel = [t.clone() for t in raw(cap)]
+    dx = torch.full((rows, d.cin), 7.0, device="cuda")
+    with pytest.raises(ValueError):
+        ops.conv_bwd_data3(ctx, d, dy, dh, dl, None, None, dx, dy_capture=cap, lazy_in=True)
+    torch.cuda.synchronize()
+    assert bool((dx == 7.0).all())
+    y = torch.full((rows, d.cout), float("nan"), device="cuda")
+    ops.conv_fwd3(ctx, d, x, fh, fl, None, None, False, y)
+    fresh = ops.Context(ctx.device, ctx.stream)
+    try:
+        ops.set_planes_format(fresh, FMT[0])
+        if getattr(ctx, "workspace", None) is not None:  # (the same split-K decisions)
+            fresh.set_workspace(ctx.workspace.numel() * 4)
+        y2 = torch.full_like(y, float("nan"))
+        ops.conv_fwd3(fresh, d, x, fh, fl, None, None, False, y2)
+        torch.cuda.synchronize()
+    finally:
+        fresh.close()
+    assert all(torch.equal(a, b) for a, b in zip(raw(cap), sentinel))
+    assert bool(y.isfinite().all()) and torch.equal(y, y2)
+
+
+def test_misplaced_conv_options_are_rejected(ctx):
+    """a pp_conv_opts field that the entry point does not consume is PP_ERR_ARG (ValueError) naming the field, before any launch:
+    the forward takes no row-block skip, the data gradient no out_flags, the weight gradient no split capture.  Every call is
+    otherwise valid (it succeeds without the foreign field); its outputs keep their sentinel."""
+    import ctypes as C
+    from pyrapose_amd import ops
+    from pyrapose_amd._lib import ConvOpts, check, lib
+    d, rows, w, (fh, fl), (dh, dl), x, dy = _opts_case(ctx)
+    nb = (rows + 31) // 32
+    flags = torch.ones((2 * nb,), dtype=torch.uint8, device="cuda")
+    blocks = torch.zeros((2 * (nb + 1),), dtype=torch.int32, device="cuda")
+    cap = ops.new_planes(rows, d.cout, fill=0x1234)
+    sentinel = [t.clone() for t in raw(cap)]
+    y = torch.full((rows, d.cout), 7.0, device="cuda")
+    dx = torch.full((rows, d.cin), 7.0, device="cuda")
+    dw = torch.full_like(w, 7.0)
+    P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    fwd = lambda o: lib.pp_conv2d_nhwc_fwd_bf16x3(ctx.handle, C.byref(d), P(x), None, None, P(fh), P(fl), None, None, 0, 0, P(y), None, None, o)  # noqa: E731
+    bwd = lambda o: lib.pp_conv2d_nhwc_bwd_data_bf16x3(ctx.handle, C.byref(d), P(dy), None, None, P(dh), P(dl), None, 0, None, 0, P(dx), None, None, o)  # noqa: E731
+    wgr = lambda o: lib.pp_conv2d_nhwc_bwd_weight_bf16x3(ctx.handle, C.byref(d), P(x), P(dy), None, None, None, None, P(dw), None, o)  # noqa: E731
+    for call, fields in ((fwd, dict(skip_flags=flags, skip_list=blocks)), (bwd, dict(out_flags=flags, out_list=blocks)),
+                         (wgr, dict(capture_hi=cap[0], capture_lo=cap[1]))):
+        o = ConvOpts()
+        for name, t in fields.items():
+            setattr(o, name, t.data_ptr())
+        rc = call(C.byref(o))
+        assert rc == -1  # PP_ERR_ARG
+        with pytest.raises(ValueError) as ei:
+            check(rc, ctx.handle, "conv")
+        assert "pp_conv_opts.%s" % next(iter(fields)) in str(ei.value)
+    torch.cuda.synchronize()
+    assert bool((y == 7.0).all()) and bool((dx == 7.0).all()) and bool((dw == 7.0).all())
+    assert all(torch.equal(a, b) for a, b in zip(raw(cap), sentinel))
+    assert fwd(None) == 0 and bwd(None) == 0 and wgr(None) == 0
+    torch.cuda.synchronize()
+    assert bool(y.isfinite().all()) and not bool((y == 7.0).all())
+
+
+def test_forward_over_listed_output_blocks(ctx):
+    """conv_fwd3(out_blocks=(flags, list)): the flagged 32-row output blocks are those of the dense forward, bit for bit; every other
+    row keeps what it held.  3x3 stride-1 'same' on plane-stored input, planes out.  (cin = 32, one channel chunk per tap: the
+    listed-block kernel -- tap outermost -- and the dense launch's tap-row-reuse kernel -- kernel row innermost -- then add the
+    same products in the same order; with more chunks the two differ by f32 summation order, tests/test_gpu_pipeline.py.)"""
+    from pyrapose_amd import ops
+    d, rows, w, (fh, fl), _, x, _ = _opts_case(ctx, cin=32, cout=64, seed=43)
+    nb = (rows + 31) // 32
+    xp = split(ctx, x)
+    bias = torch.as_tensor(np.random.default_rng(5).standard_normal(d.cout), dtype=torch.float32).cuda()
+    dense = nan_planes(torch.empty((rows, d.cout)))
+    ops.conv_fwd3(ctx, d, None, fh, fl, bias, None, True, None, x_planes=xp, y_planes=dense)
+    flags = torch.zeros((nb,), dtype=torch.uint8, device="cuda")
+    flags[[0, 3, 4, nb - 1]] = 1  # (the last block is a partial one: rows % 32 != 0)
+    assert rows % 32 != 0 and 0 < int(flags.sum()) < nb
+    blocks = torch.zeros((nb + 1,), dtype=torch.int32, device="cuda")
+    got = ops.new_planes(rows, d.cout, fill=0x1234)
+    ops.conv_fwd3(ctx, d, None, fh, fl, bias, None, True, None, x_planes=xp, y_planes=got, out_blocks=(flags, blocks))
+    torch.cuda.synchronize()
+    live = flags.bool().repeat_interleave(32)[:rows]
+    for a, b in zip(raw(got), raw(dense)):
+        print("listed-block forward: rows flagged %d, differing elements %d" % (int(live.sum()), int((a[live] != b[live]).sum())))
+        assert torch.equal(a[live], b[live])
+        assert bool((a[~live] == 0x1234).all())

@@ -1,4 +1,4 @@
-"""Timing probe of the sparse data gradient (pp_ctx_set_row_block_skip) on the regression-head shape with two 16x16-cell
+"""Timing probe of the sparse data gradient (pp_conv_opts.skip_flags / skip_list) on the regression-head shape with two 16x16-cell
 patches of non-zero gradient per image: dense vs listed-block launch, and the live block counts.  PP_SPARSE_DGRAD=0/12/22."""
 import os, sys, torch, time
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
