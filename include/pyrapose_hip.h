@@ -317,6 +317,41 @@ int pp_resize_scale(int rows, int cols, int min_side, int max_side, double* scal
 /* cv2.resize(img, None, fx = fy = scale) bilinear: dst [n_img][DH][DW][channels] with DH = round(SH * scale), DW = round(SW * scale) */
 int pp_resize_linear_u8(pp_ctx* ctx, int n_img, int SH, int SW, int channels, double scale, int DH, int DW, const unsigned char* src,
                         unsigned char* dst);
+/* ---- photometric augmentation of the input pipeline -----------------------------------------------------------------
+ * The apply half of the imgaug chain of utils/image.py:154-191 (blur, hue / saturation / grayscale, brightness, contrast) on
+ * uint8 BGR batches; the host samples one ordered op list per image and builds every table (pyrapose_amd/utils/photometric.py).
+ * After every op the image is rounded to uint8 and the next op reads those bytes.  The op definitions, float32 expression
+ * by expression, are in the header comment of pyrapose_amd/csrc/photo.hip; tests/photo_np.py restates them and the device
+ * result is byte-identical to it.  Parity with imgaug / OpenCV is unpinned (neither is installed).
+ * Offsets are byte offsets into the pool, multiples of 4.
+ *   PP_PHOTO_LUT        off0: 3 x 256 bytes, one table per channel
+ *   PP_PHOTO_GRAY       f0: alpha in [0,1] towards the luma
+ *   PP_PHOTO_HUESAT     f0: dh (H in [0,180), wraps), f1: ds (S in [0,255], saturates); both integers
+ *   PP_PHOTO_BLEND      off0: 2 x 3 x 256 bytes (first, second); off1: {int32 mh, int32 mw, float32 mask[mh][mw]}, mh, mw <= 32
+ *   PP_PHOTO_CONV       k odd <= 7; off0: k x k float32 taps (correlation, reflect-101 border)
+ *   PP_PHOTO_MEDIAN     k in {3,5,7} (replicate border)
+ *   PP_PHOTO_BILATERAL  k odd <= 7; off0: k x k float32 space weights (0 outside the circle); off1: 766 float32 colour weights
+ *                       indexed by |db|+|dg|+|dr| (reflect-101 border) */
+enum { PP_PHOTO_NONE = 0, PP_PHOTO_LUT = 1, PP_PHOTO_GRAY = 2, PP_PHOTO_HUESAT = 3, PP_PHOTO_BLEND = 4, PP_PHOTO_CONV = 5, PP_PHOTO_MEDIAN = 6,
+       PP_PHOTO_BILATERAL = 7 };
+typedef struct pp_photo_op {
+  int kind; /* PP_PHOTO_LUT .. PP_PHOTO_BILATERAL */
+  int k;
+  int off0, off1;
+  float f0, f1;
+} pp_photo_op;
+/* Image n runs ops_host[op_offsets_host[n] .. op_offsets_host[n+1]) in order (at most 32; none: a copy); n_img <= 64, channels
+ * must be 3.  op_offsets_host, ops_host and pool_host are HOST arrays, read during the call only (the op records travel as
+ * kernel arguments); pool_dev is the caller's device copy of the same pool_bytes bytes, 16-byte aligned, uploaded in stream
+ * order before the call (the upload and the lifetime of its source are the caller's, in whatever way its allocator tracks
+ * them).  A malformed program (unknown op, even k, k > 7, an offset outside the pool or not a multiple of 4, a blend mask
+ * larger than 32 x 32) is PP_ERR_ARG before anything is launched; the kernels take every size from the checked host copy.
+ * src / dst: [n_img][H][W][3] uint8, distinct device buffers; workspace: pp_photo_workspace_bytes device bytes (the ping-pong
+ * batch), 16-byte aligned.  No host synchronisation. */
+size_t pp_photo_workspace_bytes(int n_img, int H, int W);
+int pp_photo_augment_u8(pp_ctx* ctx, int n_img, int H, int W, int channels, const int* op_offsets_host, const pp_photo_op* ops_host,
+                        const unsigned char* pool_host, size_t pool_bytes, const unsigned char* pool_dev, const unsigned char* src,
+                        unsigned char* dst, void* workspace, size_t workspace_bytes);
 /* The same two producers writing into a zero frame [n_img][Hp][Wp][4] with the image at (pad, pad): the input layout of
  * pp_stem7x7s2_fwd_bf16x3 (pad = 3). */
 int pp_pack_rgb_to_4_padded(pp_ctx* ctx, int n_img, int H, int W, int Hp, int Wp, int pad, const float* x3, float* x4p);

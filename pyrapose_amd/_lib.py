@@ -124,6 +124,8 @@ _SIGS = {
     "pp_upsample_nearest_add_bwd_v": (_i, [_p, _i, _i, _i, _i, _i, _i, C.POINTER(TView), C.POINTER(TView), C.POINTER(TView)]),
     "pp_merge_planes_bf16x3": (_i, [_p, _sz, _p, _p, _p]),
     "pp_warp_affine_u8": (_i, [_p, _i, _i, _i, _i, C.POINTER(_d), _i, _i, _i, _p, _p]),
+    "pp_photo_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pp_photo_augment_u8": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _sz, _p, _p, _p, _p, _sz]),
     "pp_resize_scale": (_i, [_i, _i, _i, _i, C.POINTER(_d)]),
     "pp_resize_linear_u8": (_i, [_p, _i, _i, _i, _i, _d, _i, _i, _p, _p]),
     "pp_conv_split_weights_bf16x3_batch": (_i, [_p, _i, _p, _i]),

@@ -1074,7 +1074,8 @@ class Engine(object):
 
     def _load_input(self, inp, lane):
         """the batch into the stem's input on `lane`'s stream: ("f32", x or None) = NHWC float32 into x_in (pack_rgb follows),
-        ("u8", images, sizes) = the uint8 kernel (mean subtraction + padding + packing in one launch, no pack_rgb)"""
+        ("u8", images, sizes[, transforms, border, cval[, photometric]]) = the uint8 kernel (mean subtraction + padding + packing
+        in one launch, no pack_rgb), behind the photometric chain and the warp when given"""
         if inp[0] == "f32":
             if inp[1] is not None:
                 with torch.cuda.stream(self.streams[lane]):
@@ -1083,6 +1084,8 @@ class Engine(object):
         x4 = self.acts["input4"]
         xd = inp[1]
         with torch.cuda.stream(self.streams[lane]):  # (temporaries belong to the stream whose kernels use them)
+            if len(inp) > 6 and inp[6] is not None:  # the imgaug chain comes first (utils/image.py:154-191); the id mask is not touched
+                xd = ops.photo_augment_u8(self.ctxs[lane], xd, inp[6])
             if len(inp) > 3 and inp[3] is not None:  # augmentation: warp on the device (utils/image.py:207-214)
                 xd = ops.warp_affine_u8(self.ctxs[lane], xd, inp[3], "linear", inp[4], inp[5])
             if self.stem3:
@@ -1147,17 +1150,20 @@ class Engine(object):
         until then; Engine.RESIDENT = x_in as it is) -- its frozen prefix runs beside this batch's trunk."""
         self._forward(("f32", x), None if next_x is None else ("f32", next_x))
 
-    def forward_u8(self, images_u8, sizes_hw=None, transforms=None, border="replicate", cval=0, next_batch=None):
+    def forward_u8(self, images_u8, sizes_hw=None, transforms=None, border="replicate", cval=0, next_batch=None, photometric=None):
         """Forward from a uint8 BGR batch [B,H,W,3] on the device: mean subtraction, zero padding and channel packing run
         in one kernel in place of the host-side preprocess_image / compute_inputs (4x less host->device traffic).
         transforms: one augmentation matrix per image (the batch is warped on the device first).
-        next_batch: dict(images_u8=, sizes_hw=, transforms=, border=, cval=) of the NEXT call (same tensor object) -> its prefix is prefetched."""
+        photometric: a utils.photometric.PhotoPrograms (one op list per image): applied on the device before the warp.
+        next_batch: dict(images_u8=, sizes_hw=, transforms=, border=, cval=, photometric=) of the NEXT call (same tensor object) -> its
+        prefix is prefetched."""
         full = [(self.H, self.W)] * self.B
         nxt = None
         if next_batch is not None:
             nb = next_batch
-            nxt = ("u8", nb["images_u8"], nb.get("sizes_hw") or full, nb.get("transforms"), nb.get("border", "replicate"), nb.get("cval", 0))
-        self._forward(("u8", images_u8, sizes_hw or full, transforms, border, cval), nxt)
+            nxt = ("u8", nb["images_u8"], nb.get("sizes_hw") or full, nb.get("transforms"), nb.get("border", "replicate"), nb.get("cval", 0),
+                   nb.get("photometric"))
+        self._forward(("u8", images_u8, sizes_hw or full, transforms, border, cval, photometric), nxt)
 
     def export_outputs(self):
         """Keras prediction-model outputs (models/retinanet.py:302-335): [boxes3D, cls probs, mask probs]."""
@@ -1276,7 +1282,7 @@ class Engine(object):
             self._sparse_fwd_now = False
 
     def train_step_from_annotations(self, images_u8, annotations, image_group=None, transforms=None, border="replicate", cval=0,
-                                    next_batch=None):
+                                    next_batch=None, photometric=None):
         """The lean feed of one optimisation step: a uint8 BGR batch [B,H,W,3] (cuda, or pinned host memory) and the raw
         annotation dicts of preprocessing/generator.py:142-226 (bboxes, labels, poses, segmentations, cam_params, mask,
         mask_ids).  Mean subtraction + packing (image.py:58-60, generator.py:320-336) and target assignment
@@ -1285,8 +1291,12 @@ class Engine(object):
         device like apply_transform (utils/image.py:207-214: bilinear, border = TransformParameters.fill_mode: 'replicate' for
         the default 'nearest', or 'constant' with cval) and the id mask like apply_transform2mask; the caller has already
         moved boxes / poses (generator.py:252-286 does that on the host: a few numbers per object).
-        next_batch: dict(images_u8=, image_group=, transforms=, border=, cval=) of the NEXT call (the generator's look-ahead; the
-        same images_u8 object must come back): its upload, warp and frozen prefix run beside this step (forward_u8)."""
+        photometric: a utils.photometric.PhotoPrograms (sample_programs / compile_chain: one op list per image) -- the imgaug
+        chain of utils/image.py:154-191 (blur, hue / saturation / grayscale, brightness, contrast), applied to the image on the
+        device BEFORE the warp, as the reference does; the id mask is never touched.  None: nothing is launched or allocated.
+        next_batch: dict(images_u8=, image_group=, transforms=, border=, cval=, photometric=) of the NEXT call (the generator's
+        look-ahead; the same images_u8 object must come back): its upload, chain, warp and frozen prefix run beside this step
+        (forward_u8)."""
         from .utils import anchors as UA
         if getattr(self, "_anchors_f64", None) is None:
             self._anchors_f64 = UA.anchors_for_shape_device((self.H, self.W), pyramid_levels=list(arch.PYRAMID_LEVELS[self.pyramid]),
@@ -1306,11 +1316,11 @@ class Engine(object):
             nxd = nimg if nimg.is_cuda else nimg.cuda(non_blocking=True)
             self._next_dev = (nimg, nxd)
             nb = dict(images_u8=nxd, sizes_hw=sizes(next_batch.get("image_group")), transforms=next_batch.get("transforms"),
-                      border=next_batch.get("border", "replicate"), cval=next_batch.get("cval", 0))
+                      border=next_batch.get("border", "replicate"), cval=next_batch.get("cval", 0), photometric=next_batch.get("photometric"))
         if image_group is None:
             image_group = [np.empty((self.H, self.W, 3), np.uint8)] * self.B  # only the shapes are read
         self.set_targets(*UA.anchor_targets_bbox_device(self._anchors_f64, image_group, annotations, self.C, mask_transforms=transforms))
-        self._train_forward(lambda: self.forward_u8(xd, sizes(image_group), transforms, border, cval, next_batch=nb))
+        self._train_forward(lambda: self.forward_u8(xd, sizes(image_group), transforms, border, cval, next_batch=nb, photometric=photometric))
         self.loss_and_backward()
         if self.grad_sync is not None:
             self.grad_sync.finish()

@@ -392,6 +392,29 @@ def warp_affine_u8(ctx, images_u8, matrices, interpolation="linear", border="rep
     return out
 
 
+def photo_augment_u8(ctx, images_u8, programs, out=None):
+    """The photometric chain of utils/image.py:154-191 per image of a uint8 BGR batch [B,H,W,3]: programs = a
+    utils.photometric.PhotoPrograms of B op lists (compile_chain / sample_programs).  Enqueues on the context's stream, which
+    must be torch's current stream: the table pool goes up with a non-blocking torch copy from pinned memory, so torch's host
+    allocator knows when the pinned block may be reused -- `programs` may be dropped as soon as this returns."""
+    if images_u8.dim() != 4:
+        raise ValueError("photo_augment_u8: a [B,H,W,3] batch, got %s" % (tuple(images_u8.shape),))
+    B, H, W, ch = images_u8.shape
+    assert images_u8.dtype == torch.uint8 and images_u8.is_contiguous()
+    if len(programs) != B:
+        raise ValueError("photo_augment_u8: %d programs for %d images" % (len(programs), B))
+    if out is None:
+        out = torch.empty_like(images_u8)
+    nbytes = int(programs.pool.size)
+    pool_dev = programs.pinned_pool().to(images_u8.device, non_blocking=True)
+    ws = torch.empty(lib.pp_photo_workspace_bytes(B, H, W), dtype=torch.uint8, device=images_u8.device)
+    offs, recs = programs.op_offsets, programs.ops
+    check(lib.pp_photo_augment_u8(ctx.handle, B, H, W, ch, offs.ctypes.data, recs.ctypes.data if recs.size else None,
+                                  programs.pool.ctypes.data if nbytes else None, nbytes, _ptr(pool_dev), _ptr(images_u8), _ptr(out), _ptr(ws),
+                                  ws.numel()), ctx.handle, "pp_photo_augment_u8")
+    return out
+
+
 def resize_scale(rows, cols, min_side=480, max_side=640):
     s = C.c_double(0)
     check(lib.pp_resize_scale(int(rows), int(cols), int(min_side), int(max_side), C.byref(s)), None, "pp_resize_scale")
