@@ -634,6 +634,36 @@ int pp_pnp_refine_weighted_f64(pp_ctx* ctx, int n_problems, const int* offsets_d
                                double* R_out, double* t_out, double* rvec_out, double* cost_init, double* cost_final,
                                int* iterations, int* status, double* pose_cov);
 
+/* ---- clustering of each class's votes into object instances (csrc/cluster.hip) --------------------------------------
+ * Replaces nothing in the reference -- a stated deviation: the reference pools every vote of a class into one RANSAC problem
+ * and scores it against the first annotation of that class, because "occurences of 2 or more instances not possible in
+ * LINEMOD" (utils/tless_eval.py:378); T-LESS scenes do hold several instances of one object.  This step, the library's own,
+ * decides which votes form a problem; everything after it is already batched over problems (pp_pnp_ransac_f64, ...).
+ * One workgroup per (image, class), directly on the outputs of pp_score_threshold_compact: boxes3d [B,N,16], scores [B,N,C]
+ * float32, idx [B,C,cap] (ascending anchors, -1 padded), counts [B,C] (values above cap count as cap).
+ *   vote box: axis-aligned box of the vote's 8 corners, float32 min / max.  A vote with a non-finite corner (or an anchor
+ *     outside [0, n)) is invalid: it never leads, never joins, instance -1.
+ *   IoU: float64 on the float32 boxes, no "+1": w = max(0, min(x2a,x2b) - max(x1a,x1b)), h likewise, inter = w h,
+ *     ua = (x2a-x1a)(y2a-y1a) + (x2b-x1b)(y2b-y1b) - inter, iou = inter / ua if ua > 0 else 0; every product and sum
+ *     rounded on its own (no FMA contraction), as numpy does it.
+ *   rounds: the leader is the unassigned valid vote with the highest class score (float32 compare, ties -> lowest anchor);
+ *     its members are the leader and every unassigned valid vote with iou(leader, vote) > iou_thr; members are consumed
+ *     whether or not the cluster is kept; a cluster of at least min_votes members is kept and gets the next instance id
+ *     (dense from 0 in order of creation), a smaller one is dropped (-1).  Stops when nothing valid is unassigned, when
+ *     max_instances clusters are kept, or after max_rounds leaders; what is still unassigned gets -1.
+ * Out: inst [B,C,cap] int32 instance id per input vote (-1: padding, dropped, invalid); order [B,C,cap] the anchor indices of
+ * the kept votes, instance-major and ascending within an instance, -1 padded; inst_offsets [B,C,max_instances+1] into order
+ * (entries past n_inst repeat the total); n_inst [B,C]; leader [B,C,max_instances] anchor index (-1 unused); inst_box
+ * [B,C,max_instances,4] float32 (x1, y1, x2, y2) of the leader's vote box (0 unused).  Integer reductions in a fixed order:
+ * bit-identical run to run and independent of the batch a problem sits in.  Any count up to cap works (boxes beyond the LDS
+ * cache are recomputed from boxes3d); an empty (image, class) costs one workgroup that exits at once.
+ * Errors: null pointers, batch / n / n_class / cap / min_votes / max_instances / max_rounds < 1, iou_thr outside [0, 1):
+ * PP_ERR_ARG.  workspace >= pp_vote_cluster_workspace_bytes (0 today: workspace may be NULL). */
+size_t pp_vote_cluster_workspace_bytes(int batch, int n_class, int cap, int max_instances);
+int pp_vote_cluster(pp_ctx* ctx, int batch, int n, int n_class, int cap, const float* boxes3d, const float* scores,
+                    const int* idx, const int* counts, double iou_thr, int min_votes, int max_instances, int max_rounds,
+                    void* workspace, int* inst, int* order, int* inst_offsets, int* n_inst, int* leader, float* inst_box);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,8 @@ _SIGS = {
     "pp_vote_stats_f64": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _i, _d, _p, _p, _p, _p, _p, _p, _p]),
     "pp_pnp_refine_weighted_workspace_bytes": (_sz, [_i, _i]),
     "pp_pnp_refine_weighted_f64": (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _i, _d, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "pp_vote_cluster_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pp_vote_cluster": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _d, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 EXPORTS = sorted(_SIGS)

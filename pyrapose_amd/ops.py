@@ -924,3 +924,36 @@ def pnp_refine_weighted(ctx, offsets, obj, img, wgt, K4, R_init, t_init, max_ite
                                          _ptr(out["cost_init"]), _ptr(out["cost_final"]), _ptr(out["iterations"]), _ptr(out["status"]),
                                          _ptr(out["pose_cov"])), ctx.handle, "pp_pnp_refine_weighted_f64")
     return out
+
+
+def vote_cluster(ctx, boxes3D, scores, idx, cnt, iou=0.5, min_votes=10, max_instances=8, max_rounds=None):
+    """Each (image, class) vote list split into object instances by vote-box IoU (pp_vote_cluster; the library's own step, the
+    reference assumes one object per class per image): cuda tensors boxes3D float32 [B,N,16], scores float32 [B,N,C], and
+    idx int32 [B,C,cap], cnt int32 [B,C] as score_threshold_compact returns them.  Greedy rounds: the best-scored unassigned
+    vote leads, every unassigned vote whose box overlaps the leader's with IoU > iou joins, a cluster of at least min_votes
+    members becomes the next instance; at most max_instances instances and max_rounds (default 4 * max_instances) leaders.
+    -> (inst int32 [B,C,cap] instance per input vote or -1, order int32 [B,C,cap] anchor indices instance-major (-1 padded),
+    inst_offsets int32 [B,C,max_instances+1] into order, n_inst int32 [B,C], leader int32 [B,C,max_instances] anchor or -1,
+    inst_box float32 [B,C,max_instances,4] the leader's (x1, y1, x2, y2))."""
+    for name, a, dt, nd in (("boxes3D", boxes3D, torch.float32, 3), ("scores", scores, torch.float32, 3), ("idx", idx, torch.int32, 3),
+                            ("cnt", cnt, torch.int32, 2)):
+        if not torch.is_tensor(a) or a.dtype != dt or not a.is_cuda or a.dim() != nd:
+            raise ValueError("vote_cluster: %s must be a cuda %s tensor with %d dimensions" % (name, str(dt).split(".")[-1], nd))
+    B, N, Cc = scores.shape
+    cap = int(idx.shape[2])
+    if tuple(boxes3D.shape) != (B, N, 16) or tuple(idx.shape) != (B, Cc, cap) or tuple(cnt.shape) != (B, Cc):
+        raise ValueError("vote_cluster: need boxes3D [B,N,16], scores [B,N,C], idx [B,C,cap], cnt [B,C]")
+    mi = int(max_instances)
+    mr = 4 * mi if max_rounds is None else int(max_rounds)
+    boxes3D, scores, idx, cnt = boxes3D.contiguous(), scores.contiguous(), idx.contiguous(), cnt.contiguous()
+    dev = scores.device
+    e = lambda shape, dt=torch.int32: torch.empty(shape, dtype=dt, device=dev)
+    inst, order = e((B, Cc, cap)), e((B, Cc, cap))
+    offs, n_inst, leader = e((B, Cc, max(mi, 0) + 1)), e((B, Cc)), e((B, Cc, max(mi, 1)))
+    box = e((B, Cc, max(mi, 1), 4), torch.float32)
+    nb = lib.pp_vote_cluster_workspace_bytes(B, Cc, cap, mi)
+    ws = torch.empty((nb,), dtype=torch.uint8, device=dev) if nb else None
+    check(lib.pp_vote_cluster(ctx.handle, B, N, Cc, cap, _ptr(boxes3D), _ptr(scores), _ptr(idx), _ptr(cnt), float(iou), int(min_votes), mi, mr,
+                              _ptr(ws), _ptr(inst), _ptr(order), _ptr(offs), _ptr(n_inst), _ptr(leader), _ptr(box)), ctx.handle,
+          "pp_vote_cluster")
+    return inst, order, offs, n_inst, leader, box

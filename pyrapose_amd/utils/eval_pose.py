@@ -22,6 +22,37 @@ def quat2mat(q):
     return np.array([[1.0 - (yY + zZ), xY - wZ, xZ + wY], [xY + wZ, 1.0 - (xX + zZ), yZ - wX], [xZ - wY, yZ + wX, 1.0 - (xX + yY)]])
 
 
+def match_instances(t_est, t_gt):
+    """Detections to annotations of one class, one to one: all pairwise translation errors |t_est[i] - t_gt[j]|, assigned
+    greedily by ascending error (ties in (detection, annotation) index order), each side used once.  t_est [n,3], t_gt [m,3]
+    -> list of (detection, annotation) pairs in the order they were assigned, min(n, m) long.  The reference has no such step:
+    it scores against the first annotation of the class (tless_eval.py:378)."""
+    a = np.asarray(t_est, np.float64).reshape(-1, 3)
+    g = np.asarray(t_gt, np.float64).reshape(-1, 3)
+    if len(a) == 0 or len(g) == 0:
+        return []
+    err = np.linalg.norm(a[:, None, :] - g[None, :, :], axis=2)
+    used_d, used_g, pairs = set(), set(), []
+    for flat in np.argsort(err.reshape(-1), kind="stable"):                  # stable: ties stay in (i, j) order
+        i, j = divmod(int(flat), len(g))
+        if i in used_d or j in used_g:
+            continue
+        used_d.add(i)
+        used_g.add(j)
+        pairs.append((i, j))
+    return pairs
+
+
+def _class_pairs(group, cls, labels, anno, gt_translation_scale, instances):
+    """(detection, annotation index) pairs of one class: every detection against the first annotation of the class (the
+    reference, instances=None), or match_instances over all its annotations, in detection order"""
+    if instances is None:
+        return [(d, labels.index(cls)) for d in group]
+    gts = [gi for gi, lab in enumerate(labels) if lab == cls]
+    t_gt = [np.asarray(anno["poses"][gi], np.float64)[:3] * gt_translation_scale for gi in gts]
+    return [(group[i], gts[j]) for i, j in sorted(match_instances([d["t"] for d in group], t_gt))]
+
+
 def _refine(dets, refine, load_depth, index, mask_out, K, models):
     """the opt-in ICP step (utils.icp.refine_poses with the keyword arguments in `refine`) on the detections of one image"""
     from . import icp
@@ -34,7 +65,8 @@ def _refine(dets, refine, load_depth, index, mask_out, K, models):
 
 
 def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_diameters, K=None, threshold=0.5, min_votes=10,
-                 symmetric_classes=(), gt_translation_scale=0.001, seed=0, refine=None, load_depth=None, weighting=None):
+                 symmetric_classes=(), gt_translation_scale=0.001, seed=0, refine=None, load_depth=None, weighting=None,
+                 instances=None):
     """generator: load_image / preprocess_image / resize_image / load_annotations / size() (preprocessing/generator.py);
     predict_on_batch: the prediction model's method (x [1,H,W,3] -> [boxes3D, scores, mask]);
     threeD_boxes [C,8,3], model_points: list of [n_c,3], model_diameters [C] -- all in the unit of the estimated translation
@@ -44,7 +76,10 @@ def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_
     'models': meshes to refine against, default model_points): the detections of each image are then refined against
     load_depth(index) (millimetres) inside the network's mask output before scoring, and each error tuple gains (refined,
     fitness).  weighting: None, 'corners' or 'scores' -- the uncertainty-weighted refinement of
-    pose_decode.poses_from_outputs on every RANSAC pose (before the optional ICP).  Returns dict(allPoses, trueDets, truePoses, recall, detections, recall_all, detections_all, errors) with the
+    pose_decode.poses_from_outputs on every RANSAC pose (before the optional ICP).  instances: None (one pose per class, scored
+    against the first annotation of the class, as the reference does), or the dict of poses_from_outputs: poses are decoded per
+    object instance, matched per class to all annotations of that class (match_instances), every matched pair is scored as the
+    single pair is otherwise, trueDets counts matched pairs and each error tuple gains (instance, gt).  Returns dict(allPoses, trueDets, truePoses, recall, detections, recall_all, detections_all, errors) with the
     reference's 1-based class indexing."""
     C = len(model_diameters)
     if K is None:
@@ -61,20 +96,29 @@ def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_
         for lab in labels:
             allPoses[lab + 1] += 1
         boxes3D, scores, _mask = predict_on_batch(np.expand_dims(image, axis=0))
-        poses = pose_decode.poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=threshold, min_votes=min_votes, seed=seed + index, weighting=weighting)
+        poses = pose_decode.poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=threshold, min_votes=min_votes, seed=seed + index, weighting=weighting,
+                                                instances=instances)
         if refine is not None:
             poses = _refine([d for d in poses if d["cls"] in labels], refine, load_depth, index, _mask, K, model_points)
+        if instances is not None:  # per class, detections matched one to one to all annotations of that class
+            poses = [(d, gi) for cls in sorted(set(labels)) for d, gi in
+                     _class_pairs([d for d in poses if d["cls"] == cls], cls, labels, anno, gt_translation_scale, instances)]
         for det in poses:
+            if instances is not None:
+                det, gi = det
             cls = det["cls"]
             if cls not in labels:  # the reference only scores the annotated class (:327-329)
                 continue
             trueDets[cls + 1] += 1
-            gi = labels.index(cls)
+            if instances is None:
+                gi = labels.index(cls)
             pose = np.asarray(anno["poses"][gi], np.float64)
             R_gt, t_gt = quat2mat(pose[3:]), pose[:3] * gt_translation_scale
             fn = pose_error.adi if cls in symmetric_classes else pose_error.add
             err = fn(det["R"], det["t"].reshape(3, 1), R_gt, t_gt.reshape(3, 1), model_points[cls])
             errors.append((index, cls, float(err)) if refine is None else (index, cls, float(err), det["refined"], det["fitness"]))
+            if instances is not None:
+                errors[-1] = errors[-1] + (det["instance"], gi)
             if det["ok"] and err < model_diameters[cls] * 0.1:
                 truePoses[cls + 1] += 1
     with np.errstate(divide="ignore", invalid="ignore"):
@@ -90,7 +134,7 @@ ADD_FRACTIONS = tuple(round(0.05 * k, 2) for k in range(1, 20))  # tless_eval.py
 
 def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, model_diameters, load_depth, K, threshold=0.5, min_votes=10,
                           delta=0.3, tau=20.0, vsd_threshold=0.3, cost_type="step", symmetric_classes=(), gt_translation_scale=0.001,
-                          depth_scale=1000.0, seed=0, refine=None, weighting=None):
+                          depth_scale=1000.0, seed=0, refine=None, weighting=None, instances=None):
     """The metric block of tless_eval.py:470-725 (also in occlusion_eval.py / ycbv_eval.py / homebrewed_eval.py) on top of the
     loop of evaluate_add: per detected, annotated class, the rotation / translation errors re / te (correct when re < 5 deg
     and te < 0.05), the reprojection error (< 5 px), VSD against the image's depth (< vsd_threshold) and ADD (ADI for
@@ -102,7 +146,8 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
     millimetres with delta / tau as the reference passes them, 0.3 / 20).  One launch per metric per (image, class).
     refine: None, or the keyword arguments of utils.icp.refine_poses: the detections of each image are then refined against
     its depth inside the network's mask output before scoring, and each error dict gains 'refined' and 'fitness'.
-    weighting: as in evaluate_add.
+    weighting: as in evaluate_add.  instances: as in evaluate_add (None: today's one pose per class against the first
+    annotation of the class); with a dict each error dict gains 'instance' and 'gt' (the annotation index).
     Returns dict(allPoses, trueDets, less5, rep_less5, vsd_less_t, add_less [len(ADD_FRACTIONS), C+1], add_fractions, the
     matching rates (counter / allPoses) and errors: one dict per scored detection); index = class id + 1 as in evaluate_add."""
     C = len(model_diameters)
@@ -121,7 +166,8 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
             out["allPoses"][lab + 1] += 1
         Kc = np.asarray(K(index) if callable(K) else K, np.float64).reshape(3, 3)
         boxes3D, scores, _mask = predict_on_batch(np.expand_dims(image, axis=0))
-        poses = pose_decode.poses_from_outputs(boxes3D, scores, threeD_boxes, Kc, threshold=threshold, min_votes=min_votes, seed=seed + index, weighting=weighting)
+        poses = pose_decode.poses_from_outputs(boxes3D, scores, threeD_boxes, Kc, threshold=threshold, min_votes=min_votes, seed=seed + index, weighting=weighting,
+                                                instances=instances)
         dets = [d for d in poses if d["cls"] in labels]  # the reference only scores the annotated classes
         if not dets:
             continue
@@ -129,13 +175,14 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
         if refine is not None:
             dets = _refine(dets, dict(refine, depth_scale=depth_scale), lambda _i: depth, index, _mask, Kc, models)
         for cls in sorted(set(d["cls"] for d in dets)):
-            group = [d for d in dets if d["cls"] == cls]
-            pose = np.asarray(anno["poses"][labels.index(cls)], np.float64)
-            R_gt, t_gt = quat2mat(pose[3:]), pose[:3] * gt_translation_scale
-            n = len(group)
+            pairs = _class_pairs([d for d in dets if d["cls"] == cls], cls, labels, anno, gt_translation_scale, instances)
+            if not pairs:
+                continue
+            group = [d for d, _gi in pairs]
+            gt = [np.asarray(anno["poses"][gi], np.float64) for _d, gi in pairs]
             R_est = np.stack([d["R"] for d in group])
             t_est = np.stack([np.asarray(d["t"], np.float64).reshape(3) for d in group])
-            R_g, t_g = np.repeat(R_gt[None], n, 0), np.repeat(t_gt[None], n, 0)
+            R_g, t_g = np.stack([quat2mat(p[3:]) for p in gt]), np.stack([p[:3] * gt_translation_scale for p in gt])
             model = models[cls]
             rd = pose_error.re_batch(R_g, R_est)                                 # re(R_gt, R_est) as at tless_eval.py:470
             xyz = pose_error.te_batch(t_g, t_est)
@@ -149,6 +196,8 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
                                    vsd=float(e_vsd[k]), add=float(e_add[k])))
                 if refine is not None:
                     errors[-1].update(refined=d["refined"], fitness=d["fitness"])
+                if instances is not None:
+                    errors[-1].update(instance=d["instance"], gt=pairs[k][1])
                 if not d["ok"]:
                     continue
                 out["less5"][cls + 1] += bool(rd[k] < 5.0 and xyz[k] < 0.05)

@@ -218,14 +218,19 @@ def model_cloud(model, voxel_size, scale=1000.0, ctx=None):
 
 def refine_poses(dets, depth, mask_scores, K, models, mask_threshold=0.5, min_mask_pixels=3000, voxel_size=5.0, normal_radius=10.0,
                  normal_max_nn=10, z_gate=75.0, min_gate_points=50, max_correspondence_distance=10.0, max_iteration=100,
-                 relative_fitness=1e-6, relative_rmse=1e-6, depth_scale=1000.0, ctx=None):
+                 relative_fitness=1e-6, relative_rmse=1e-6, depth_scale=1000.0, ctx=None, box_margin=8.0):
     """Refine the PnP poses of one image against its depth (pyrapose_node.py:662-756).  dets: dicts of
     pose_decode.poses_from_outputs (cls, R, t in model units = metres); depth [h,w] in depth units (millimetres); mask_scores the
     mask output of predict_on_batch for this image, [h/8 * w/8, C] (or [1, ., C]); K 3x3; models: per class a load_ply dict
     ('pts' in metres, 'faces') or a point array; depth_scale: model unit -> depth unit.  All detections run in one ICP batch.
     Returns new dicts: the input's keys with R / t replaced by the refined pose, plus refined, fitness, inlier_rmse and
     iterations.  A detection whose upsampled mask has at most min_mask_pixels pixels, whose scene is empty, or whose ICP fails
-    keeps its input pose with refined=False."""
+    keeps its input pose with refined=False.
+    A detection that carries a 'box' key (x1, y1, x2, y2 in pixels: the per-instance detections of
+    poses_from_outputs(instances=...)) has its class mask restricted, before the min_mask_pixels test and the cloud cut, to the
+    P3 cells whose pixel footprint intersects the box grown by box_margin pixels (default 8: one cell) -- several objects of
+    one class share a mask channel, and the median, the gate and the ICP target must see one of them.  The library's own
+    step; detections without 'box' behave as before."""
     ctx = ctx or default_context()
     d = np.asarray(depth)
     if d.ndim != 2:
@@ -242,7 +247,11 @@ def refine_poses(dets, depth, mask_scores, K, models, mask_threshold=0.5, min_ma
                     ("max_correspondence_distance", max_correspondence_distance)):
         if not v > 0:
             raise ValueError("refine_poses: %s must be positive" % name)
+    if not box_margin >= 0:
+        raise ValueError("refine_poses: box_margin must be >= 0")
     for det in dets:
+        if det.get("box") is not None and (np.asarray(det["box"]).size != 4 or not np.isfinite(np.asarray(det["box"], np.float64)).all()):
+            raise ValueError("refine_poses: box must be four finite numbers (x1, y1, x2, y2)")
         if not 0 <= int(det["cls"]) < ms.shape[1] or int(det["cls"]) >= len(models):
             raise ValueError("refine_poses: class %r has no mask channel or no model" % (det["cls"],))
         if np.asarray(det["R"]).shape != (3, 3) or np.asarray(det["t"]).size != 3:
@@ -266,6 +275,13 @@ def refine_poses(dets, depth, mask_scores, K, models, mask_threshold=0.5, min_ma
     for k, det in enumerate(dets):
         cls = int(det["cls"])
         grid = (ms[:, cls] > mask_threshold).reshape(mh, mw)
+        if det.get("box") is not None:
+            x1, y1, x2, y2 = (float(v) for v in np.asarray(det["box"], np.float64).reshape(4))
+            # pixel p covers [p, p + 1]; a cell is kept when one of its pixels touches the grown box
+            py, px = np.arange(h), np.arange(w)
+            row_hit = np.bincount(rows, weights=((py + 1 >= y1 - box_margin) & (py <= y2 + box_margin)), minlength=mh) > 0
+            col_hit = np.bincount(cols, weights=((px + 1 >= x1 - box_margin) & (px <= x2 + box_margin)), minlength=mw) > 0
+            grid = grid & row_hit[:, None] & col_hit[None, :]
         if float(rcount @ grid.astype(np.float64) @ ccount) <= min_mask_pixels:
             continue
         scene, _ = ops.cloud_from_depth(ctx, dt, fx, fy, cx, cy, 1.0, _dev(grid.astype(np.uint8), torch.uint8), rows_d, cols_d)

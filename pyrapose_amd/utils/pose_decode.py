@@ -15,7 +15,7 @@ from ..runtime import default_context
 
 
 def poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=0.5, min_votes=10, iterations=300, reproj_error=5.0, seed=0,
-                       ctx=None, weighting=None, sigma_floor=0.5):
+                       ctx=None, weighting=None, sigma_floor=0.5, instances=None):
     """boxes3D [B,N,16], scores [B,N,C] (numpy or cuda float32 tensors: predict_on_batch outputs); threeD_boxes [C,8,3]
     cuboid corners per class (model units); K 3x3 or [B,3,3].  Returns one dict per (image, class) that reached
     `min_votes` votes, image-major then class ascending like the reference loop:
@@ -28,9 +28,18 @@ def poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=0.5, min_vote
       'scores':  every inlier vote stays a correspondence with wxx = wyy = its class score, wxy = 0 (pose_weights there).
     The dicts then gain R_ransac, t_ransac, cost (of the returned pose), cost_ransac (of the RANSAC pose under the same
     weights), pose_cov [6,6] and refine_status (ops.WPNP_*); a problem whose RANSAC failed or whose refinement did not end
-    converged / at max_iterations keeps the RANSAC pose."""
+    converged / at max_iterations keeps the RANSAC pose.
+
+    instances: None (one problem per (image, class), the reference's one-object-per-class assumption, tless_eval.py:378), or a
+    dict with any of iou (0.5), max_instances (8), max_rounds (4 * max_instances): the votes of each (image, class) are first
+    clustered into object instances by vote-box IoU (ops.vote_cluster -- the library's own step, no counterpart in the
+    reference) and every instance is its own problem, enumerated (image, class, instance) ascending; `min_votes` then applies
+    per instance and `weighting` per problem as before.  Each dict gains instance, leader (anchor index of the cluster's
+    best-scored vote), box (its vote box x1, y1, x2, y2 in pixels) and score (its class score)."""
     if weighting not in (None, "corners", "scores"):
         raise ValueError("weighting must be None, 'corners' or 'scores'")
+    if instances is not None and (not isinstance(instances, dict) or set(instances) - {"iou", "max_instances", "max_rounds"}):
+        raise ValueError("instances must be None or a dict with iou / max_instances / max_rounds")
     ctx = ctx or default_context()
     dev = lambda a: a.cuda() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
     boxes3D, scores = dev(boxes3D).float().contiguous(), dev(scores).float().contiguous()
@@ -41,20 +50,35 @@ def poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=0.5, min_vote
     if Ks is None:
         raise ValueError("K must be 3x3 or [B,3,3]")
     idx, cnt = ops.score_threshold_compact(ctx, scores, float(threshold))  # bit-exact np.where order
-    # everything below stays on the device until the poses come back: one gather for all (image, class) problems
-    sel = cnt >= max(int(min_votes), 1)                                        # [B, C]
-    if not bool(sel.any()):
-        return []
     cap = idx.shape[2]
-    live = (torch.arange(cap, device="cuda")[None, None, :] < cnt[:, :, None]) & sel[:, :, None]  # [B, C, cap], (b, c, vote) order
-    b_of, c_of, _ = torch.nonzero(live, as_tuple=True)
-    anchor = idx[live].long()
+    if instances is None:
+        # everything below stays on the device until the poses come back: one gather for all (image, class) problems
+        sel = cnt >= max(int(min_votes), 1)                                        # [B, C]
+        if not bool(sel.any()):
+            return []
+        live = (torch.arange(cap, device="cuda")[None, None, :] < cnt[:, :, None]) & sel[:, :, None]  # [B, C, cap], (b, c, vote) order
+        b_of, c_of, _ = torch.nonzero(live, as_tuple=True)
+        anchor = idx[live].long()
+        k = cnt[sel].long()                                                        # votes per problem, (b, c) order
+        pb, pc = torch.nonzero(sel, as_tuple=True)
+    else:
+        # one problem per (image, class, instance): `order` already lists the kept votes instance-major, so the same gather
+        # over its first inst_offsets[.., -1] entries yields the votes in problem order
+        mi = int(instances.get("max_instances", 8))
+        _inst, order, ioffs, n_inst, lead, lbox = ops.vote_cluster(ctx, boxes3D, scores, idx, cnt, float(instances.get("iou", 0.5)),
+                                                                   max(int(min_votes), 1), mi, instances.get("max_rounds"))
+        sel = torch.arange(mi, device="cuda")[None, None, :] < n_inst[:, :, None]  # [B, C, max_instances]
+        if not bool(sel.any()):
+            return []
+        live = torch.arange(cap, device="cuda")[None, None, :] < ioffs[:, :, mi:]
+        b_of, c_of, _ = torch.nonzero(live, as_tuple=True)
+        anchor = order[live].long()
+        k = (ioffs[:, :, 1:] - ioffs[:, :, :-1])[sel].long()                       # votes per problem, (b, c, instance) order
+        pb, pc, pk = torch.nonzero(sel, as_tuple=True)
     img = boxes3D[b_of, anchor, :].double().reshape(-1, 2)
     obj = corners[c_of].reshape(-1, 3)
-    k = cnt[sel].long()                                                        # votes per problem, (b, c) order
     offs = torch.zeros((k.numel() + 1,), dtype=torch.int32, device="cuda")
     offs[1:] = (8 * torch.cumsum(k, 0)).to(torch.int32)
-    pb, pc = torch.nonzero(sel, as_tuple=True)
     K_all = torch.as_tensor(np.stack([[Kb[0, 0], Kb[1, 1], Kb[0, 2], Kb[1, 2]] for Kb in Ks]), dtype=torch.float64, device="cuda")
     R, t, n_in, mask, ok = ops.pnp_ransac(ctx, offs, obj.contiguous(), img.contiguous(), K_all[pb].contiguous(), iterations, reproj_error, seed, 8)
     extra = None
@@ -78,6 +102,8 @@ def poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=0.5, min_vote
         R, t = torch.where(use[:, None, None], ref["R"], R), torch.where(use[:, None], ref["t"], t)
     R, t, mask, ok = R.cpu().numpy(), t.cpu().numpy(), mask.cpu().numpy(), ok.cpu().numpy()
     offs_h, anchor_h, k_h = offs.cpu().numpy(), anchor.cpu().numpy(), k.cpu().numpy()
+    if instances is not None:
+        inst_info = (pk.cpu().numpy(), lead[sel].cpu().numpy(), lbox[sel].cpu().numpy(), scores[pb, lead[sel].long(), pc].cpu().numpy())
     pb, pc = pb.cpu().numpy(), pc.cpu().numpy()
     out, v0 = [], 0
     for p in range(len(k_h)):
@@ -86,5 +112,7 @@ def poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=0.5, min_vote
         if extra is not None:
             out[-1].update(R_ransac=extra["R_ransac"][p], t_ransac=extra["t_ransac"][p], cost=float(extra["cost"][p]),
                            cost_ransac=float(extra["cost_ransac"][p]), pose_cov=extra["pose_cov"][p], refine_status=int(extra["refine_status"][p]))
+        if instances is not None:
+            out[-1].update(instance=int(inst_info[0][p]), leader=int(inst_info[1][p]), box=inst_info[2][p], score=float(inst_info[3][p]))
         v0 += int(k_h[p])
     return out
