@@ -16,10 +16,9 @@
 // Compiled with -ffp-contract=off: tests/icp_np.py evaluates the same expressions in the same order.
 #include <float.h>
 #include <math.h>
-#include "pp_internal.h"
+#include "pose_common.h"
 
 #define CLOUD_THREADS 256
-#define SCAN_THREADS 1024
 #define VOX_THREADS 256
 #define NRM_THREADS 64       // one wave; per-thread neighbour lists live in LDS
 #define NRM_MAXNN 32
@@ -28,8 +27,6 @@
 #define ICP_NV 29            // partial sums per tile: plane 21 JTJ + 6 JTr + count + SSE; point 3 + 3 + 9 (+ 12 unused) + count + SSE
 #define ICP_STRIDE 32
 #define ICP_SWEEPS 10
-
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---- point cloud from depth ----------------------------------------------------------------------------------------------
 
@@ -58,31 +55,6 @@ cloud_count_kernel(int width, const float* __restrict__ depth, const unsigned ch
     __syncthreads();
   }
   if (tid == 0) row_cnt[r] = red[0];
-}
-
-// one workgroup: offsets[i] = sum of counts[0..i), offsets[n] = total
-__global__ void __launch_bounds__(SCAN_THREADS) icp_scan_kernel(int n, const int* __restrict__ counts, int* __restrict__ offsets) {
-  __shared__ int s[SCAN_THREADS];
-  __shared__ int carry;
-  const int tid = threadIdx.x;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < n; base += SCAN_THREADS) {
-    const int v = base + tid < n ? counts[base + tid] : 0;
-    s[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < SCAN_THREADS; off <<= 1) {
-      const int u = tid >= off ? s[tid - off] : 0;
-      __syncthreads();
-      s[tid] += u;
-      __syncthreads();
-    }
-    if (base + tid < n) offsets[base + tid] = carry + s[tid] - v;
-    __syncthreads();
-    if (tid == SCAN_THREADS - 1) carry += s[SCAN_THREADS - 1];
-    __syncthreads();
-  }
-  if (tid == 0) offsets[n] = carry;
 }
 
 // create_point_cloud's expressions: x = ((c - cx) z) / fx, y = ((r - cy) z) / fy
@@ -136,7 +108,7 @@ __global__ void cloud_dense_kernel(int width, int hw, const float* __restrict__ 
 
 extern "C" size_t pp_cloud_from_depth_workspace_bytes(int height, int width) {
   if (height <= 0 || width <= 0) return 0;
-  return align256((size_t)height * sizeof(int));
+  return pp_align256((size_t)height * sizeof(int));
 }
 
 extern "C" int pp_cloud_from_depth_f64(pp_ctx* ctx, int height, int width, const float* depth, const unsigned char* mask, int mask_h,
@@ -160,7 +132,7 @@ extern "C" int pp_cloud_from_depth_f64(pp_ctx* ctx, int height, int width, const
   int* row_cnt = (int*)workspace;
   hipLaunchKernelGGL(cloud_count_kernel, dim3(height), dim3(CLOUD_THREADS), 0, ctx->stream, width, depth, mask, mask_w, row_idx, col_idx,
                      ds, row_cnt);
-  hipLaunchKernelGGL(icp_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, height, (const int*)row_cnt, row_offsets);
+  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, height, (const int*)row_cnt, row_offsets, (int*)nullptr);
   hipLaunchKernelGGL(cloud_scatter_kernel, dim3(height), dim3(CLOUD_THREADS), 0, ctx->stream, width, depth, mask, mask_w, row_idx, col_idx,
                      fx, fy, cx, cy, ds, (const int*)row_offsets, pts);
   PP_CHECK_LAUNCH(ctx, "pp_cloud_from_depth_f64");
@@ -737,10 +709,10 @@ __global__ void icp_out_kernel(int P, const icp_state* __restrict__ st, double* 
 
 static size_t icp_layout(int P, int max_src, char* base, icp_state** st, double** partial) {
   const int max_tiles = (max_src + ICP_TILE - 1) / ICP_TILE;
-  const size_t a = align256((size_t)P * sizeof(icp_state));
+  const size_t a = pp_align256((size_t)P * sizeof(icp_state));
   if (st) *st = (icp_state*)base;
   if (partial) *partial = (double*)(base + a);
-  return a + align256((size_t)P * max_tiles * ICP_STRIDE * sizeof(double));
+  return a + pp_align256((size_t)P * max_tiles * ICP_STRIDE * sizeof(double));
 }
 
 extern "C" size_t pp_icp_workspace_bytes(int n_problems, int max_source_points) {

@@ -1,31 +1,18 @@
 // Pose-error metrics of the evaluation tail: ADD and ADD-S/ADI (utils/pose_error.py:210-246, called at
-// utils/linemod_eval.py:525-531 with the decision err < 0.1 * diameter).  float64 like the reference's numpy.
+// utils/linemod_eval.py:525-531 with the decision err < 0.1 * diameter) and the reprojection error (pose_error.py:179-207,
+// tless_eval.py:651-662).  float64 like the reference's numpy.
 //   ADD = mean_i || (R_est p_i + t_est) - (R_gt p_i + t_gt) ||
 //   ADI = mean_i  min_j || (R_gt p_i + t_gt) - (R_est p_j + t_est) ||     (cKDTree(pts_est).query(pts_gt, k=1))
+//   reproj = mean_i || proj(K, R_est, t_est, p_i) - proj(K, R_gt, t_gt, p_i) ||   (float32 pixels and norm)
 // Reductions are fixed-order (per-tile partial sums, then one pass over the tiles): results do not depend on timing.
 // Compiled with -ffp-contract=off: x*x + y*y + z*z is evaluated as written.
-#include "pp_internal.h"
-
-#define POSE_TILE 256
+#include "pose_common.h"
 
 __device__ __forceinline__ void rigid(const double* __restrict__ R, const double* __restrict__ t, double x, double y, double z,
                                       double* ox, double* oy, double* oz) {
   *ox = R[0] * x + R[1] * y + R[2] * z + t[0];
   *oy = R[3] * x + R[4] * y + R[5] * z + t[1];
   *oz = R[6] * x + R[7] * y + R[8] * z + t[2];
-}
-
-__device__ double block_sum(double v, double* red) {
-  const int tid = threadIdx.x;
-  red[tid] = v;
-  __syncthreads();
-  for (int s = POSE_TILE / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
 }
 
 // grid (tiles, poses): partial[pose][tile] = sum over the tile's points of the per-point distance
@@ -43,7 +30,7 @@ __global__ void pose_add_kernel(int n_pts, const double* __restrict__ pts, const
     const double dx = ax - bx, dy = ay - by, dz = az - bz;
     d = sqrt(dx * dx + dy * dy + dz * dz);
   }
-  const double s = block_sum(d, red);
+  const double s = tile_sum256(d, red);
   if (threadIdx.x == 0) partial[(size_t)pose * gridDim.x + blockIdx.x] = s;
 }
 
@@ -68,16 +55,38 @@ __global__ void pose_adi_kernel(int n_pts, const double* __restrict__ pts, const
       best = q < best ? q : best;
     }
   }
-  const double s = block_sum(i < n_pts ? sqrt(best) : 0.0, red);
+  const double s = tile_sum256(i < n_pts ? sqrt(best) : 0.0, red);
   if (threadIdx.x == 0) partial[(size_t)pose * gridDim.x + blockIdx.x] = s;
 }
 
-__global__ void pose_mean_kernel(int n_pose, int n_tiles, int n_pts, const double* __restrict__ partial, double* __restrict__ out) {
-  const int pose = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pose >= n_pose) return;
-  double s = 0.0;
-  for (int t = 0; t < n_tiles; ++t) s += partial[(size_t)pose * n_tiles + t];
-  out[pose] = s / (double)n_pts;
+// pose_error.py:179-207: both poses projected with K, pixels rounded to float32 as the reference's arrays are
+__device__ __forceinline__ void project_f32(const double* __restrict__ K, const double* __restrict__ R, const double* __restrict__ t,
+                                            double x, double y, double z, float* u, float* v) {
+  const double X = R[0] * x + R[1] * y + R[2] * z + t[0];
+  const double Y = R[3] * x + R[4] * y + R[5] * z + t[1];
+  const double Z = R[6] * x + R[7] * y + R[8] * z + t[2];
+  const double a = K[0] * X + K[1] * Y + K[2] * Z, b = K[3] * X + K[4] * Y + K[5] * Z, w = K[6] * X + K[7] * Y + K[8] * Z;
+  *u = (float)(a / w);
+  *v = (float)(b / w);
+}
+
+// grid (tiles, poses): partial[pose][tile] = sum over the tile's points of || est_px - gt_px || (float32 pixels, float32 norm)
+__global__ void pose_reproj_kernel(int n_pts, const double* __restrict__ pts, const double* __restrict__ K9, const double* __restrict__ R_est,
+                                   const double* __restrict__ t_est, const double* __restrict__ R_gt, const double* __restrict__ t_gt,
+                                   double* __restrict__ partial) {
+  __shared__ double red[POSE_TILE];
+  const int pose = blockIdx.y, i = blockIdx.x * POSE_TILE + threadIdx.x;
+  double d = 0.0;
+  if (i < n_pts) {
+    const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
+    float ue, ve, ug, vg;
+    project_f32(K9 + 9 * pose, R_est + 9 * pose, t_est + 3 * pose, x, y, z, &ue, &ve);
+    project_f32(K9 + 9 * pose, R_gt + 9 * pose, t_gt + 3 * pose, x, y, z, &ug, &vg);
+    const float du = ue - ug, dv = ve - vg;
+    d = (double)sqrtf(du * du + dv * dv);
+  }
+  const double s = tile_sum256(d, red);
+  if (threadIdx.x == 0) partial[(size_t)pose * gridDim.x + blockIdx.x] = s;
 }
 
 extern "C" size_t pp_pose_error_workspace_bytes(int n_pose, int n_pts) {
@@ -85,28 +94,17 @@ extern "C" size_t pp_pose_error_workspace_bytes(int n_pose, int n_pts) {
   return (size_t)n_pose * ((n_pts + POSE_TILE - 1) / POSE_TILE) * sizeof(double);
 }
 
-static int pose_error(pp_ctx* ctx, bool symmetric, int n_pose, int n_pts, const double* pts, const double* R_est, const double* t_est,
-                      const double* R_gt, const double* t_gt, void* workspace, double* out, const char* who) {
-  PP_REQUIRE_CTX(ctx);
-  PP_CHECK_ARG(ctx, n_pose > 0 && n_pose <= 65535 && n_pts > 0, PP_ERR_SHAPE, "%s: need 1..65535 poses and at least one model point", who);
-  PP_CHECK_ARG(ctx, pts && R_est && t_est && R_gt && t_gt && workspace && out, PP_ERR_ARG, "%s: null argument", who);
-  const int tiles = (n_pts + POSE_TILE - 1) / POSE_TILE;
-  double* partial = (double*)workspace;
-  if (symmetric)
-    hipLaunchKernelGGL(pose_adi_kernel, dim3(tiles, n_pose), dim3(POSE_TILE), 0, ctx->stream, n_pts, pts, R_est, t_est, R_gt, t_gt, partial);
-  else
-    hipLaunchKernelGGL(pose_add_kernel, dim3(tiles, n_pose), dim3(POSE_TILE), 0, ctx->stream, n_pts, pts, R_est, t_est, R_gt, t_gt, partial);
-  hipLaunchKernelGGL(pose_mean_kernel, dim3((n_pose + 63) / 64), dim3(64), 0, ctx->stream, n_pose, tiles, n_pts, (const double*)partial, out);
-  PP_CHECK_LAUNCH(ctx, who);
-  return PP_OK;
-}
-
 extern "C" int pp_pose_add_f64(pp_ctx* ctx, int n_pose, int n_pts, const double* pts, const double* R_est, const double* t_est,
                                const double* R_gt, const double* t_gt, void* workspace, double* out) {
-  return pose_error(ctx, false, n_pose, n_pts, pts, R_est, t_est, R_gt, t_gt, workspace, out, "pp_pose_add_f64");
+  return tile_mean_launch(ctx, "pp_pose_add_f64", pose_add_kernel, n_pose, n_pts, workspace, out, pts, R_est, t_est, R_gt, t_gt);
 }
 
 extern "C" int pp_pose_adi_f64(pp_ctx* ctx, int n_pose, int n_pts, const double* pts, const double* R_est, const double* t_est,
                                const double* R_gt, const double* t_gt, void* workspace, double* out) {
-  return pose_error(ctx, true, n_pose, n_pts, pts, R_est, t_est, R_gt, t_gt, workspace, out, "pp_pose_adi_f64");
+  return tile_mean_launch(ctx, "pp_pose_adi_f64", pose_adi_kernel, n_pose, n_pts, workspace, out, pts, R_est, t_est, R_gt, t_gt);
+}
+
+extern "C" int pp_pose_reproj_f64(pp_ctx* ctx, int n_pose, int n_pts, const double* pts, const double* K9, const double* R_est,
+                                  const double* t_est, const double* R_gt, const double* t_gt, void* workspace, double* out) {
+  return tile_mean_launch(ctx, "pp_pose_reproj_f64", pose_reproj_kernel, n_pose, n_pts, workspace, out, pts, K9, R_est, t_est, R_gt, t_gt);
 }

@@ -1,4 +1,4 @@
-// Depth renderer and the VSD / reprojection pose errors of the evaluation tail (tless_eval.py:470-471, 651-662 and the
+// Depth renderer and the VSD pose error of the evaluation tail (tless_eval.py:470-471, 651-662 and the
 // same calls in occlusion_eval.py / ycbv_eval.py / homebrewed_eval.py / linemod_eval.py).
 //
 // Renderer: the depth pass of utils/hodan_renderer.py (mode='depth'), which the reference's vsd() (utils/pose_error.py:105-176)
@@ -25,11 +25,11 @@
 // bits whatever order the lists and the atomics run in.
 //
 // VSD: pose_error.py:15-61 + 105-176 per problem on the rendered depth images, float64 where the reference is; per-block
-// partial counts / sums, then one ordered pass per problem.  reproj: pose_error.py:179-207 like pose.hip's ADD.
+// partial counts / sums, then one ordered pass per problem.
 // Compiled with -ffp-contract=off: the host restatements (tests/render_np.py, utils/pose_error.py) evaluate the same
 // expressions in the same order.
 #include <math.h>
-#include "pp_internal.h"
+#include "pose_common.h"
 
 #define RT 32                  // screen tile edge (pixels)
 #define RASTER_THREADS 256
@@ -38,7 +38,6 @@
 #define VSD_THREADS 256
 #define VSD_PER_THREAD 4
 #define VSD_BLOCK (VSD_THREADS * VSD_PER_THREAD)
-#define REPROJ_TILE 256
 
 struct __align__(16) rvtx {
   float x, y;   // screen position (OpenCV pixel coordinates)
@@ -172,35 +171,6 @@ __global__ void render_bin_kernel(int mode, int n_vert, int n_tri, const int* __
     }
 }
 
-// one workgroup: offsets[i] = sum of counts[0..i), offsets[n] = total; cursor = offsets
-__global__ void render_scan_kernel(int n, const int* __restrict__ counts, int* __restrict__ offsets, int* __restrict__ cursor) {
-  __shared__ int s[1024];
-  __shared__ int carry;
-  const int tid = threadIdx.x;
-  if (tid == 0) carry = 0;
-  __syncthreads();
-  for (int base = 0; base < n; base += 1024) {
-    const int v = base + tid < n ? counts[base + tid] : 0;
-    s[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-      const int u = tid >= off ? s[tid - off] : 0;
-      __syncthreads();
-      s[tid] += u;
-      __syncthreads();
-    }
-    const int excl = carry + s[tid] - v;
-    if (base + tid < n) {
-      offsets[base + tid] = excl;
-      cursor[base + tid] = excl;
-    }
-    __syncthreads();
-    if (tid == 1023) carry += s[1023];
-    __syncthreads();
-  }
-  if (tid == 0) offsets[n] = carry;
-}
-
 __device__ __forceinline__ void raster_px(unsigned* zb, const tri_setup& T, int r, int c, int r0, int c0, double zn, double zf) {
   const float z = shade(T, r, c, zn, zf);
   if (z > 0.0f) atomicMin(&zb[(r - r0) * RT + (c - c0)], __float_as_uint(z));
@@ -292,8 +262,6 @@ struct render_ws {
   int *counts, *offsets, *cursor, *list, *big_n, *big;
 };
 
-static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static size_t render_layout(int n_pose, int n_vert, int n_tri, int width, int height, char* base, render_ws* w) {
   const size_t tiles = (size_t)((width + RT - 1) / RT) * ((height + RT - 1) / RT);
   const size_t nb = (size_t)n_pose * tiles;
@@ -303,7 +271,7 @@ static size_t render_layout(int n_pose, int n_vert, int n_tri, int width, int he
   size_t off[7], total = 0;
   for (int i = 0; i < 7; ++i) {
     off[i] = total;
-    total += align256(sizes[i]);
+    total += pp_align256(sizes[i]);
   }
   if (w) {
     w->vtx = (rvtx*)(base + off[0]);
@@ -346,7 +314,7 @@ extern "C" int pp_render_depth_f32(pp_ctx* ctx, int n_pose, int n_vert, const do
   const dim3 tg((n_tri + 255) / 256, n_pose);
   hipLaunchKernelGGL(render_bin_kernel, tg, dim3(256), 0, ctx->stream, 0, n_vert, n_tri, faces, (const rvtx*)w.vtx, width, height,
                      tiles_x, n_tiles, w.counts, w.cursor, w.list, w.big_n, w.big);
-  hipLaunchKernelGGL(render_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, (int)nb, (const int*)w.counts, w.offsets, w.cursor);
+  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, (int)nb, (const int*)w.counts, w.offsets, w.cursor);
   hipLaunchKernelGGL(render_bin_kernel, tg, dim3(256), 0, ctx->stream, 1, n_vert, n_tri, faces, (const rvtx*)w.vtx, width, height,
                      tiles_x, n_tiles, w.counts, w.cursor, w.list, w.big_n, w.big);
   hipLaunchKernelGGL(render_raster_kernel, dim3(n_tiles, n_pose), dim3(RASTER_THREADS), 0, ctx->stream, n_vert, faces,
@@ -452,7 +420,7 @@ __global__ void vsd_final_kernel(int n, int nblk, const double* __restrict__ par
 extern "C" size_t pp_vsd_workspace_bytes(int n, int width, int height) {
   if (n <= 0 || width <= 0 || height <= 0) return 0;
   const size_t nblk = ((size_t)width * height + VSD_BLOCK - 1) / VSD_BLOCK;
-  return align256((size_t)n * nblk * sizeof(double)) + (size_t)n * nblk * 2 * sizeof(int);
+  return pp_align256((size_t)n * nblk * sizeof(double)) + (size_t)n * nblk * 2 * sizeof(int);
 }
 
 extern "C" int pp_vsd_f64(pp_ctx* ctx, int n, int width, int height, const float* depth_test, long long test_stride,
@@ -468,68 +436,11 @@ extern "C" int pp_vsd_f64(pp_ctx* ctx, int n, int width, int height, const float
   PP_CHECK_ARG(ctx, tau > 0.0, PP_ERR_ARG, "pp_vsd_f64: tau must be positive");
   const int hw = width * height, nblk = (hw + VSD_BLOCK - 1) / VSD_BLOCK;
   double* part_cost = (double*)workspace;
-  int* part_cnt = (int*)((char*)workspace + align256((size_t)n * nblk * sizeof(double)));
+  int* part_cnt = (int*)((char*)workspace + pp_align256((size_t)n * nblk * sizeof(double)));
   hipLaunchKernelGGL(vsd_partial_kernel, dim3(nblk, n), dim3(VSD_THREADS), 0, ctx->stream, width, hw, depth_test, test_stride,
                      depth_est, depth_gt, K4, (float)delta, tau, cost_type, part_cost, part_cnt);
   hipLaunchKernelGGL(vsd_final_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, n, nblk, (const double*)part_cost,
                      (const int*)part_cnt, e, inter, uni);
   PP_CHECK_LAUNCH(ctx, "pp_vsd_f64");
-  return PP_OK;
-}
-
-// ---- reprojection error ---------------------------------------------------------------------------------------------------
-
-__device__ __forceinline__ void project_f32(const double* __restrict__ K, const double* __restrict__ R, const double* __restrict__ t,
-                                            double x, double y, double z, float* u, float* v) {
-  const double X = R[0] * x + R[1] * y + R[2] * z + t[0];
-  const double Y = R[3] * x + R[4] * y + R[5] * z + t[1];
-  const double Z = R[6] * x + R[7] * y + R[8] * z + t[2];
-  const double a = K[0] * X + K[1] * Y + K[2] * Z, b = K[3] * X + K[4] * Y + K[5] * Z, w = K[6] * X + K[7] * Y + K[8] * Z;
-  *u = (float)(a / w);
-  *v = (float)(b / w);
-}
-
-// grid (tiles, poses): partial[pose][tile] = sum over the tile's points of || est_px - gt_px || (float32 pixels, float32 norm)
-__global__ void pose_reproj_kernel(int n_pts, const double* __restrict__ pts, const double* __restrict__ K9, const double* __restrict__ R_est,
-                                   const double* __restrict__ t_est, const double* __restrict__ R_gt, const double* __restrict__ t_gt,
-                                   double* __restrict__ partial) {
-  __shared__ double red[REPROJ_TILE];
-  const int pose = blockIdx.y, i = blockIdx.x * REPROJ_TILE + threadIdx.x, tid = threadIdx.x;
-  double d = 0.0;
-  if (i < n_pts) {
-    const double x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-    float ue, ve, ug, vg;
-    project_f32(K9 + 9 * pose, R_est + 9 * pose, t_est + 3 * pose, x, y, z, &ue, &ve);
-    project_f32(K9 + 9 * pose, R_gt + 9 * pose, t_gt + 3 * pose, x, y, z, &ug, &vg);
-    const float du = ue - ug, dv = ve - vg;
-    d = (double)sqrtf(du * du + dv * dv);
-  }
-  red[tid] = d;
-  __syncthreads();
-  for (int s = REPROJ_TILE / 2; s > 0; s >>= 1) {
-    if (tid < s) red[tid] += red[tid + s];
-    __syncthreads();
-  }
-  if (tid == 0) partial[(size_t)pose * gridDim.x + blockIdx.x] = red[0];
-}
-
-__global__ void pose_reproj_mean_kernel(int n_pose, int n_tiles, int n_pts, const double* __restrict__ partial, double* __restrict__ out) {
-  const int pose = blockIdx.x * blockDim.x + threadIdx.x;
-  if (pose >= n_pose) return;
-  double s = 0.0;
-  for (int t = 0; t < n_tiles; ++t) s += partial[(size_t)pose * n_tiles + t];
-  out[pose] = s / (double)n_pts;
-}
-
-extern "C" int pp_pose_reproj_f64(pp_ctx* ctx, int n_pose, int n_pts, const double* pts, const double* K9, const double* R_est,
-                                  const double* t_est, const double* R_gt, const double* t_gt, void* workspace, double* out) {
-  PP_REQUIRE_CTX(ctx);
-  PP_CHECK_ARG(ctx, n_pose > 0 && n_pose <= 65535 && n_pts > 0, PP_ERR_SHAPE, "pp_pose_reproj_f64: need 1..65535 poses and at least one model point");
-  PP_CHECK_ARG(ctx, pts && K9 && R_est && t_est && R_gt && t_gt && workspace && out, PP_ERR_ARG, "pp_pose_reproj_f64: null argument");
-  const int tiles = (n_pts + REPROJ_TILE - 1) / REPROJ_TILE;
-  double* partial = (double*)workspace;
-  hipLaunchKernelGGL(pose_reproj_kernel, dim3(tiles, n_pose), dim3(REPROJ_TILE), 0, ctx->stream, n_pts, pts, K9, R_est, t_est, R_gt, t_gt, partial);
-  hipLaunchKernelGGL(pose_reproj_mean_kernel, dim3((n_pose + 63) / 64), dim3(64), 0, ctx->stream, n_pose, tiles, n_pts, (const double*)partial, out);
-  PP_CHECK_LAUNCH(ctx, "pp_pose_reproj_f64");
   return PP_OK;
 }

@@ -630,18 +630,29 @@ def filter_detections(ctx, boxes, boxes3d, scores, score_thr=0.05, iou_thr=0.5, 
     return ob, o3, osc, ol
 
 
-def pose_errors(ctx, pts, R_est, t_est, R_gt, t_gt, symmetric=False):
-    """ADD (symmetric=False) or ADD-S / ADI (True) of n poses against one model: cuda float64 tensors
-    pts [n_pts,3], R_* [n,3,3], t_* [n,3] -> float64 [n]."""
-    n, n_pts = R_est.shape[0], pts.shape[0]
-    args = [t.contiguous() for t in (pts, R_est, t_est, R_gt, t_gt)]
+def _pose_mean(ctx, fn, name, pts, *poses):
+    """a per-pose mean over model points: entry point `fn`, cuda float64 tensors in ABI order (pts [n_pts,3] first) -> float64 [n]"""
+    n, n_pts = poses[-4].shape[0], pts.shape[0]  # poses end with R_est, t_est, R_gt, t_gt
+    args = [t.contiguous() for t in (pts,) + poses]
     for t in args:
         assert t.dtype == torch.float64 and t.is_cuda
     ws = torch.empty((max(1, lib.pp_pose_error_workspace_bytes(n, n_pts)),), dtype=torch.uint8, device="cuda")
     out = torch.empty((n,), dtype=torch.float64, device="cuda")
-    fn = lib.pp_pose_adi_f64 if symmetric else lib.pp_pose_add_f64
-    check(fn(ctx.handle, n, n_pts, *[_ptr(t) for t in args], _ptr(ws), _ptr(out)), ctx.handle, "pp_pose_adi_f64" if symmetric else "pp_pose_add_f64")
+    check(fn(ctx.handle, n, n_pts, *[_ptr(t) for t in args], _ptr(ws), _ptr(out)), ctx.handle, name)
     return out
+
+
+def pose_errors(ctx, pts, R_est, t_est, R_gt, t_gt, symmetric=False):
+    """ADD (symmetric=False) or ADD-S / ADI (True) of n poses against one model: cuda float64 tensors
+    pts [n_pts,3], R_* [n,3,3], t_* [n,3] -> float64 [n]."""
+    name = "pp_pose_adi_f64" if symmetric else "pp_pose_add_f64"
+    return _pose_mean(ctx, getattr(lib, name), name, pts, R_est, t_est, R_gt, t_gt)
+
+
+def pose_reproj(ctx, pts, K9, R_est, t_est, R_gt, t_gt):
+    """Mean 2-D reprojection error of n poses against one model (pp_pose_reproj_f64): cuda float64 tensors pts [n_pts,3],
+    K9 [n,3,3], R_* [n,3,3], t_* [n,3] -> float64 [n] (pixels)."""
+    return _pose_mean(ctx, lib.pp_pose_reproj_f64, "pp_pose_reproj_f64", pts, K9, R_est, t_est, R_gt, t_gt)
 
 
 def pnp_ransac(ctx, offsets, obj, img, K4, iterations=300, reproj_error=5.0, seed=0, points_per_vote=8):
@@ -710,19 +721,6 @@ def vsd(ctx, depth_test, depth_est, depth_gt, K4, delta, tau, cost_type="step"):
     check(lib.pp_vsd_f64(ctx.handle, n, w, h, _ptr(dt), stride, _ptr(de), _ptr(dg), _ptr(K4), float(delta), float(tau),
                          VSD_COSTS[cost_type], _ptr(ws), _ptr(e), _ptr(inter), _ptr(uni)), ctx.handle, "pp_vsd_f64")
     return e, inter, uni
-
-
-def pose_reproj(ctx, pts, K9, R_est, t_est, R_gt, t_gt):
-    """Mean 2-D reprojection error of n poses against one model (pp_pose_reproj_f64): cuda float64 tensors pts [n_pts,3],
-    K9 [n,3,3], R_* [n,3,3], t_* [n,3] -> float64 [n] (pixels)."""
-    n, n_pts = R_est.shape[0], pts.shape[0]
-    args = [a.contiguous() for a in (pts, K9, R_est, t_est, R_gt, t_gt)]
-    for a in args:
-        assert a.dtype == torch.float64 and a.is_cuda
-    ws = torch.empty((max(1, lib.pp_pose_error_workspace_bytes(n, n_pts)),), dtype=torch.uint8, device="cuda")
-    out = torch.empty((n,), dtype=torch.float64, device="cuda")
-    check(lib.pp_pose_reproj_f64(ctx.handle, n, n_pts, *[_ptr(a) for a in args], _ptr(ws), _ptr(out)), ctx.handle, "pp_pose_reproj_f64")
-    return out
 
 
 ICP_MODES = {"point_to_point": 0, "point_to_plane": 1}

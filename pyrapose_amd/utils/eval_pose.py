@@ -53,15 +53,51 @@ def _class_pairs(group, cls, labels, anno, gt_translation_scale, instances):
     return [(group[i], gts[j]) for i, j in sorted(match_instances([d["t"] for d in group], t_gt))]
 
 
-def _refine(dets, refine, load_depth, index, mask_out, K, models):
+def _refine(dets, refine, depth, mask_out, K, models):
     """the opt-in ICP step (utils.icp.refine_poses with the keyword arguments in `refine`) on the detections of one image"""
     from . import icp
-    if load_depth is None:
-        raise ValueError("refine needs load_depth")
     kw = dict(refine)
     models = kw.pop("models", models)
     m = mask_out.cpu().numpy() if hasattr(mask_out, "cpu") else np.asarray(mask_out)
-    return icp.refine_poses(dets, np.asarray(load_depth(index)), m[0], K, models, **kw)
+    return icp.refine_poses(dets, depth, m[0], K, models, **kw)
+
+
+def _scored_images(generator, predict_on_batch, decode_kw, K, refine, load_depth, models, gt_translation_scale, instances,
+                   depth_always=False):
+    """The per-image loop of evaluate_add and evaluate_pose_metrics, once.  Per image with at least one label: predict, decode
+    (pose_decode.poses_from_outputs with threeD_boxes and the keywords of `decode_kw`, its seed plus the image index), keep the
+    detections of annotated classes (the reference only scores those, linemod_eval.py:327-329), optionally refine them, and
+    pair them per class with annotations (_class_pairs).  K: 3x3 intrinsics or a callable index -> 3x3.
+    load_depth: None, or index -> depth image, called once per image where a detection survived the class filter (with
+    depth_always: on every labelled image, and `refine` then also sees an empty detection list, as evaluate_add has it).
+    Yields (index, labels, anno, Kc, depth or None, mask, pairs_by_class) for every such image, pairs_by_class =
+    [(cls, [(det, annotation index), ...])] with classes ascending and no empty class."""
+    kw = dict(decode_kw)
+    threeD_boxes, seed = kw.pop("threeD_boxes"), kw.pop("seed")
+    for index in range(generator.size()):
+        image = generator.preprocess_image(generator.load_image(index))
+        image, _scale = generator.resize_image(image)
+        anno = generator.load_annotations(index)
+        if len(anno["labels"]) < 1:
+            continue
+        labels = [int(l) for l in anno["labels"]]
+        Kc = np.asarray(K(index) if callable(K) else K, np.float64).reshape(3, 3)
+        boxes3D, scores, mask = predict_on_batch(np.expand_dims(image, axis=0))
+        poses = pose_decode.poses_from_outputs(boxes3D, scores, threeD_boxes, Kc, seed=seed + index, instances=instances, **kw)
+        dets = [d for d in poses if d["cls"] in labels]
+        if refine is not None and load_depth is None:
+            raise ValueError("refine needs load_depth")
+        depth = None
+        if load_depth is not None and (dets or depth_always):
+            depth = np.asarray(load_depth(index))
+            if refine is not None:
+                dets = _refine(dets, refine, depth, mask, Kc, models)
+        pairs_by_class = []
+        for cls in sorted(set(d["cls"] for d in dets)):
+            pairs = _class_pairs([d for d in dets if d["cls"] == cls], cls, labels, anno, gt_translation_scale, instances)
+            if pairs:
+                pairs_by_class.append((cls, pairs))
+        yield index, labels, anno, Kc, depth, mask, pairs_by_class
 
 
 def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_diameters, K=None, threshold=0.5, min_votes=10,
@@ -86,41 +122,25 @@ def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_
         K = np.array([[572.4114, 0.0, 325.2611], [0.0, 573.57043, 242.04899], [0.0, 0.0, 1.0]])
     allPoses, truePoses, trueDets = (np.zeros((C + 1,), np.uint32) for _ in range(3))
     errors = []
-    for index in range(generator.size()):
-        image = generator.preprocess_image(generator.load_image(index))
-        image, _scale = generator.resize_image(image)
-        anno = generator.load_annotations(index)
-        if len(anno["labels"]) < 1:
-            continue
-        labels = [int(l) for l in anno["labels"]]
+    decode_kw = dict(threeD_boxes=threeD_boxes, threshold=threshold, min_votes=min_votes, seed=seed, weighting=weighting)
+    # depth only serves the refinement here, which runs on every labelled image
+    for index, labels, anno, _Kc, _depth, _mask, pairs_by_class in _scored_images(
+            generator, predict_on_batch, decode_kw, K, refine, load_depth if refine is not None else None, model_points,
+            gt_translation_scale, instances, depth_always=True):
         for lab in labels:
             allPoses[lab + 1] += 1
-        boxes3D, scores, _mask = predict_on_batch(np.expand_dims(image, axis=0))
-        poses = pose_decode.poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=threshold, min_votes=min_votes, seed=seed + index, weighting=weighting,
-                                                instances=instances)
-        if refine is not None:
-            poses = _refine([d for d in poses if d["cls"] in labels], refine, load_depth, index, _mask, K, model_points)
-        if instances is not None:  # per class, detections matched one to one to all annotations of that class
-            poses = [(d, gi) for cls in sorted(set(labels)) for d, gi in
-                     _class_pairs([d for d in poses if d["cls"] == cls], cls, labels, anno, gt_translation_scale, instances)]
-        for det in poses:
-            if instances is not None:
-                det, gi = det
-            cls = det["cls"]
-            if cls not in labels:  # the reference only scores the annotated class (:327-329)
-                continue
-            trueDets[cls + 1] += 1
-            if instances is None:
-                gi = labels.index(cls)
-            pose = np.asarray(anno["poses"][gi], np.float64)
-            R_gt, t_gt = quat2mat(pose[3:]), pose[:3] * gt_translation_scale
-            fn = pose_error.adi if cls in symmetric_classes else pose_error.add
-            err = fn(det["R"], det["t"].reshape(3, 1), R_gt, t_gt.reshape(3, 1), model_points[cls])
-            errors.append((index, cls, float(err)) if refine is None else (index, cls, float(err), det["refined"], det["fitness"]))
-            if instances is not None:
-                errors[-1] = errors[-1] + (det["instance"], gi)
-            if det["ok"] and err < model_diameters[cls] * 0.1:
-                truePoses[cls + 1] += 1
+        for cls, pairs in pairs_by_class:
+            for det, gi in pairs:
+                trueDets[cls + 1] += 1
+                pose = np.asarray(anno["poses"][gi], np.float64)
+                R_gt, t_gt = quat2mat(pose[3:]), pose[:3] * gt_translation_scale
+                fn = pose_error.adi if cls in symmetric_classes else pose_error.add
+                err = fn(det["R"], det["t"].reshape(3, 1), R_gt, t_gt.reshape(3, 1), model_points[cls])
+                errors.append((index, cls, float(err)) if refine is None else (index, cls, float(err), det["refined"], det["fitness"]))
+                if instances is not None:
+                    errors[-1] = errors[-1] + (det["instance"], gi)
+                if det["ok"] and err < model_diameters[cls] * 0.1:
+                    truePoses[cls + 1] += 1
     with np.errstate(divide="ignore", invalid="ignore"):
         recall = np.nan_to_num(truePoses / allPoses.astype(np.float64))
         detections = np.nan_to_num(trueDets / allPoses.astype(np.float64))
@@ -155,29 +175,13 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
     out = {k: np.zeros((C + 1,), np.uint32) for k in counters}
     add_less = np.zeros((len(ADD_FRACTIONS), C + 1), np.uint32)
     errors = []
-    for index in range(generator.size()):
-        image = generator.preprocess_image(generator.load_image(index))
-        image, _scale = generator.resize_image(image)
-        anno = generator.load_annotations(index)
-        if len(anno["labels"]) < 1:
-            continue
-        labels = [int(l) for l in anno["labels"]]
+    decode_kw = dict(threeD_boxes=threeD_boxes, threshold=threshold, min_votes=min_votes, seed=seed, weighting=weighting)
+    refine = None if refine is None else dict(refine, depth_scale=depth_scale)
+    for index, labels, anno, Kc, depth, _mask, pairs_by_class in _scored_images(
+            generator, predict_on_batch, decode_kw, K, refine, load_depth, models, gt_translation_scale, instances):
         for lab in labels:
             out["allPoses"][lab + 1] += 1
-        Kc = np.asarray(K(index) if callable(K) else K, np.float64).reshape(3, 3)
-        boxes3D, scores, _mask = predict_on_batch(np.expand_dims(image, axis=0))
-        poses = pose_decode.poses_from_outputs(boxes3D, scores, threeD_boxes, Kc, threshold=threshold, min_votes=min_votes, seed=seed + index, weighting=weighting,
-                                                instances=instances)
-        dets = [d for d in poses if d["cls"] in labels]  # the reference only scores the annotated classes
-        if not dets:
-            continue
-        depth = np.asarray(load_depth(index))
-        if refine is not None:
-            dets = _refine(dets, dict(refine, depth_scale=depth_scale), lambda _i: depth, index, _mask, Kc, models)
-        for cls in sorted(set(d["cls"] for d in dets)):
-            pairs = _class_pairs([d for d in dets if d["cls"] == cls], cls, labels, anno, gt_translation_scale, instances)
-            if not pairs:
-                continue
+        for cls, pairs in pairs_by_class:
             group = [d for d, _gi in pairs]
             gt = [np.asarray(anno["poses"][gi], np.float64) for _d, gi in pairs]
             R_est = np.stack([d["R"] for d in group])

@@ -7,11 +7,85 @@
         est_points = boxes3D[0, cls_indices, :].reshape(k * 8, 1, 2);  obj_points = repeat(threeD_boxes[cls], k)
         retval, rvec, tvec, inliers = cv2.solvePnPRansac(obj_points, est_points, K, None, 300, 5.0, 0.99, ITERATIVE)
 """
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
 from .. import ops
 from ..runtime import default_context
+
+
+def _problems_per_class(idx, cnt, min_votes):
+    """One problem per (image, class) with at least min_votes votes, (b, c) ascending; None when there is none.  The record:
+    pb / pc (/ pk: instance, here None) per problem, b_of / c_of / anchor per vote in problem order, k votes per problem."""
+    sel = cnt >= min_votes                                                     # [B, C]
+    if not bool(sel.any()):
+        return None
+    # everything stays on the device until the poses come back: one gather for all (image, class) problems
+    live = (torch.arange(idx.shape[2], device="cuda")[None, None, :] < cnt[:, :, None]) & sel[:, :, None]  # [B, C, cap], (b, c, vote) order
+    b_of, c_of, _ = torch.nonzero(live, as_tuple=True)
+    pb, pc = torch.nonzero(sel, as_tuple=True)
+    return SimpleNamespace(pb=pb, pc=pc, pk=None, b_of=b_of, c_of=c_of, anchor=idx[live].long(), k=cnt[sel].long())
+
+
+def _problems_per_instance(ctx, boxes3D, scores, idx, cnt, min_votes, instances):
+    """One problem per (image, class, instance) of ops.vote_cluster, ascending; None when there is none.  The record of
+    _problems_per_class with pk set, plus lead / lbox: each problem's leader anchor and its vote box."""
+    mi = int(instances.get("max_instances", 8))
+    _inst, order, ioffs, n_inst, lead, lbox = ops.vote_cluster(ctx, boxes3D, scores, idx, cnt, float(instances.get("iou", 0.5)), min_votes, mi,
+                                                               instances.get("max_rounds"))
+    sel = torch.arange(mi, device="cuda")[None, None, :] < n_inst[:, :, None]  # [B, C, max_instances]
+    if not bool(sel.any()):
+        return None
+    # `order` already lists the kept votes instance-major, so the same gather over its first inst_offsets[.., -1] entries
+    # yields the votes in problem order
+    live = torch.arange(idx.shape[2], device="cuda")[None, None, :] < ioffs[:, :, mi:]
+    b_of, c_of, _ = torch.nonzero(live, as_tuple=True)
+    pb, pc, pk = torch.nonzero(sel, as_tuple=True)
+    return SimpleNamespace(pb=pb, pc=pc, pk=pk, b_of=b_of, c_of=c_of, anchor=order[live].long(),
+                           k=(ioffs[:, :, 1:] - ioffs[:, :, :-1])[sel].long(), lead=lead[sel], lbox=lbox[sel])
+
+
+def _weighted(ctx, pr, ransac, weighting, scores, corners, sigma_floor):
+    """The weighted stage on the RANSAC poses of the problems `pr` (with offs / obj / img / K_p set): (R, t, extra), a problem
+    whose RANSAC failed or whose refinement did not end converged / at max_iterations keeping its RANSAC pose."""
+    R, t, mask, ok = ransac
+    score = scores[pr.b_of, pr.anchor, pr.c_of].double().contiguous()          # one per vote, (b, c, vote) order
+    if weighting == "corners":
+        st = ops.vote_stats(ctx, pr.offs, pr.img, 8, score, mask, "full", float(sigma_floor), check_offsets=False)
+        o8 = (8 * torch.arange(int(pr.k.numel()) + 1, device="cuda")).to(torch.int32)
+        ref = ops.pnp_refine_weighted(ctx, o8, corners[pr.pc].reshape(-1, 3).contiguous(), st["mu"].reshape(-1, 2), st["wgt"].reshape(-1, 3),
+                                      pr.K_p, R, t, check_offsets=False)
+    else:
+        w = score.repeat_interleave(8) * mask.double()
+        wgt = torch.stack([w, torch.zeros_like(w), w], 1).contiguous()
+        ref = ops.pnp_refine_weighted(ctx, pr.offs, pr.obj, pr.img, wgt, pr.K_p, R, t, check_offsets=False)
+    use = (ok != 0) & (ref["status"] <= ops.WPNP_MAX_ITER)
+    extra = dict(R_ransac=R.cpu().numpy(), t_ransac=t.cpu().numpy(), cost=torch.where(use, ref["cost_final"], ref["cost_init"]).cpu().numpy(),
+                 cost_ransac=ref["cost_init"].cpu().numpy(), pose_cov=ref["pose_cov"].cpu().numpy(), refine_status=ref["status"].cpu().numpy())
+    return torch.where(use[:, None, None], ref["R"], R), torch.where(use[:, None], ref["t"], t), extra
+
+
+def _to_dicts(pr, R, t, mask, ok, extra, scores):
+    """the output list of poses_from_outputs, one dict per problem in problem order"""
+    R, t, mask, ok = R.cpu().numpy(), t.cpu().numpy(), mask.cpu().numpy(), ok.cpu().numpy()
+    offs, anchor, k = pr.offs.cpu().numpy(), pr.anchor.cpu().numpy(), pr.k.cpu().numpy()
+    if pr.pk is not None:
+        pk, lead, lbox, lscore = pr.pk.cpu().numpy(), pr.lead.cpu().numpy(), pr.lbox.cpu().numpy(), scores[pr.pb, pr.lead.long(), pr.pc].cpu().numpy()
+    pb, pc = pr.pb.cpu().numpy(), pr.pc.cpu().numpy()
+    out, v0 = [], 0
+    for p in range(len(k)):
+        d = dict(image=int(pb[p]), cls=int(pc[p]), votes=anchor[v0: v0 + k[p]], ok=bool(ok[p]), R=R[p], t=t[p],
+                 inliers=np.nonzero(mask[offs[p]:offs[p + 1]])[0])
+        if extra is not None:
+            d.update(R_ransac=extra["R_ransac"][p], t_ransac=extra["t_ransac"][p], cost=float(extra["cost"][p]),
+                     cost_ransac=float(extra["cost_ransac"][p]), pose_cov=extra["pose_cov"][p], refine_status=int(extra["refine_status"][p]))
+        if pr.pk is not None:
+            d.update(instance=int(pk[p]), leader=int(lead[p]), box=lbox[p], score=float(lscore[p]))
+        out.append(d)
+        v0 += int(k[p])
+    return out
 
 
 def poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=0.5, min_votes=10, iterations=300, reproj_error=5.0, seed=0,
@@ -50,69 +124,18 @@ def poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=0.5, min_vote
     if Ks is None:
         raise ValueError("K must be 3x3 or [B,3,3]")
     idx, cnt = ops.score_threshold_compact(ctx, scores, float(threshold))  # bit-exact np.where order
-    cap = idx.shape[2]
-    if instances is None:
-        # everything below stays on the device until the poses come back: one gather for all (image, class) problems
-        sel = cnt >= max(int(min_votes), 1)                                        # [B, C]
-        if not bool(sel.any()):
-            return []
-        live = (torch.arange(cap, device="cuda")[None, None, :] < cnt[:, :, None]) & sel[:, :, None]  # [B, C, cap], (b, c, vote) order
-        b_of, c_of, _ = torch.nonzero(live, as_tuple=True)
-        anchor = idx[live].long()
-        k = cnt[sel].long()                                                        # votes per problem, (b, c) order
-        pb, pc = torch.nonzero(sel, as_tuple=True)
-    else:
-        # one problem per (image, class, instance): `order` already lists the kept votes instance-major, so the same gather
-        # over its first inst_offsets[.., -1] entries yields the votes in problem order
-        mi = int(instances.get("max_instances", 8))
-        _inst, order, ioffs, n_inst, lead, lbox = ops.vote_cluster(ctx, boxes3D, scores, idx, cnt, float(instances.get("iou", 0.5)),
-                                                                   max(int(min_votes), 1), mi, instances.get("max_rounds"))
-        sel = torch.arange(mi, device="cuda")[None, None, :] < n_inst[:, :, None]  # [B, C, max_instances]
-        if not bool(sel.any()):
-            return []
-        live = torch.arange(cap, device="cuda")[None, None, :] < ioffs[:, :, mi:]
-        b_of, c_of, _ = torch.nonzero(live, as_tuple=True)
-        anchor = order[live].long()
-        k = (ioffs[:, :, 1:] - ioffs[:, :, :-1])[sel].long()                       # votes per problem, (b, c, instance) order
-        pb, pc, pk = torch.nonzero(sel, as_tuple=True)
-    img = boxes3D[b_of, anchor, :].double().reshape(-1, 2)
-    obj = corners[c_of].reshape(-1, 3)
-    offs = torch.zeros((k.numel() + 1,), dtype=torch.int32, device="cuda")
-    offs[1:] = (8 * torch.cumsum(k, 0)).to(torch.int32)
+    mv = max(int(min_votes), 1)
+    pr = _problems_per_class(idx, cnt, mv) if instances is None else _problems_per_instance(ctx, boxes3D, scores, idx, cnt, mv, instances)
+    if pr is None:
+        return []
+    pr.img = boxes3D[pr.b_of, pr.anchor, :].double().reshape(-1, 2).contiguous()
+    pr.obj = corners[pr.c_of].reshape(-1, 3).contiguous()
+    pr.offs = torch.zeros((pr.k.numel() + 1,), dtype=torch.int32, device="cuda")
+    pr.offs[1:] = (8 * torch.cumsum(pr.k, 0)).to(torch.int32)
     K_all = torch.as_tensor(np.stack([[Kb[0, 0], Kb[1, 1], Kb[0, 2], Kb[1, 2]] for Kb in Ks]), dtype=torch.float64, device="cuda")
-    R, t, n_in, mask, ok = ops.pnp_ransac(ctx, offs, obj.contiguous(), img.contiguous(), K_all[pb].contiguous(), iterations, reproj_error, seed, 8)
+    pr.K_p = K_all[pr.pb].contiguous()
+    R, t, _n_in, mask, ok = ops.pnp_ransac(ctx, pr.offs, pr.obj, pr.img, pr.K_p, iterations, reproj_error, seed, 8)
     extra = None
     if weighting is not None:
-        P = int(k.numel())
-        score = scores[b_of, anchor, c_of].double().contiguous()               # one per vote, (b, c, vote) order
-        K_p = K_all[pb].contiguous()
-        if weighting == "corners":
-            st = ops.vote_stats(ctx, offs, img.contiguous(), 8, score, mask, "full", float(sigma_floor), check_offsets=False)
-            o8 = (8 * torch.arange(P + 1, device="cuda")).to(torch.int32)
-            ref = ops.pnp_refine_weighted(ctx, o8, corners[pc].reshape(-1, 3).contiguous(), st["mu"].reshape(-1, 2), st["wgt"].reshape(-1, 3),
-                                          K_p, R, t, check_offsets=False)
-        else:
-            w = score.repeat_interleave(8) * mask.double()
-            wgt = torch.stack([w, torch.zeros_like(w), w], 1).contiguous()
-            ref = ops.pnp_refine_weighted(ctx, offs, obj.contiguous(), img.contiguous(), wgt, K_p, R, t, check_offsets=False)
-        use = (ok != 0) & (ref["status"] <= ops.WPNP_MAX_ITER)
-        extra = dict(R_ransac=R.cpu().numpy(), t_ransac=t.cpu().numpy(), cost_ransac=ref["cost_init"].cpu().numpy(),
-                     cost=torch.where(use, ref["cost_final"], ref["cost_init"]).cpu().numpy(), pose_cov=ref["pose_cov"].cpu().numpy(),
-                     refine_status=ref["status"].cpu().numpy())
-        R, t = torch.where(use[:, None, None], ref["R"], R), torch.where(use[:, None], ref["t"], t)
-    R, t, mask, ok = R.cpu().numpy(), t.cpu().numpy(), mask.cpu().numpy(), ok.cpu().numpy()
-    offs_h, anchor_h, k_h = offs.cpu().numpy(), anchor.cpu().numpy(), k.cpu().numpy()
-    if instances is not None:
-        inst_info = (pk.cpu().numpy(), lead[sel].cpu().numpy(), lbox[sel].cpu().numpy(), scores[pb, lead[sel].long(), pc].cpu().numpy())
-    pb, pc = pb.cpu().numpy(), pc.cpu().numpy()
-    out, v0 = [], 0
-    for p in range(len(k_h)):
-        out.append(dict(image=int(pb[p]), cls=int(pc[p]), votes=anchor_h[v0: v0 + k_h[p]], ok=bool(ok[p]), R=R[p], t=t[p],
-                        inliers=np.nonzero(mask[offs_h[p]:offs_h[p + 1]])[0]))
-        if extra is not None:
-            out[-1].update(R_ransac=extra["R_ransac"][p], t_ransac=extra["t_ransac"][p], cost=float(extra["cost"][p]),
-                           cost_ransac=float(extra["cost_ransac"][p]), pose_cov=extra["pose_cov"][p], refine_status=int(extra["refine_status"][p]))
-        if instances is not None:
-            out[-1].update(instance=int(inst_info[0][p]), leader=int(inst_info[1][p]), box=inst_info[2][p], score=float(inst_info[3][p]))
-        v0 += int(k_h[p])
-    return out
+        R, t, extra = _weighted(ctx, pr, (R, t, mask, ok), weighting, scores, corners, sigma_floor)
+    return _to_dicts(pr, R, t, mask, ok, extra, scores)

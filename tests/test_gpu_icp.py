@@ -35,6 +35,21 @@ def test_back_projection_matches_the_restatement():
     assert icp.cloud_from_depth(d, Kc, mask=np.zeros((6, 8), np.uint8)).shape == (0, 3)
 
 
+@pytest.mark.parametrize("h", [1023, 1024, 1025, 2049])  # below, at and past one 1024-row pass of the row scan; a third pass
+def test_row_offsets_across_the_scan_width(h):
+    from pyrapose_amd import ops
+    from pyrapose_amd.runtime import default_context
+    rng = np.random.default_rng(h)
+    w = 8
+    d = rng.uniform(400, 1200, (h, w)).astype(np.float32)
+    d[rng.uniform(size=d.shape) < 0.5] = 0.0
+    dev = torch.from_numpy(d).cuda()
+    pts, offs = ops.cloud_from_depth(default_context(), dev, 572.4, 573.5, 3.7, h / 2.0, dense=False)
+    assert np.array_equal(offs.cpu().numpy(), np.concatenate([[0], np.cumsum((d != 0).sum(1))]))
+    dense = ops.cloud_from_depth(default_context(), dev, 572.4, 573.5, 3.7, h / 2.0, dense=True).cpu().numpy()
+    assert np.array_equal(pts.cpu().numpy(), dense[np.isfinite(dense).all(1)])
+
+
 def surface_cloud(seed, n=900):
     rng = np.random.default_rng(seed)
     p, _ = asymmetric_cloud(n, seed)
