@@ -508,6 +508,23 @@ int pp_vsd_f64(pp_ctx* ctx, int n, int width, int height, const float* depth_tes
 int pp_pose_reproj_f64(pp_ctx* ctx, int n_pose, int n_pts, const double* pts, const double* K9, const double* R_est,
                        const double* t_est, const double* R_gt, const double* t_gt, void* workspace, double* out);
 
+/* ---- BOP's symmetry-aware pose errors MSSD / MSPD (csrc/pose.hip) ---------------------------------------------------
+ * bop_toolkit's pose_error.mssd / mspd (parity with bop_toolkit unpinned: its definition restated, tests/pose_sym_np.py) for
+ * n_pose pose pairs of ONE model pts [n_pts,3] and one symmetry set shared by the launch: S_R [n_sym,3,3] row-major, S_t
+ * [n_sym,3] (utils/symmetry.py: get_symmetry_transformations, identity first).  With G_s = (R_gt S_R[s], R_gt S_t[s] + t_gt):
+ *   MSSD = min_s max_i || (R_est p_i + t_est) - (G_s.R p_i + G_s.t) ||                         (unit of pts and t)
+ *   MSPD = min_s max_i || proj(K, R_est, t_est, p_i) - proj(K, G_s.R, G_s.t, p_i) ||           (pixels, K9 [n_pose,3,3])
+ * float64 throughout (the projection is the one of pp_pose_reproj_f64 without its rounding to float32).  out [n_pose];
+ * best_sym [n_pose] int32 (NULL = skip): the symmetry that attains the minimum, the lowest index on ties.  Maxima and minima
+ * only: bit-identical run to run.  n_pose <= 65535, n_sym <= 8 * 65535.  workspace >= pp_pose_sym_workspace_bytes. */
+size_t pp_pose_sym_workspace_bytes(int n_pose, int n_pts, int n_sym);
+int pp_pose_mssd_f64(pp_ctx* ctx, int n_pose, int n_pts, int n_sym, const double* pts, const double* S_R, const double* S_t,
+                     const double* R_est, const double* t_est, const double* R_gt, const double* t_gt, void* workspace, double* out,
+                     int* best_sym);
+int pp_pose_mspd_f64(pp_ctx* ctx, int n_pose, int n_pts, int n_sym, const double* pts, const double* S_R, const double* S_t,
+                     const double* K9, const double* R_est, const double* t_est, const double* R_gt, const double* t_gt,
+                     void* workspace, double* out, int* best_sym);
+
 /* ---- RANSAC-PnP of the evaluation tail ----------------------------------------------------------------
  * In place of cv2.solvePnPRansac(obj_points, est_points, K, None, iterationsCount=300, reprojectionError=5.0,
  * confidence=0.99, flags=cv2.SOLVEPNP_ITERATIVE) + cv2.Rodrigues at utils/linemod_eval.py:479-485 (same call in the

@@ -172,6 +172,9 @@ _SIGS = {
     "pp_vsd_workspace_bytes": (_sz, [_i, _i, _i]),
     "pp_vsd_f64": (_i, [_p, _i, _i, _i, _p, _ll, _p, _p, _p, _d, _d, _i, _p, _p, _p, _p]),
     "pp_pose_reproj_f64": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "pp_pose_sym_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pp_pose_mssd_f64": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "pp_pose_mspd_f64": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pp_pnp_ransac_workspace_bytes": (_sz, [_i, _i]),
     "pp_pnp_ransac_f64": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _d, C.c_ulonglong, _i, _p, _p, _p, _p, _p, _p]),
     "pp_cloud_from_depth_workspace_bytes": (_sz, [_i, _i]),

@@ -1,5 +1,5 @@
 // Pieces shared by the evaluation tail (pose.hip, render.hip, icp.hip): the 256-wide tile sum with its mean over tiles, the
-// one-workgroup exclusive scan and the workspace alignment.  Every includer is compiled with -ffp-contract=off.
+// tile maximum, the one-workgroup exclusive scan and the workspace alignment.  Every includer is compiled with -ffp-contract=off.
 // Not here, on purpose: the small-matrix code of pnp.hip / wpnp.hip / icp.hip (solve6 vs wpnp_ldlt, so3_exp_mul vs
 // wpnp_rot_and_jl, the point accumulators) -- each is pinned operation by operation to its own numpy restatement.
 #pragma once
@@ -22,6 +22,32 @@ __device__ __forceinline__ double tile_sum256(double v, double* red) {
   const double r = red[0];
   __syncthreads();
   return r;
+}
+
+// max of each of v[0..N) over the workgroup's POSE_TILE threads, returned to every thread.  A maximum is exact in any order:
+// 64-lane butterflies, then the waves' values through red (N * POSE_TILE / 64 doubles).  NaN never wins a comparison.
+template <int N>
+__device__ __forceinline__ void tile_max256(double (&v)[N], double* red) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    for (int o = 32; o > 0; o >>= 1) {
+      const double u = __shfl_xor(v[k], o, 64);
+      v[k] = u > v[k] ? u : v[k];
+    }
+    if (lane == 0) red[k * (POSE_TILE / 64) + wave] = v[k];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    double r = red[k * (POSE_TILE / 64)];
+    for (int w = 1; w < POSE_TILE / 64; ++w) {
+      const double u = red[k * (POSE_TILE / 64) + w];
+      r = u > r ? u : r;
+    }
+    v[k] = r;
+  }
+  __syncthreads();
 }
 
 // out[pose] = (partial[pose][0] + partial[pose][1] + ...) / n_pts, the tiles in order

@@ -655,6 +655,44 @@ def pose_reproj(ctx, pts, K9, R_est, t_est, R_gt, t_gt):
     return _pose_mean(ctx, lib.pp_pose_reproj_f64, "pp_pose_reproj_f64", pts, K9, R_est, t_est, R_gt, t_gt)
 
 
+POSE_SYM_CHUNK = 8     # symmetries per workgroup of the MSSD / MSPD kernel (csrc/pose.hip)
+POSE_SYM_RANGE = 2048  # model points per workgroup: every further range of this many points is one more workgroup
+
+
+def _pose_sym(ctx, fn, name, pts, S_R, S_t, poses, best_sym):
+    """min over symmetries of a per-pose max over model points: entry point `fn`, cuda float64 tensors, poses in ABI order
+    ([K9,] R_est, t_est, R_gt, t_gt) -> (float64 [n], int32 [n] or None).  Wrong tensors raise ValueError before any launch."""
+    for t in (pts, S_R, S_t) + tuple(poses):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64):
+            raise ValueError("%s: every argument must be a cuda float64 tensor" % name)
+    n, n_pts, n_sym = int(poses[-4].shape[0]), int(pts.shape[0]), int(S_R.shape[0])
+    if tuple(pts.shape) != (n_pts, 3) or tuple(S_R.shape) != (n_sym, 3, 3) or tuple(S_t.shape) != (n_sym, 3):
+        raise ValueError("%s: need pts [n_pts,3], S_R [n_sym,3,3] and S_t [n_sym,3] of one n_sym, got %s, %s, %s" %
+                         (name, tuple(pts.shape), tuple(S_R.shape), tuple(S_t.shape)))
+    for t in poses:
+        if t.shape[0] != n or t.numel() != n * (9 if t.dim() == 3 else 3):
+            raise ValueError("%s: need [n,3,3] matrices and [n,3] translations of one n, got %s" % (name, tuple(t.shape)))
+    args = [t.contiguous() for t in (pts, S_R, S_t) + tuple(poses)]
+    ws = torch.empty((max(1, lib.pp_pose_sym_workspace_bytes(n, n_pts, n_sym)),), dtype=torch.uint8, device="cuda")
+    out = torch.empty((n,), dtype=torch.float64, device="cuda")
+    sym = torch.empty((n,), dtype=torch.int32, device="cuda") if best_sym else None
+    check(fn(ctx.handle, n, n_pts, n_sym, *[_ptr(t) for t in args], _ptr(ws), _ptr(out), _ptr(sym)), ctx.handle, name)
+    return out, sym
+
+
+def pose_mssd(ctx, pts, S_R, S_t, R_est, t_est, R_gt, t_gt, best_sym=True):
+    """BOP's Maximum Symmetry-Aware Surface Distance of n poses against one model and one symmetry set (pp_pose_mssd_f64):
+    cuda float64 tensors pts [n_pts,3], S_R [n_sym,3,3], S_t [n_sym,3] (utils.symmetry.stack_symmetries), R_* [n,3,3], t_*
+    [n,3] -> (err float64 [n], best_sym int32 [n]: the symmetry attaining the minimum, lowest index on ties; None with
+    best_sym=False)."""
+    return _pose_sym(ctx, lib.pp_pose_mssd_f64, "pp_pose_mssd_f64", pts, S_R, S_t, (R_est, t_est, R_gt, t_gt), best_sym)
+
+
+def pose_mspd(ctx, pts, S_R, S_t, K9, R_est, t_est, R_gt, t_gt, best_sym=True):
+    """BOP's Maximum Symmetry-Aware Projection Distance (pp_pose_mspd_f64): as pose_mssd with K9 [n,3,3]; err in pixels."""
+    return _pose_sym(ctx, lib.pp_pose_mspd_f64, "pp_pose_mspd_f64", pts, S_R, S_t, (K9, R_est, t_est, R_gt, t_gt), best_sym)
+
+
 def pnp_ransac(ctx, offsets, obj, img, K4, iterations=300, reproj_error=5.0, seed=0, points_per_vote=8):
     """Batched RANSAC-PnP (pp_pnp_ransac_f64): cuda tensors offsets int32 [P+1], obj float64 [N,3], img float64 [N,2],
     K4 float64 [P,4] -> (R [P,3,3], t [P,3], n_inliers int32 [P], inlier mask uint8 [N], ok int32 [P])."""

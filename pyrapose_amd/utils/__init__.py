@@ -1,6 +1,7 @@
 """The reference's utils/__init__.py:1 re-exports reproj, add, adi, re, te from utils/pose_error.py.  Here they resolve on
-first use (module __getattr__), so that importing a host-only submodule such as utils.anchors does not load the HIP library."""
-_POSE_ERROR_NAMES = ("reproj", "add", "adi", "re", "te")
+first use (module __getattr__), so that importing a host-only submodule such as utils.anchors does not load the HIP library.
+mssd / mspd (BOP's symmetry-aware errors) come beside them."""
+_POSE_ERROR_NAMES = ("reproj", "add", "adi", "re", "te", "mssd", "mspd")
 __all__ = list(_POSE_ERROR_NAMES)
 
 

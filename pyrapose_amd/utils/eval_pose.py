@@ -150,11 +150,14 @@ def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_
 
 
 ADD_FRACTIONS = tuple(round(0.05 * k, 2) for k in range(1, 20))  # tless_eval.py:665-725: 0.05 ... 0.95 x diameter
+# BOP's thresholds of correctness (BOP Challenge 2019 on): MSSD < f x diameter, MSPD < p x (image width / 640) pixels
+BOP_FRACTIONS = tuple(round(0.05 * k, 2) for k in range(1, 11))
+BOP_PIXELS = tuple(5 * k for k in range(1, 11))
 
 
 def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, model_diameters, load_depth, K, threshold=0.5, min_votes=10,
                           delta=0.3, tau=20.0, vsd_threshold=0.3, cost_type="step", symmetric_classes=(), gt_translation_scale=0.001,
-                          depth_scale=1000.0, seed=0, refine=None, weighting=None, instances=None):
+                          depth_scale=1000.0, seed=0, refine=None, weighting=None, instances=None, symmetries=None):
     """The metric block of tless_eval.py:470-725 (also in occlusion_eval.py / ycbv_eval.py / homebrewed_eval.py) on top of the
     loop of evaluate_add: per detected, annotated class, the rotation / translation errors re / te (correct when re < 5 deg
     and te < 0.05), the reprojection error (< 5 px), VSD against the image's depth (< vsd_threshold) and ADD (ADI for
@@ -168,6 +171,12 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
     its depth inside the network's mask output before scoring, and each error dict gains 'refined' and 'fitness'.
     weighting: as in evaluate_add.  instances: as in evaluate_add (None: today's one pose per class against the first
     annotation of the class); with a dict each error dict gains 'instance' and 'gt' (the annotation index).
+    symmetries: None (nothing below is computed or returned), or per class None (no symmetry), a list from
+    utils.symmetry.get_symmetry_transformations or an (S_R, S_t) pair: BOP's MSSD and MSPD (pose_error.mssd / mspd, one launch
+    each per (image, class), MSSD in the unit of the model) are scored too.  Each error dict gains 'mssd', 'mspd' and
+    'sym_mssd', 'sym_mspd' (the symmetry that attains each); the result gains mssd_less / mspd_less [10, C+1] (ok detections
+    with MSSD < BOP_FRACTIONS x the model diameter, MSPD < BOP_PIXELS x depth image width / 640 pixels), their _rate arrays,
+    ar_mssd / ar_mspd [C+1] (the mean of the rates over the ten thresholds) and bop_fractions / bop_pixels.
     Returns dict(allPoses, trueDets, less5, rep_less5, vsd_less_t, add_less [len(ADD_FRACTIONS), C+1], add_fractions, the
     matching rates (counter / allPoses) and errors: one dict per scored detection); index = class id + 1 as in evaluate_add."""
     C = len(model_diameters)
@@ -175,6 +184,13 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
     out = {k: np.zeros((C + 1,), np.uint32) for k in counters}
     add_less = np.zeros((len(ADD_FRACTIONS), C + 1), np.uint32)
     errors = []
+    if symmetries is not None:
+        from .symmetry import stack_symmetries
+        if len(symmetries) != C:
+            raise ValueError("symmetries: need one entry per class (%d), got %d" % (C, len(symmetries)))
+        symmetries = [stack_symmetries(s) for s in symmetries]
+        mssd_less = np.zeros((len(BOP_FRACTIONS), C + 1), np.uint32)
+        mspd_less = np.zeros((len(BOP_PIXELS), C + 1), np.uint32)
     decode_kw = dict(threeD_boxes=threeD_boxes, threshold=threshold, min_votes=min_votes, seed=seed, weighting=weighting)
     refine = None if refine is None else dict(refine, depth_scale=depth_scale)
     for index, labels, anno, Kc, depth, _mask, pairs_by_class in _scored_images(
@@ -194,6 +210,10 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
             mm = dict(model, pts=np.asarray(model["pts"], np.float64) * depth_scale)
             e_vsd = pose_error.vsd_batch(R_est, t_est * depth_scale, R_g, t_g * depth_scale, mm, depth, Kc, delta, tau, cost_type)
             e_add = pose_error.add_batch(R_est, t_est, R_g, t_g, model["pts"], symmetric=cls in symmetric_classes)
+            if symmetries is not None:
+                e_mssd, s_mssd = pose_error.mssd_batch(R_est, t_est, R_g, t_g, model["pts"], symmetries[cls], return_sym=True)
+                e_mspd, s_mspd = pose_error.mspd_batch(R_est, t_est, R_g, t_g, Kc, model["pts"], symmetries[cls], return_sym=True)
+                width = np.shape(depth)[1]
             for k, d in enumerate(group):
                 out["trueDets"][cls + 1] += 1
                 errors.append(dict(image=index, cls=cls, ok=d["ok"], re=float(rd[k]), te=float(xyz[k]), reproj=float(rep[k]),
@@ -202,6 +222,8 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
                     errors[-1].update(refined=d["refined"], fitness=d["fitness"])
                 if instances is not None:
                     errors[-1].update(instance=d["instance"], gt=pairs[k][1])
+                if symmetries is not None:
+                    errors[-1].update(mssd=float(e_mssd[k]), mspd=float(e_mspd[k]), sym_mssd=int(s_mssd[k]), sym_mspd=int(s_mspd[k]))
                 if not d["ok"]:
                     continue
                 out["less5"][cls + 1] += bool(rd[k] < 5.0 and xyz[k] < 0.05)
@@ -209,10 +231,20 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
                 out["vsd_less_t"][cls + 1] += bool(e_vsd[k] < vsd_threshold)
                 for j, f in enumerate(ADD_FRACTIONS):
                     add_less[j, cls + 1] += bool(e_add[k] < model_diameters[cls] * f)
+                if symmetries is not None:
+                    for j, f in enumerate(BOP_FRACTIONS):
+                        mssd_less[j, cls + 1] += bool(e_mssd[k] < f * model_diameters[cls])
+                    for j, p in enumerate(BOP_PIXELS):
+                        mspd_less[j, cls + 1] += bool(e_mspd[k] < p * width / 640.0)
     all_f = out["allPoses"].astype(np.float64)
     with np.errstate(divide="ignore", invalid="ignore"):
         for k in counters[1:]:
             out[k + "_rate"] = np.nan_to_num(out[k] / all_f)
         out["add_less_rate"] = np.nan_to_num(add_less / all_f[None])
+        if symmetries is not None:
+            out.update(mssd_less=mssd_less, mspd_less=mspd_less, mssd_less_rate=np.nan_to_num(mssd_less / all_f[None]),
+                       mspd_less_rate=np.nan_to_num(mspd_less / all_f[None]), bop_fractions=np.array(BOP_FRACTIONS),
+                       bop_pixels=np.array(BOP_PIXELS, np.float64))
+            out.update(ar_mssd=out["mssd_less_rate"].mean(axis=0), ar_mspd=out["mspd_less_rate"].mean(axis=0))
     out.update(add_less=add_less, add_fractions=np.array(ADD_FRACTIONS), errors=errors)
     return out

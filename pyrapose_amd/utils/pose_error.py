@@ -1,7 +1,8 @@
 """Mirror of the pose-error functions the evaluation loops call (utils/pose_error.py:43-75, 105-275;
 utils/linemod_eval.py:525-531, tless_eval.py:470-471, 651-662): same names, arguments and float return values, computed by the
 HIP kernels (ADD / ADI / reproj in csrc/pose.hip, VSD in csrc/render.hip on depth images from utils.renderer); re / te and
-depth_im_to_dist_im stay on the host in numpy."""
+depth_im_to_dist_im stay on the host in numpy.  mssd / mspd are BOP's symmetry-aware errors (bop_toolkit_lib.pose_error), also
+in csrc/pose.hip, over the symmetry sets of utils/symmetry.py."""
 import math
 
 import numpy as np
@@ -81,6 +82,44 @@ def reproj_batch(K, R_est, t_est, R_gt, t_gt, pts):
 def reproj(K, R_est, t_est, R_gt, t_gt, pts):
     """Mean 2-D reprojection error in pixels (pose_error.py:179-207)."""
     return float(reproj_batch(K, R_est, t_est, R_gt, t_gt, pts)[0])
+
+
+def _sym_batch(op, R_est, t_est, R_gt, t_gt, pts, syms, K, return_sym):
+    from .symmetry import stack_symmetries
+    pts = np.asarray(pts, np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+        raise ValueError("pts must be n x 3")
+    S_R, S_t = stack_symmetries(syms)
+    R_est, t_est, R_gt, t_gt = _poses(R_est, t_est, R_gt, t_gt)
+    poses = [_dev(a) for a in (R_est, t_est, R_gt, t_gt)]
+    if K is not None:
+        poses.insert(0, _dev(_stack(K, R_est.shape[0], (3, 3))))
+    err, sym = op(default_context(), _dev(pts), _dev(S_R), _dev(S_t), *poses, best_sym=return_sym)
+    return (err.cpu().numpy(), sym.cpu().numpy()) if return_sym else err.cpu().numpy()
+
+
+def mssd_batch(R_est, t_est, R_gt, t_gt, pts, syms, return_sym=False):
+    """mssd() of n poses of one object in one launch: R_* [n,3,3], t_* [n,3], syms: a list from
+    utils.symmetry.get_symmetry_transformations, an (S_R, S_t) pair or None (the identity) -> float64 [n]; with return_sym also
+    int32 [n], the index of the symmetry that attains each minimum (the lowest on ties)."""
+    return _sym_batch(ops.pose_mssd, R_est, t_est, R_gt, t_gt, pts, syms, None, return_sym)
+
+
+def mspd_batch(R_est, t_est, R_gt, t_gt, K, pts, syms, return_sym=False):
+    """mspd() of n poses of one object in one launch: K 3x3 or [n,3,3], the rest as mssd_batch -> float64 [n] (pixels)."""
+    return _sym_batch(ops.pose_mspd, R_est, t_est, R_gt, t_gt, pts, syms, K, return_sym)
+
+
+def mssd(R_est, t_est, R_gt, t_gt, pts, syms):
+    """Maximum Symmetry-Aware Surface Distance (bop_toolkit_lib.pose_error.mssd, its argument order; parity with bop_toolkit
+    unpinned): min over the symmetry transformations S of max over the model points of |P_est x - P_gt S x|."""
+    return float(mssd_batch(R_est, t_est, R_gt, t_gt, pts, syms)[0])
+
+
+def mspd(R_est, t_est, R_gt, t_gt, K, pts, syms):
+    """Maximum Symmetry-Aware Projection Distance in pixels (bop_toolkit_lib.pose_error.mspd, its argument order; parity with
+    bop_toolkit unpinned): as mssd() between the projections with K, in float64."""
+    return float(mspd_batch(R_est, t_est, R_gt, t_gt, K, pts, syms)[0])
 
 
 def re(R_est, R_gt):
