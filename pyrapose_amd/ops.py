@@ -630,53 +630,109 @@ def filter_detections(ctx, boxes, boxes3d, scores, score_thr=0.05, iou_thr=0.5, 
     return ob, o3, osc, ol
 
 
-def _pose_mean(ctx, fn, name, pts, *poses):
-    """a per-pose mean over model points: entry point `fn`, cuda float64 tensors in ABI order (pts [n_pts,3] first) -> float64 [n]"""
-    n, n_pts = poses[-4].shape[0], pts.shape[0]  # poses end with R_est, t_est, R_gt, t_gt
-    args = [t.contiguous() for t in (pts,) + poses]
-    for t in args:
-        assert t.dtype == torch.float64 and t.is_cuda
-    ws = torch.empty((max(1, lib.pp_pose_error_workspace_bytes(n, n_pts)),), dtype=torch.uint8, device="cuda")
-    out = torch.empty((n,), dtype=torch.float64, device="cuda")
-    check(fn(ctx.handle, n, n_pts, *[_ptr(t) for t in args], _ptr(ws), _ptr(out)), ctx.handle, name)
+# The pose tail (everything below): every argument error is a ValueError raised before anything is enqueued.  The wrappers share
+# one tensor check (_arg), one offsets check (_check_offsets), one workspace allocation (_workspace) and one output allocation (_out).
+
+_F32, _F64, _I32, _U8 = torch.float32, torch.float64, torch.int32, torch.uint8
+
+
+def _arg(what, name, t, dtype, shape, optional=False):
+    """Argument `name` of wrapper `what`: a cuda tensor of `dtype` and `shape` (None: a free dimension) -> t.contiguous();
+    None passes where the argument is optional."""
+    if t is None and optional:
+        return None
+    ok = torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and len(t.shape) == len(shape)
+    if ok:  # (a plain loop costs less than all() over a generator: the small launches of the tail are host-bound)
+        for s, d in zip(shape, t.shape):
+            ok = ok and (s is None or s == d)
+    if not ok:
+        got = "a %s %s tensor %s" % (t.device.type, str(t.dtype)[6:], list(t.shape)) if torch.is_tensor(t) else type(t).__name__
+        raise ValueError("%s: %s must be a cuda %s tensor [%s], got %s" %
+                         (what, name, str(dtype)[6:], ",".join("*" if s is None else str(s) for s in shape), got))
+    return t.contiguous()
+
+
+def _check_offsets(what, offsets, n_total, check, multiple=1, name="offsets"):
+    """offsets int32 [P+1] -> (offsets.contiguous(), their host copy).  With `check` they must rise from 0 to n_total in
+    multiples of `multiple`; without it the host-side look (a sync) is skipped and the copy is None."""
+    offsets = _arg(what, name, offsets, _I32, (None,))
+    if offsets.numel() < 1:
+        raise ValueError("%s: %s must hold P+1 >= 1 entries" % (what, name))
+    if not check:
+        return offsets, None
+    o = offsets.cpu().numpy()
+    if o[0] != 0 or o[-1] != n_total or (np.diff(o) < 0).any() or (o % multiple != 0).any():
+        raise ValueError("%s: %s must rise from 0 to the number of points%s" %
+                         (what, name, " in multiples of points_per_vote" if multiple > 1 else ""))
+    return offsets, o
+
+
+def _workspace(nbytes, refused=None):
+    """The uint8 workspace a *_workspace_bytes call asks for, at least 1 byte.  0 bytes from an entry point that always needs
+    some means the library refuses the shape: ValueError(refused) where given, otherwise the entry point's own check reports it."""
+    if nbytes == 0 and refused:
+        raise ValueError(refused)
+    return torch.empty((max(1, nbytes),), dtype=_U8, device="cuda")
+
+
+def _out(like, shape, dtype=_F64, fill=None):
+    """an output on like's device: uninitialised, or filled with `fill` (one fill kernel)"""
+    if fill is None:
+        return torch.empty(shape, dtype=dtype, device=like.device)
+    return torch.full(shape, fill, dtype=dtype, device=like.device)
+
+
+_POSE_ARGS = (("K9", (3, 3)), ("R_est", (3, 3)), ("t_est", (3,)), ("R_gt", (3, 3)), ("t_gt", (3,)))
+
+
+def _pose_args(what, pts, poses):
+    """pts [n_pts,3] and the poses ([K9,] R_est, t_est, R_gt, t_gt) of one n, in ABI order -> (n, n_pts, checked poses)"""
+    n, out = None, []
+    for (name, tail), t in zip(_POSE_ARGS[-len(poses):], poses):
+        out.append(_arg(what, name, t, _F64, (n,) + tail))
+        n = n or int(out[0].shape[0])
+    return n, int(pts.shape[0]), out
+
+
+def _pose_mean(ctx, what, name, pts, *poses):
+    """a per-pose mean over model points: entry point `name`, cuda float64 tensors in ABI order (pts [n_pts,3] first) -> float64 [n]"""
+    pts = _arg(what, "pts", pts, _F64, (None, 3))
+    n, n_pts, poses = _pose_args(what, pts, poses)
+    ws = _workspace(lib.pp_pose_error_workspace_bytes(n, n_pts))
+    out = _out(pts, (n,))
+    check(getattr(lib, name)(ctx.handle, n, n_pts, _ptr(pts), *[_ptr(t) for t in poses], _ptr(ws), _ptr(out)), ctx.handle, name)
     return out
 
 
 def pose_errors(ctx, pts, R_est, t_est, R_gt, t_gt, symmetric=False):
     """ADD (symmetric=False) or ADD-S / ADI (True) of n poses against one model: cuda float64 tensors
     pts [n_pts,3], R_* [n,3,3], t_* [n,3] -> float64 [n]."""
-    name = "pp_pose_adi_f64" if symmetric else "pp_pose_add_f64"
-    return _pose_mean(ctx, getattr(lib, name), name, pts, R_est, t_est, R_gt, t_gt)
+    return _pose_mean(ctx, "pose_errors", "pp_pose_adi_f64" if symmetric else "pp_pose_add_f64", pts, R_est, t_est, R_gt, t_gt)
 
 
 def pose_reproj(ctx, pts, K9, R_est, t_est, R_gt, t_gt):
     """Mean 2-D reprojection error of n poses against one model (pp_pose_reproj_f64): cuda float64 tensors pts [n_pts,3],
     K9 [n,3,3], R_* [n,3,3], t_* [n,3] -> float64 [n] (pixels)."""
-    return _pose_mean(ctx, lib.pp_pose_reproj_f64, "pp_pose_reproj_f64", pts, K9, R_est, t_est, R_gt, t_gt)
+    return _pose_mean(ctx, "pose_reproj", "pp_pose_reproj_f64", pts, K9, R_est, t_est, R_gt, t_gt)
 
 
 POSE_SYM_CHUNK = 8     # symmetries per workgroup of the MSSD / MSPD kernel (csrc/pose.hip)
 POSE_SYM_RANGE = 2048  # model points per workgroup: every further range of this many points is one more workgroup
 
 
-def _pose_sym(ctx, fn, name, pts, S_R, S_t, poses, best_sym):
-    """min over symmetries of a per-pose max over model points: entry point `fn`, cuda float64 tensors, poses in ABI order
-    ([K9,] R_est, t_est, R_gt, t_gt) -> (float64 [n], int32 [n] or None).  Wrong tensors raise ValueError before any launch."""
-    for t in (pts, S_R, S_t) + tuple(poses):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64):
-            raise ValueError("%s: every argument must be a cuda float64 tensor" % name)
-    n, n_pts, n_sym = int(poses[-4].shape[0]), int(pts.shape[0]), int(S_R.shape[0])
-    if tuple(pts.shape) != (n_pts, 3) or tuple(S_R.shape) != (n_sym, 3, 3) or tuple(S_t.shape) != (n_sym, 3):
-        raise ValueError("%s: need pts [n_pts,3], S_R [n_sym,3,3] and S_t [n_sym,3] of one n_sym, got %s, %s, %s" %
-                         (name, tuple(pts.shape), tuple(S_R.shape), tuple(S_t.shape)))
-    for t in poses:
-        if t.shape[0] != n or t.numel() != n * (9 if t.dim() == 3 else 3):
-            raise ValueError("%s: need [n,3,3] matrices and [n,3] translations of one n, got %s" % (name, tuple(t.shape)))
-    args = [t.contiguous() for t in (pts, S_R, S_t) + tuple(poses)]
-    ws = torch.empty((max(1, lib.pp_pose_sym_workspace_bytes(n, n_pts, n_sym)),), dtype=torch.uint8, device="cuda")
-    out = torch.empty((n,), dtype=torch.float64, device="cuda")
-    sym = torch.empty((n,), dtype=torch.int32, device="cuda") if best_sym else None
-    check(fn(ctx.handle, n, n_pts, n_sym, *[_ptr(t) for t in args], _ptr(ws), _ptr(out), _ptr(sym)), ctx.handle, name)
+def _pose_sym(ctx, what, name, pts, S_R, S_t, poses, best_sym):
+    """min over symmetries of a per-pose max over model points: entry point `name`, cuda float64 tensors, poses in ABI order
+    ([K9,] R_est, t_est, R_gt, t_gt) -> (float64 [n], int32 [n] or None)."""
+    pts = _arg(what, "pts", pts, _F64, (None, 3))
+    S_R = _arg(what, "S_R", S_R, _F64, (None, 3, 3))
+    n_sym = int(S_R.shape[0])
+    S_t = _arg(what, "S_t", S_t, _F64, (n_sym, 3))
+    n, n_pts, poses = _pose_args(what, pts, poses)
+    ws = _workspace(lib.pp_pose_sym_workspace_bytes(n, n_pts, n_sym))
+    out = _out(pts, (n,))
+    sym = _out(pts, (n,), _I32) if best_sym else None
+    check(getattr(lib, name)(ctx.handle, n, n_pts, n_sym, _ptr(pts), _ptr(S_R), _ptr(S_t), *[_ptr(t) for t in poses], _ptr(ws), _ptr(out),
+                             _ptr(sym)), ctx.handle, name)
     return out, sym
 
 
@@ -685,29 +741,27 @@ def pose_mssd(ctx, pts, S_R, S_t, R_est, t_est, R_gt, t_gt, best_sym=True):
     cuda float64 tensors pts [n_pts,3], S_R [n_sym,3,3], S_t [n_sym,3] (utils.symmetry.stack_symmetries), R_* [n,3,3], t_*
     [n,3] -> (err float64 [n], best_sym int32 [n]: the symmetry attaining the minimum, lowest index on ties; None with
     best_sym=False)."""
-    return _pose_sym(ctx, lib.pp_pose_mssd_f64, "pp_pose_mssd_f64", pts, S_R, S_t, (R_est, t_est, R_gt, t_gt), best_sym)
+    return _pose_sym(ctx, "pose_mssd", "pp_pose_mssd_f64", pts, S_R, S_t, (R_est, t_est, R_gt, t_gt), best_sym)
 
 
 def pose_mspd(ctx, pts, S_R, S_t, K9, R_est, t_est, R_gt, t_gt, best_sym=True):
     """BOP's Maximum Symmetry-Aware Projection Distance (pp_pose_mspd_f64): as pose_mssd with K9 [n,3,3]; err in pixels."""
-    return _pose_sym(ctx, lib.pp_pose_mspd_f64, "pp_pose_mspd_f64", pts, S_R, S_t, (K9, R_est, t_est, R_gt, t_gt), best_sym)
+    return _pose_sym(ctx, "pose_mspd", "pp_pose_mspd_f64", pts, S_R, S_t, (K9, R_est, t_est, R_gt, t_gt), best_sym)
 
 
 def pnp_ransac(ctx, offsets, obj, img, K4, iterations=300, reproj_error=5.0, seed=0, points_per_vote=8):
     """Batched RANSAC-PnP (pp_pnp_ransac_f64): cuda tensors offsets int32 [P+1], obj float64 [N,3], img float64 [N,2],
-    K4 float64 [P,4] -> (R [P,3,3], t [P,3], n_inliers int32 [P], inlier mask uint8 [N], ok int32 [P])."""
+    K4 float64 [P,4] -> (R [P,3,3], t [P,3], n_inliers int32 [P], inlier mask uint8 [N], ok int32 [P]).  The offsets' values are
+    not looked at on the host (callers build them on the device)."""
+    offsets, _ = _check_offsets("pnp_ransac", offsets, None, False)
     P = int(offsets.numel()) - 1
+    obj = _arg("pnp_ransac", "obj", obj, _F64, (None, 3))
     N = int(obj.shape[0])
-    assert offsets.dtype == torch.int32 and obj.dtype == torch.float64 and img.dtype == torch.float64 and K4.dtype == torch.float64
-    assert obj.shape == (N, 3) and img.shape == (N, 2) and K4.shape == (P, 4)
-    obj, img, K4, offsets = obj.contiguous(), img.contiguous(), K4.contiguous(), offsets.contiguous()
-    dev = obj.device
-    ws = torch.empty((max(1, lib.pp_pnp_ransac_workspace_bytes(P, int(iterations))),), dtype=torch.uint8, device=dev)
-    R = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
-    t = torch.empty((P, 3), dtype=torch.float64, device=dev)
-    n_in = torch.zeros((P,), dtype=torch.int32, device=dev)
-    mask = torch.zeros((max(N, 1),), dtype=torch.uint8, device=dev)
-    ok = torch.zeros((P,), dtype=torch.int32, device=dev)
+    img = _arg("pnp_ransac", "img", img, _F64, (N, 2))
+    K4 = _arg("pnp_ransac", "K4", K4, _F64, (P, 4))
+    ws = _workspace(lib.pp_pnp_ransac_workspace_bytes(P, int(iterations)))
+    R, t = _out(obj, (P, 3, 3)), _out(obj, (P, 3))
+    n_in, mask, ok = _out(obj, (P,), _I32, 0), _out(obj, (max(N, 1),), _U8, 0), _out(obj, (P,), _I32, 0)
     check(lib.pp_pnp_ransac_f64(ctx.handle, P, _ptr(offsets), N, _ptr(obj), _ptr(img), _ptr(K4), int(iterations), float(reproj_error),
                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(points_per_vote), _ptr(ws), _ptr(R), _ptr(t), _ptr(n_in), _ptr(mask),
                                 _ptr(ok)), ctx.handle, "pp_pnp_ransac_f64")
@@ -717,19 +771,17 @@ def pnp_ransac(ctx, offsets, obj, img, K4, iterations=300, reproj_error=5.0, see
 def render_depth(ctx, verts, faces, R, t, K4, width, height, clip_near=100.0, clip_far=10000.0):
     """Depth images of one mesh at n poses (pp_render_depth_f32): cuda tensors verts float64 [n_vert,3], faces int32
     [n_tri,3], R float64 [n,3,3], t [n,3], K4 [n,4] = (fx, fy, cx, cy) -> float32 [n, height, width], 0 = empty."""
+    verts = _arg("render_depth", "verts", verts, _F64, (None, 3))
+    faces = _arg("render_depth", "faces", faces, _I32, (None, 3))
+    R = _arg("render_depth", "R", R, _F64, (None, 3, 3))
     n, nv, nt = int(R.shape[0]), int(verts.shape[0]), int(faces.shape[0])
-    assert verts.dtype == torch.float64 and R.dtype == torch.float64 and t.dtype == torch.float64 and K4.dtype == torch.float64
-    assert faces.dtype == torch.int32 and verts.shape == (nv, 3) and faces.shape == (nt, 3)
-    assert R.shape == (n, 3, 3) and t.shape == (n, 3) and K4.shape == (n, 4)
-    args = [a.contiguous() for a in (verts, faces, R, t, K4)]
+    t = _arg("render_depth", "t", t, _F64, (n, 3))
+    K4 = _arg("render_depth", "K4", K4, _F64, (n, 4))
     nbytes = lib.pp_render_workspace_bytes(n, nv, nt, int(width), int(height))
-    if nbytes == 0:
-        raise ValueError("render_depth: unsupported shape (n=%d, vertices=%d, triangles=%d, %dx%d)" % (n, nv, nt, width, height))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device="cuda")
-    out = torch.empty((n, int(height), int(width)), dtype=torch.float32, device="cuda")
-    check(lib.pp_render_depth_f32(ctx.handle, n, nv, _ptr(args[0]), nt, _ptr(args[1]), _ptr(args[2]), _ptr(args[3]), _ptr(args[4]),
-                                  int(width), int(height), float(clip_near), float(clip_far), _ptr(ws), nbytes, _ptr(out)),
-          ctx.handle, "pp_render_depth_f32")
+    ws = _workspace(nbytes, "render_depth: unsupported shape (n=%d, vertices=%d, triangles=%d, %dx%d)" % (n, nv, nt, width, height))
+    out = _out(verts, (n, int(height), int(width)), _F32)
+    check(lib.pp_render_depth_f32(ctx.handle, n, nv, _ptr(verts), nt, _ptr(faces), _ptr(R), _ptr(t), _ptr(K4), int(width), int(height),
+                                  float(clip_near), float(clip_far), _ptr(ws), nbytes, _ptr(out)), ctx.handle, "pp_render_depth_f32")
     return out
 
 
@@ -741,22 +793,15 @@ def vsd(ctx, depth_test, depth_est, depth_gt, K4, delta, tau, cost_type="step"):
     (shared by all problems) or [n,h,w], K4 float64 [n,4] -> (e float64 [n], intersection int64 [n], union int64 [n])."""
     if cost_type not in VSD_COSTS:
         raise ValueError("vsd: unknown pixel matching cost %r (step | tlinear)" % (cost_type,))
-    n, h, w = (int(s) for s in depth_est.shape)
-    assert depth_gt.shape == depth_est.shape and K4.shape == (n, 4) and K4.dtype == torch.float64
-    for d in (depth_test, depth_est, depth_gt):
-        assert d.dtype == torch.float32 and d.is_cuda
-    if tuple(depth_test.shape) == (h, w):
-        stride = 0
-    elif tuple(depth_test.shape) == (n, h, w):
-        stride = h * w
-    else:
-        raise ValueError("vsd: depth_test must be [h,w] or [n,h,w], got %s" % (tuple(depth_test.shape),))
-    dt, de, dg, K4 = depth_test.contiguous(), depth_est.contiguous(), depth_gt.contiguous(), K4.contiguous()
-    ws = torch.empty((max(1, lib.pp_vsd_workspace_bytes(n, w, h)),), dtype=torch.uint8, device="cuda")
-    e = torch.empty((n,), dtype=torch.float64, device="cuda")
-    inter = torch.empty((n,), dtype=torch.int64, device="cuda")
-    uni = torch.empty((n,), dtype=torch.int64, device="cuda")
-    check(lib.pp_vsd_f64(ctx.handle, n, w, h, _ptr(dt), stride, _ptr(de), _ptr(dg), _ptr(K4), float(delta), float(tau),
+    de = _arg("vsd", "depth_est", depth_est, _F32, (None, None, None))
+    n, h, w = (int(s) for s in de.shape)
+    dg = _arg("vsd", "depth_gt", depth_gt, _F32, (n, h, w))
+    shared = torch.is_tensor(depth_test) and depth_test.dim() == 2  # one scene [h,w] for all problems, else [n,h,w]
+    dt = _arg("vsd", "depth_test", depth_test, _F32, (h, w) if shared else (n, h, w))
+    K4 = _arg("vsd", "K4", K4, _F64, (n, 4))
+    ws = _workspace(lib.pp_vsd_workspace_bytes(n, w, h))
+    e, inter, uni = _out(de, (n,)), _out(de, (n,), torch.int64), _out(de, (n,), torch.int64)
+    check(lib.pp_vsd_f64(ctx.handle, n, w, h, _ptr(dt), 0 if shared else h * w, _ptr(de), _ptr(dg), _ptr(K4), float(delta), float(tau),
                          VSD_COSTS[cost_type], _ptr(ws), _ptr(e), _ptr(inter), _ptr(uni)), ctx.handle, "pp_vsd_f64")
     return e, inter, uni
 
@@ -769,21 +814,15 @@ def cloud_from_depth(ctx, depth, fx, fy, cx, cy, ds=1.0, mask=None, row_idx=None
     """Back-projection of a depth image (pp_cloud_from_depth_f64): cuda float32 depth [h,w]; mask cuda uint8 [mh,mw] with cuda
     int32 row_idx [h] / col_idx [w] into it (None = every pixel).  dense: float64 [h*w,3] with all-NaN rows where z == 0;
     otherwise the valid masked pixels compacted in row-major order -> (float64 [n,3], row offsets int32 [h+1])."""
+    depth = _arg("cloud_from_depth", "depth", depth, _F32, (None, None))
     h, w = (int(s) for s in depth.shape)
-    if depth.dtype != torch.float32 or not depth.is_cuda:
-        raise ValueError("cloud_from_depth: depth must be a cuda float32 [h,w] tensor")
-    depth = depth.contiguous()
-    mh = mw = 0
-    if mask is not None:
-        if mask.dtype != torch.uint8 or mask.dim() != 2 or row_idx is None or col_idx is None:
-            raise ValueError("cloud_from_depth: the mask must be uint8 [mh,mw] with row and column index maps")
-        mh, mw = (int(s) for s in mask.shape)
-        if tuple(row_idx.shape) != (h,) or tuple(col_idx.shape) != (w,) or row_idx.dtype != torch.int32 or col_idx.dtype != torch.int32:
-            raise ValueError("cloud_from_depth: row_idx / col_idx must be int32 [h] / [w]")
-        mask, row_idx, col_idx = mask.contiguous(), row_idx.contiguous(), col_idx.contiguous()
-    pts = torch.empty((h * w, 3), dtype=torch.float64, device=depth.device)
-    offs = torch.empty((h + 1,), dtype=torch.int32, device=depth.device)
-    ws = torch.empty((max(1, lib.pp_cloud_from_depth_workspace_bytes(h, w)),), dtype=torch.uint8, device=depth.device)
+    mask = _arg("cloud_from_depth", "mask", mask, _U8, (None, None), optional=True)
+    mh, mw = (int(s) for s in mask.shape) if mask is not None else (0, 0)
+    # a mask needs both index maps; without one they are not read
+    row_idx = _arg("cloud_from_depth", "row_idx", row_idx, _I32, (h,)) if mask is not None else None
+    col_idx = _arg("cloud_from_depth", "col_idx", col_idx, _I32, (w,)) if mask is not None else None
+    pts, offs = _out(depth, (h * w, 3)), _out(depth, (h + 1,), _I32)
+    ws = _workspace(lib.pp_cloud_from_depth_workspace_bytes(h, w))
     check(lib.pp_cloud_from_depth_f64(ctx.handle, h, w, _ptr(depth), _ptr(mask), mh, mw, _ptr(row_idx), _ptr(col_idx), float(fx), float(fy),
                                       float(cx), float(cy), float(ds), int(bool(dense)), _ptr(ws), _ptr(pts), _ptr(offs)),
           ctx.handle, "pp_cloud_from_depth_f64")
@@ -793,28 +832,31 @@ def cloud_from_depth(ctx, depth, fx, fy, cx, cy, ds=1.0, mask=None, row_idx=None
     return pts[:n], offs
 
 
+def _cloud(what, pts):
+    """a non-empty cuda float64 point cloud [n,3] -> (pts.contiguous(), n)"""
+    pts = _arg(what, "pts", pts, _F64, (None, 3))
+    if pts.shape[0] < 1:
+        raise ValueError("%s: pts must not be empty" % what)
+    return pts, int(pts.shape[0])
+
+
 def voxel_down_sample(ctx, pts, voxel, normals=None):
     """Open3D voxel_down_sample (pp_voxel_keys_f64, a stable torch sort, pp_voxel_means_f64): cuda float64 pts [n,3] (and
     normals [n,3]) -> (means [m,3], renormalised mean normals [m,3] or None), ascending voxel key order."""
-    n = int(pts.shape[0])
-    if pts.dtype != torch.float64 or pts.dim() != 2 or pts.shape[1] != 3 or n < 1:
-        raise ValueError("voxel_down_sample: points must be a non-empty cuda float64 [n,3] tensor")
-    if normals is not None and (normals.dtype != torch.float64 or tuple(normals.shape) != (n, 3)):
-        raise ValueError("voxel_down_sample: normals must be float64 [n,3] like the points")
-    pts = pts.contiguous()
-    normals = normals.contiguous() if normals is not None else None
-    keys = torch.empty((n,), dtype=torch.int64, device=pts.device)
-    ws = torch.empty((max(1, lib.pp_voxel_workspace_bytes(n)),), dtype=torch.uint8, device=pts.device)
+    pts, n = _cloud("voxel_down_sample", pts)
+    normals = _arg("voxel_down_sample", "normals", normals, _F64, (n, 3), optional=True)
+    keys = _out(pts, (n,), torch.int64)
+    ws = _workspace(lib.pp_voxel_workspace_bytes(n))
     check(lib.pp_voxel_keys_f64(ctx.handle, n, _ptr(pts), float(voxel), _ptr(ws), _ptr(keys)), ctx.handle, "pp_voxel_keys_f64")
     sk, perm = torch.sort(keys, stable=True)
     if bool((sk[:1] < 0).any()):
         raise ValueError("voxel_down_sample: non-finite points, or more than 2^21 voxels along an axis")
     _, counts = torch.unique_consecutive(sk, return_counts=True)
     m = int(counts.numel())
-    seg = torch.zeros((m + 1,), dtype=torch.int64, device=pts.device)
+    seg = _out(pts, (m + 1,), torch.int64, 0)
     seg[1:] = torch.cumsum(counts, 0)
-    out = torch.empty((m, 3), dtype=torch.float64, device=pts.device)
-    out_n = torch.empty((m, 3), dtype=torch.float64, device=pts.device) if normals is not None else None
+    out = _out(pts, (m, 3))
+    out_n = _out(pts, (m, 3)) if normals is not None else None
     check(lib.pp_voxel_means_f64(ctx.handle, n, _ptr(pts), _ptr(normals), _ptr(perm.contiguous()), m, _ptr(seg), _ptr(out), _ptr(out_n)),
           ctx.handle, "pp_voxel_means_f64")
     return out, out_n
@@ -823,12 +865,9 @@ def voxel_down_sample(ctx, pts, voxel, normals=None):
 def estimate_normals(ctx, pts, radius, max_nn, return_neighbors=False):
     """Open3D estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)) (pp_estimate_normals_f64): cuda float64 pts [n,3]
     -> normals [n,3] toward the camera, zero with fewer than 3 neighbours (and the neighbour lists int32 [n,max_nn])."""
-    n = int(pts.shape[0])
-    if pts.dtype != torch.float64 or pts.dim() != 2 or pts.shape[1] != 3 or n < 1:
-        raise ValueError("estimate_normals: points must be a non-empty cuda float64 [n,3] tensor")
-    pts = pts.contiguous()
-    out = torch.empty((n, 3), dtype=torch.float64, device=pts.device)
-    nbr = torch.empty((n, int(max_nn)), dtype=torch.int32, device=pts.device) if return_neighbors and int(max_nn) > 0 else None
+    pts, n = _cloud("estimate_normals", pts)
+    out = _out(pts, (n, 3))
+    nbr = _out(pts, (n, int(max_nn)), _I32) if return_neighbors and int(max_nn) > 0 else None
     check(lib.pp_estimate_normals_f64(ctx.handle, n, _ptr(pts), float(radius), int(max_nn), None, _ptr(out), _ptr(nbr)), ctx.handle,
           "pp_estimate_normals_f64")
     return (out, nbr) if return_neighbors else out
@@ -841,36 +880,22 @@ def icp(ctx, src_offsets, tgt_offsets, src, tgt, init, max_correspondence_distan
     -> (R [P,3,3], t [P,3], fitness [P], inlier_rmse [P], iterations int32 [P], status int32 [P], corr int32 [Ns])."""
     if mode not in ICP_MODES:
         raise ValueError("icp: unknown estimation %r (point_to_point | point_to_plane)" % (mode,))
-    P = int(src_offsets.numel()) - 1
+    src, tgt = _arg("icp", "src", src, _F64, (None, 3)), _arg("icp", "tgt", tgt, _F64, (None, 3))
     Ns, Nt = int(src.shape[0]), int(tgt.shape[0])
-    for name, a in (("src", src), ("tgt", tgt), ("init", init)) + ((("tgt_normals", tgt_normals),) if tgt_normals is not None else ()):
-        if a.dtype != torch.float64 or not a.is_cuda:
-            raise ValueError("icp: %s must be a cuda float64 tensor" % name)
-    if src.shape != (Ns, 3) or tgt.shape != (Nt, 3) or tuple(init.shape) != (P, 4, 4) or P < 1:
-        raise ValueError("icp: need src [Ns,3], tgt [Nt,3], init [P,4,4] with P >= 1")
-    if tgt_offsets.numel() != P + 1 or src_offsets.dtype != torch.int32 or tgt_offsets.dtype != torch.int32:
-        raise ValueError("icp: offsets must be int32 [P+1]")
-    if mode == "point_to_plane" and (tgt_normals is None or tgt_normals.shape != (Nt, 3)):
-        raise ValueError("icp: point_to_plane needs target normals [Nt,3]")
-    so, to = src_offsets.cpu().numpy(), tgt_offsets.cpu().numpy()
-    if so[0] != 0 or to[0] != 0 or so[-1] != Ns or to[-1] != Nt or (np.diff(so) < 0).any() or (np.diff(to) < 0).any():
-        raise ValueError("icp: offsets must rise from 0 to the number of source / target points")
+    src_offsets, so = _check_offsets("icp", src_offsets, Ns, True, name="src_offsets")
+    tgt_offsets, to = _check_offsets("icp", tgt_offsets, Nt, True, name="tgt_offsets")
+    P = len(so) - 1
+    if P < 1 or len(to) != P + 1:
+        raise ValueError("icp: src_offsets and tgt_offsets must be [P+1] of one P >= 1")
+    init = _arg("icp", "init", init, _F64, (P, 4, 4))
+    tgt_normals = _arg("icp", "tgt_normals", tgt_normals, _F64, (Nt, 3), optional=mode != "point_to_plane")
     max_source_points = max(int(np.diff(so).max()), 1)
-    dev = src.device
-    args = [a.contiguous() if a is not None else None for a in (src_offsets, tgt_offsets, src, tgt, tgt_normals, init)]
     nbytes = lib.pp_icp_workspace_bytes(P, max_source_points)
-    if nbytes == 0:
-        raise ValueError("icp: unsupported shape (%d problems)" % P)
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    R = torch.empty((P, 3, 3), dtype=torch.float64, device=dev)
-    t = torch.empty((P, 3), dtype=torch.float64, device=dev)
-    fit = torch.empty((P,), dtype=torch.float64, device=dev)
-    rmse = torch.empty((P,), dtype=torch.float64, device=dev)
-    iters = torch.empty((P,), dtype=torch.int32, device=dev)
-    status = torch.empty((P,), dtype=torch.int32, device=dev)
-    corr = torch.full((max(Ns, 1),), -1, dtype=torch.int32, device=dev)
-    check(lib.pp_icp_f64(ctx.handle, P, _ptr(args[0]), _ptr(args[1]), max_source_points, _ptr(args[2]), _ptr(args[3]), _ptr(args[4]),
-                         _ptr(args[5]), float(max_correspondence_distance), int(max_iteration), float(relative_fitness), float(relative_rmse),
+    ws = _workspace(nbytes, "icp: unsupported shape (%d problems)" % P)
+    R, t, fit, rmse = _out(src, (P, 3, 3)), _out(src, (P, 3)), _out(src, (P,)), _out(src, (P,))
+    iters, status, corr = _out(src, (P,), _I32), _out(src, (P,), _I32), _out(src, (max(Ns, 1),), _I32, -1)
+    check(lib.pp_icp_f64(ctx.handle, P, _ptr(src_offsets), _ptr(tgt_offsets), max_source_points, _ptr(src), _ptr(tgt), _ptr(tgt_normals),
+                         _ptr(init), float(max_correspondence_distance), int(max_iteration), float(relative_fitness), float(relative_rmse),
                          ICP_MODES[mode], _ptr(ws), nbytes, _ptr(R), _ptr(t), _ptr(fit), _ptr(rmse), _ptr(iters), _ptr(status), _ptr(corr)),
           ctx.handle, "pp_icp_f64")
     return R, t, fit, rmse, iters, status, corr[:Ns]
@@ -878,16 +903,6 @@ def icp(ctx, src_offsets, tgt_offsets, src, tgt, init, max_correspondence_distan
 
 WPNP_MODES = {"full": 0, "iso": 1}
 WPNP_CONVERGED, WPNP_MAX_ITER, WPNP_TOO_FEW, WPNP_SINGULAR, WPNP_BEHIND = 0, 1, 2, 3, 4
-
-
-def _check_offsets(what, offsets, n_total, check, multiple=1):
-    if offsets.dtype != torch.int32 or not offsets.is_cuda or offsets.dim() != 1 or offsets.numel() < 1:
-        raise ValueError("%s: offsets must be a cuda int32 tensor [P+1]" % what)
-    if check:
-        o = offsets.cpu().numpy()
-        if o[0] != 0 or o[-1] != n_total or (np.diff(o) < 0).any() or (o % multiple != 0).any():
-            raise ValueError("%s: offsets must rise from 0 to the number of points%s" %
-                             (what, " in multiples of points_per_vote" if multiple > 1 else ""))
 
 
 def vote_stats(ctx, offsets, img, points_per_vote=8, vote_weight=None, inlier_mask=None, mode="full", sigma_floor=0.5,
@@ -900,27 +915,19 @@ def vote_stats(ctx, offsets, img, points_per_vote=8, vote_weight=None, inlier_ma
     if mode not in WPNP_MODES:
         raise ValueError("vote_stats: unknown mode %r (full | iso)" % (mode,))
     ppv = int(points_per_vote)
-    if not torch.is_tensor(img) or img.dtype != torch.float64 or not img.is_cuda or img.dim() != 2 or img.shape[1] != 2:
-        raise ValueError("vote_stats: img must be a cuda float64 tensor [N,2]")
+    img = _arg("vote_stats", "img", img, _F64, (None, 2))
     N = int(img.shape[0])
     if ppv < 1 or ppv > 64 or N % ppv != 0:
         raise ValueError("vote_stats: points_per_vote must be 1..64 and divide the number of points")
-    if vote_weight is not None and (vote_weight.dtype != torch.float64 or not vote_weight.is_cuda or tuple(vote_weight.shape) != (N // ppv,)):
-        raise ValueError("vote_stats: vote_weight must be a cuda float64 tensor [N / points_per_vote]")
-    if inlier_mask is not None and (inlier_mask.dtype != torch.uint8 or not inlier_mask.is_cuda or tuple(inlier_mask.shape) != (N,)):
-        raise ValueError("vote_stats: inlier_mask must be a cuda uint8 tensor [N]")
+    vw = _arg("vote_stats", "vote_weight", vote_weight, _F64, (N // ppv,), optional=True)
+    mk = _arg("vote_stats", "inlier_mask", inlier_mask, _U8, (N,), optional=True)
     if not (0.0 <= float(sigma_floor) < 1e150):
         raise ValueError("vote_stats: sigma_floor must be finite and >= 0")
-    _check_offsets("vote_stats", offsets, N, check_offsets, ppv)
+    offsets, _ = _check_offsets("vote_stats", offsets, N, check_offsets, ppv)
     P = int(offsets.numel()) - 1
-    dev = img.device
-    img, offsets = img.contiguous(), offsets.contiguous()
-    vw = vote_weight.contiguous() if vote_weight is not None else None
-    mk = inlier_mask.contiguous() if inlier_mask is not None else None
-    ws = torch.empty((max(1, lib.pp_vote_stats_workspace_bytes(P, ppv)),), dtype=torch.uint8, device=dev)
-    f = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
-    out = dict(wsum=f(P, ppv), count=torch.zeros((P, ppv), dtype=torch.int32, device=dev), mu=f(P, ppv, 2), cov=f(P, ppv, 3),
-               n_eff=f(P, ppv), wgt=f(P, ppv, 3))
+    ws = _workspace(lib.pp_vote_stats_workspace_bytes(P, ppv))
+    z = lambda *shape, dtype=_F64: _out(img, shape, dtype, 0)
+    out = dict(wsum=z(P, ppv), count=z(P, ppv, dtype=_I32), mu=z(P, ppv, 2), cov=z(P, ppv, 3), n_eff=z(P, ppv), wgt=z(P, ppv, 3))
     check(lib.pp_vote_stats_f64(ctx.handle, P, _ptr(offsets), N, _ptr(img), ppv, _ptr(vw), _ptr(mk), WPNP_MODES[mode], float(sigma_floor),
                                 _ptr(ws), _ptr(out["wsum"]), _ptr(out["count"]), _ptr(out["mu"]), _ptr(out["cov"]), _ptr(out["n_eff"]),
                                 _ptr(out["wgt"])), ctx.handle, "pp_vote_stats_f64")
@@ -933,32 +940,24 @@ def pnp_refine_weighted(ctx, offsets, obj, img, wgt, K4, R_init, t_init, max_ite
     obj float64 [N,3], img [N,2], wgt [N,3] = (wxx, wxy, wyy), K4 [P,4], R_init [P,3,3], t_init [P,3].
     -> dict(R [P,3,3], t [P,3], rvec [P,3], cost_init [P], cost_final [P], iterations int32 [P], status int32 [P],
     pose_cov [P,6,6] or None).  Tolerances default to Ceres' (parity with Ceres unpinned: same cost, own minimiser)."""
-    shapes = (("obj", obj, 3), ("img", img, 2), ("wgt", wgt, 3))
-    for name, a, _ in shapes + (("K4", K4, 4), ("R_init", R_init, 3), ("t_init", t_init, 3)):
-        if not torch.is_tensor(a) or a.dtype != torch.float64 or not a.is_cuda:
-            raise ValueError("pnp_refine_weighted: %s must be a cuda float64 tensor" % name)
-    N = int(obj.shape[0]) if obj.dim() == 2 else -1
-    for name, a, w in shapes:
-        if a.dim() != 2 or tuple(a.shape) != (N, w):
-            raise ValueError("pnp_refine_weighted: need obj [N,3], img [N,2], wgt [N,3]")
-    _check_offsets("pnp_refine_weighted", offsets, N, check_offsets)
+    what = "pnp_refine_weighted"
+    obj = _arg(what, "obj", obj, _F64, (None, 3))
+    N = int(obj.shape[0])
+    img, wgt = _arg(what, "img", img, _F64, (N, 2)), _arg(what, "wgt", wgt, _F64, (N, 3))
+    offsets, _ = _check_offsets(what, offsets, N, check_offsets)
     P = int(offsets.numel()) - 1
-    if tuple(K4.shape) != (P, 4) or tuple(R_init.shape) != (P, 3, 3) or tuple(t_init.shape) != (P, 3):
-        raise ValueError("pnp_refine_weighted: need K4 [P,4], R_init [P,3,3], t_init [P,3]")
+    K4, R_init, t_init = _arg(what, "K4", K4, _F64, (P, 4)), _arg(what, "R_init", R_init, _F64, (P, 3, 3)), _arg(what, "t_init", t_init, _F64, (P, 3))
     if int(max_iterations) < 0 or not all(float(v) >= 0.0 for v in (gradient_tol, parameter_tol, function_tol)):
         raise ValueError("pnp_refine_weighted: max_iterations and the tolerances must be >= 0")
-    dev = obj.device
-    args = [a.contiguous() for a in (offsets, obj, img, wgt, K4, R_init, t_init)]
-    ws = torch.empty((max(1, lib.pp_pnp_refine_weighted_workspace_bytes(P, N)),), dtype=torch.uint8, device=dev)
-    f = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
-    out = dict(R=f(P, 3, 3), t=f(P, 3), rvec=f(P, 3), cost_init=f(P), cost_final=f(P),
-               iterations=torch.zeros((P,), dtype=torch.int32, device=dev), status=torch.zeros((P,), dtype=torch.int32, device=dev),
-               pose_cov=f(P, 6, 6) if pose_cov else None)
-    check(lib.pp_pnp_refine_weighted_f64(ctx.handle, P, _ptr(args[0]), N, _ptr(args[1]), _ptr(args[2]), _ptr(args[3]), _ptr(args[4]),
-                                         _ptr(args[5]), _ptr(args[6]), int(max_iterations), float(gradient_tol), float(parameter_tol),
-                                         float(function_tol), _ptr(ws), _ptr(out["R"]), _ptr(out["t"]), _ptr(out["rvec"]),
-                                         _ptr(out["cost_init"]), _ptr(out["cost_final"]), _ptr(out["iterations"]), _ptr(out["status"]),
-                                         _ptr(out["pose_cov"])), ctx.handle, "pp_pnp_refine_weighted_f64")
+    ws = _workspace(lib.pp_pnp_refine_weighted_workspace_bytes(P, N))
+    z = lambda *shape, dtype=_F64: _out(obj, shape, dtype, 0)
+    out = dict(R=z(P, 3, 3), t=z(P, 3), rvec=z(P, 3), cost_init=z(P), cost_final=z(P), iterations=z(P, dtype=_I32), status=z(P, dtype=_I32),
+               pose_cov=z(P, 6, 6) if pose_cov else None)
+    check(lib.pp_pnp_refine_weighted_f64(ctx.handle, P, _ptr(offsets), N, _ptr(obj), _ptr(img), _ptr(wgt), _ptr(K4), _ptr(R_init), _ptr(t_init),
+                                         int(max_iterations), float(gradient_tol), float(parameter_tol), float(function_tol), _ptr(ws),
+                                         _ptr(out["R"]), _ptr(out["t"]), _ptr(out["rvec"]), _ptr(out["cost_init"]), _ptr(out["cost_final"]),
+                                         _ptr(out["iterations"]), _ptr(out["status"]), _ptr(out["pose_cov"])), ctx.handle,
+          "pp_pnp_refine_weighted_f64")
     return out
 
 
@@ -971,24 +970,19 @@ def vote_cluster(ctx, boxes3D, scores, idx, cnt, iou=0.5, min_votes=10, max_inst
     -> (inst int32 [B,C,cap] instance per input vote or -1, order int32 [B,C,cap] anchor indices instance-major (-1 padded),
     inst_offsets int32 [B,C,max_instances+1] into order, n_inst int32 [B,C], leader int32 [B,C,max_instances] anchor or -1,
     inst_box float32 [B,C,max_instances,4] the leader's (x1, y1, x2, y2))."""
-    for name, a, dt, nd in (("boxes3D", boxes3D, torch.float32, 3), ("scores", scores, torch.float32, 3), ("idx", idx, torch.int32, 3),
-                            ("cnt", cnt, torch.int32, 2)):
-        if not torch.is_tensor(a) or a.dtype != dt or not a.is_cuda or a.dim() != nd:
-            raise ValueError("vote_cluster: %s must be a cuda %s tensor with %d dimensions" % (name, str(dt).split(".")[-1], nd))
-    B, N, Cc = scores.shape
+    scores = _arg("vote_cluster", "scores", scores, _F32, (None, None, None))
+    B, N, Cc = (int(s) for s in scores.shape)
+    boxes3D = _arg("vote_cluster", "boxes3D", boxes3D, _F32, (B, N, 16))
+    idx = _arg("vote_cluster", "idx", idx, _I32, (B, Cc, None))
     cap = int(idx.shape[2])
-    if tuple(boxes3D.shape) != (B, N, 16) or tuple(idx.shape) != (B, Cc, cap) or tuple(cnt.shape) != (B, Cc):
-        raise ValueError("vote_cluster: need boxes3D [B,N,16], scores [B,N,C], idx [B,C,cap], cnt [B,C]")
+    cnt = _arg("vote_cluster", "cnt", cnt, _I32, (B, Cc))
     mi = int(max_instances)
     mr = 4 * mi if max_rounds is None else int(max_rounds)
-    boxes3D, scores, idx, cnt = boxes3D.contiguous(), scores.contiguous(), idx.contiguous(), cnt.contiguous()
-    dev = scores.device
-    e = lambda shape, dt=torch.int32: torch.empty(shape, dtype=dt, device=dev)
-    inst, order = e((B, Cc, cap)), e((B, Cc, cap))
-    offs, n_inst, leader = e((B, Cc, max(mi, 0) + 1)), e((B, Cc)), e((B, Cc, max(mi, 1)))
-    box = e((B, Cc, max(mi, 1), 4), torch.float32)
+    inst, order = _out(scores, (B, Cc, cap), _I32), _out(scores, (B, Cc, cap), _I32)
+    offs, n_inst, leader = _out(scores, (B, Cc, max(mi, 0) + 1), _I32), _out(scores, (B, Cc), _I32), _out(scores, (B, Cc, max(mi, 1)), _I32)
+    box = _out(scores, (B, Cc, max(mi, 1), 4), _F32)
     nb = lib.pp_vote_cluster_workspace_bytes(B, Cc, cap, mi)
-    ws = torch.empty((nb,), dtype=torch.uint8, device=dev) if nb else None
+    ws = _workspace(nb) if nb else None  # this entry point takes no workspace when it asks for none
     check(lib.pp_vote_cluster(ctx.handle, B, N, Cc, cap, _ptr(boxes3D), _ptr(scores), _ptr(idx), _ptr(cnt), float(iou), int(min_votes), mi, mr,
                               _ptr(ws), _ptr(inst), _ptr(order), _ptr(offs), _ptr(n_inst), _ptr(leader), _ptr(box)), ctx.handle,
           "pp_vote_cluster")

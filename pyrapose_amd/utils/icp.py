@@ -28,6 +28,7 @@ import torch
 
 from .. import ops
 from ..runtime import default_context
+from ._host import k4, pack_ragged, to_device
 from .anchors import guess_shapes
 
 
@@ -48,24 +49,11 @@ class RegistrationResult(object):
             self.fitness, self.inlier_rmse, self.iterations, self.status)
 
 
-def _dev(a, dtype=torch.float64):
-    if torch.is_tensor(a):
-        return a.to(device="cuda", dtype=dtype).contiguous()
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64 if dtype == torch.float64 else None)).to("cuda", dtype).contiguous()
-
-
 def _points(a, what):
     p = a if torch.is_tensor(a) else np.asarray(a, np.float64)
     if p.ndim != 2 or p.shape[1] != 3:
         raise ValueError("%s must be [n,3], got %s" % (what, tuple(p.shape)))
     return p
-
-
-def _K4(K):
-    K = np.asarray(K, np.float64)
-    if K.shape != (3, 3):
-        raise ValueError("K must be 3x3, got %s" % (K.shape,))
-    return K[0, 0], K[1, 1], K[0, 2], K[1, 2]
 
 
 def create_point_cloud(depth, fx, fy, cx, cy, ds):
@@ -74,8 +62,7 @@ def create_point_cloud(depth, fx, fy, cx, cy, ds):
     d = np.asarray(depth)
     if d.ndim != 2:
         raise ValueError("create_point_cloud: depth must be [rows, cols]")
-    dt = _dev(d.astype(np.float32), torch.float32)
-    return ops.cloud_from_depth(default_context(), dt, fx, fy, cx, cy, ds, dense=True).cpu().numpy()
+    return ops.cloud_from_depth(default_context(), to_device(d, torch.float32), fx, fy, cx, cy, ds, dense=True).cpu().numpy()
 
 
 def _mask_grid(mask, shape):
@@ -97,12 +84,12 @@ def cloud_from_depth(depth, K, mask=None, ds=1.0, ctx=None):
     d = depth if torch.is_tensor(depth) else np.asarray(depth)
     if d.ndim != 2:
         raise ValueError("cloud_from_depth: depth must be [h,w]")
-    fx, fy, cx, cy = _K4(K)
-    dt = d.to("cuda", torch.float32).contiguous() if torch.is_tensor(d) else _dev(d.astype(np.float32), torch.float32)
+    fx, fy, cx, cy = k4(K)
+    dt = to_device(d, torch.float32)
     if mask is None:
         return ops.cloud_from_depth(ctx, dt, fx, fy, cx, cy, ds)[0]
     g, rows, cols = _mask_grid(mask, tuple(d.shape))
-    return ops.cloud_from_depth(ctx, dt, fx, fy, cx, cy, ds, _dev(g, torch.uint8), _dev(rows, torch.int32), _dev(cols, torch.int32))[0]
+    return ops.cloud_from_depth(ctx, dt, fx, fy, cx, cy, ds, to_device(g, torch.uint8), to_device(rows, torch.int32), to_device(cols, torch.int32))[0]
 
 
 def voxel_down_sample(points, voxel_size, normals=None, ctx=None):
@@ -110,8 +97,8 @@ def voxel_down_sample(points, voxel_size, normals=None, ctx=None):
     order.  Returns cuda float64 [m,3], or ([m,3], [m,3]) with normals."""
     if not voxel_size > 0:
         raise ValueError("voxel_down_sample: voxel_size must be positive")
-    p = _dev(_points(points, "points"))
-    n = _dev(_points(normals, "normals")) if normals is not None else None
+    p = to_device(_points(points, "points"))
+    n = to_device(_points(normals, "normals")) if normals is not None else None
     out, out_n = ops.voxel_down_sample(ctx or default_context(), p, float(voxel_size), n)
     return (out, out_n) if normals is not None else out
 
@@ -119,7 +106,7 @@ def voxel_down_sample(points, voxel_size, normals=None, ctx=None):
 def estimate_normals(points, radius, max_nn, ctx=None):
     """Open3D estimate_normals(KDTreeSearchParamHybrid(radius, max_nn)): cuda float64 [n,3], toward the camera at the origin,
     zero for points with fewer than 3 neighbours."""
-    return ops.estimate_normals(ctx or default_context(), _dev(_points(points, "points")), float(radius), int(max_nn))
+    return ops.estimate_normals(ctx or default_context(), to_device(_points(points, "points")), float(radius), int(max_nn))
 
 
 def registration_icp_batch(problems, max_correspondence_distance, estimation="point_to_plane", max_iteration=30,
@@ -136,8 +123,8 @@ def registration_icp_batch(problems, max_correspondence_distance, estimation="po
         T = np.asarray(pr.get("init", np.eye(4)), np.float64)
         if T.shape != (4, 4):
             raise ValueError("registration_icp: init must be 4x4")
-        src.append(_dev(s))
-        tgt.append(_dev(t))
+        src.append(to_device(s))
+        tgt.append(to_device(t))
         init.append(T)
         if estimation == "point_to_plane":
             if pr.get("target_normals") is None:
@@ -145,11 +132,10 @@ def registration_icp_batch(problems, max_correspondence_distance, estimation="po
             nn = _points(pr["target_normals"], "target_normals")
             if nn.shape[0] != t.shape[0]:
                 raise ValueError("registration_icp: target_normals must match the target points")
-            nrm.append(_dev(nn))
-    so = np.concatenate([[0], np.cumsum([s.shape[0] for s in src])]).astype(np.int32)
-    to = np.concatenate([[0], np.cumsum([t.shape[0] for t in tgt])]).astype(np.int32)
+            nrm.append(to_device(nn))
+    (so, src), (to, tgt) = pack_ragged(src), pack_ragged(tgt)
     R, t, fit, rmse, iters, status, corr = ops.icp(
-        ctx or default_context(), _dev(so, torch.int32), _dev(to, torch.int32), torch.cat(src), torch.cat(tgt), _dev(np.stack(init)),
+        ctx or default_context(), to_device(so, torch.int32), to_device(to, torch.int32), src, tgt, to_device(np.stack(init)),
         float(max_correspondence_distance), int(max_iteration), float(relative_fitness), float(relative_rmse), estimation,
         torch.cat(nrm) if nrm else None)
     R, t, fit, rmse = R.cpu().numpy(), t.cpu().numpy(), fit.cpu().numpy(), rmse.cpu().numpy()
@@ -207,9 +193,9 @@ def model_cloud(model, voxel_size, scale=1000.0, ctx=None):
     faces = model.get("faces") if isinstance(model, dict) else None
     if faces is not None and len(faces):
         S, N = _mesh_samples(pts, np.asarray(faces, np.int64), 0.5 * voxel_size)
-        p, n = ops.voxel_down_sample(ctx, _dev(S), float(voxel_size), _dev(N))
+        p, n = ops.voxel_down_sample(ctx, to_device(S), float(voxel_size), to_device(N))
         return p, n
-    p = ops.voxel_down_sample(ctx, _dev(pts), float(voxel_size))[0]
+    p = ops.voxel_down_sample(ctx, to_device(pts), float(voxel_size))[0]
     n = ops.estimate_normals(ctx, p, 2.0 * voxel_size, 30)
     out = p - p.mean(0, keepdim=True)
     n = torch.where(((n * out).sum(1, keepdim=True) < 0), -n, n)
@@ -236,7 +222,7 @@ def refine_poses(dets, depth, mask_scores, K, models, mask_threshold=0.5, min_ma
     if d.ndim != 2:
         raise ValueError("refine_poses: depth must be [h,w]")
     h, w = d.shape
-    fx, fy, cx, cy = _K4(K)
+    fx, fy, cx, cy = k4(K)
     ms = np.asarray(mask_scores.cpu() if torch.is_tensor(mask_scores) else mask_scores, np.float32)
     if ms.ndim == 3 and ms.shape[0] == 1:
         ms = ms[0]
@@ -267,8 +253,8 @@ def refine_poses(dets, depth, mask_scores, K, models, mask_threshold=0.5, min_ma
             raise ValueError("refine_poses: model %d is larger than 10 m at depth_scale %g: model points must be in metres" % (m, depth_scale))
     rows, cols = ops.pil_nearest_index(mh, h), ops.pil_nearest_index(mw, w)
     rcount, ccount = np.bincount(rows, minlength=mh), np.bincount(cols, minlength=mw)
-    dt = _dev(d.astype(np.float32), torch.float32)
-    rows_d, cols_d = _dev(rows, torch.int32), _dev(cols, torch.int32)
+    dt = to_device(d, torch.float32)
+    rows_d, cols_d = to_device(rows, torch.int32), to_device(cols, torch.int32)
     cache = {}
     problems, owners = [], []
     out = [dict(det, refined=False, fitness=0.0, inlier_rmse=0.0, iterations=0) for det in dets]
@@ -284,15 +270,15 @@ def refine_poses(dets, depth, mask_scores, K, models, mask_threshold=0.5, min_ma
             grid = grid & row_hit[:, None] & col_hit[None, :]
         if float(rcount @ grid.astype(np.float64) @ ccount) <= min_mask_pixels:
             continue
-        scene, _ = ops.cloud_from_depth(ctx, dt, fx, fy, cx, cy, 1.0, _dev(grid.astype(np.uint8), torch.uint8), rows_d, cols_d)
+        scene, _ = ops.cloud_from_depth(ctx, dt, fx, fy, cx, cy, 1.0, to_device(grid, torch.uint8), rows_d, cols_d)
         if scene.shape[0] < 3:
             continue
         scene = ops.voxel_down_sample(ctx, scene, float(voxel_size))[0]
         if cls not in cache:
             cache[cls] = model_cloud(models[cls], voxel_size, depth_scale, ctx)
         mp, mn = cache[cls]
-        R = _dev(np.asarray(det["R"], np.float64))
-        t = _dev(np.asarray(det["t"], np.float64).reshape(3) * depth_scale)
+        R = to_device(det["R"])
+        t = to_device(np.asarray(det["t"], np.float64).reshape(3) * depth_scale)
         front = (mn @ R.T)[:, 2] < 0                                       # model points facing the camera (:686-693)
         src = mp[front]
         if src.shape[0] < 6:

@@ -9,6 +9,7 @@ import torch
 
 from .. import ops
 from ..runtime import default_context
+from ._host import k4, pack_ragged, to_device
 
 
 def rodrigues(rvec):
@@ -45,19 +46,16 @@ def solve_pnp_batch(problems, iterations=300, reproj_error=5.0, seed=0, points_p
     if not problems:
         return []
     ctx = ctx or default_context()
-    offs, objs, imgs, Ks = [0], [], [], []
+    objs, imgs, Ks = [], [], []
     for obj, img, K in problems:
         obj = np.asarray(obj, np.float64).reshape(-1, 3)
         img = np.asarray(img, np.float64).reshape(-1, 2)
         if obj.shape[0] != img.shape[0]:
             raise ValueError("objectPoints and imagePoints differ in length")
-        K = np.asarray(K, np.float64).reshape(3, 3)
-        objs.append(obj); imgs.append(img); Ks.append([K[0, 0], K[1, 1], K[0, 2], K[1, 2]])
-        offs.append(offs[-1] + obj.shape[0])
-    dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a)).to(dt).cuda()
-    R, t, n_in, mask, ok = ops.pnp_ransac(ctx, dev(np.asarray(offs, np.int32), torch.int32), dev(np.concatenate(objs), torch.float64),
-                                          dev(np.concatenate(imgs), torch.float64), dev(np.asarray(Ks), torch.float64), iterations,
-                                          reproj_error, seed, points_per_vote)
+        objs.append(obj); imgs.append(img); Ks.append(k4(K))
+    offs, obj = pack_ragged(objs)
+    R, t, n_in, mask, ok = ops.pnp_ransac(ctx, to_device(offs, torch.int32), to_device(obj), to_device(np.concatenate(imgs)), to_device(Ks),
+                                          iterations, reproj_error, seed, points_per_vote)
     R, t, mask, ok = R.cpu().numpy(), t.cpu().numpy(), mask.cpu().numpy(), ok.cpu().numpy()
     return [(bool(ok[p]), R[p], t[p], np.nonzero(mask[offs[p]:offs[p + 1]])[0]) for p in range(len(problems))]
 

@@ -14,6 +14,7 @@ import torch
 
 from .. import ops
 from ..runtime import default_context
+from ._host import k4, to_device
 
 
 def _problems_per_class(idx, cnt, min_votes):
@@ -115,14 +116,10 @@ def poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=0.5, min_vote
     if instances is not None and (not isinstance(instances, dict) or set(instances) - {"iou", "max_instances", "max_rounds"}):
         raise ValueError("instances must be None or a dict with iou / max_instances / max_rounds")
     ctx = ctx or default_context()
-    dev = lambda a: a.cuda() if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
-    boxes3D, scores = dev(boxes3D).float().contiguous(), dev(scores).float().contiguous()
+    boxes3D, scores = to_device(boxes3D, torch.float32), to_device(scores, torch.float32)
     B, N, C = scores.shape
-    corners = torch.as_tensor(np.asarray(threeD_boxes, np.float64).reshape(C, 8, 3), device="cuda")
-    K = np.asarray(K, np.float64)
-    Ks = np.broadcast_to(K.reshape(-1, 3, 3), (B, 3, 3)) if K.ndim == 3 or K.size == 9 else None
-    if Ks is None:
-        raise ValueError("K must be 3x3 or [B,3,3]")
+    corners = to_device(threeD_boxes, shape=(C, 8, 3))
+    K_all = to_device(k4(K, B))  # K 3x3 or [B,3,3], anything else is a ValueError
     idx, cnt = ops.score_threshold_compact(ctx, scores, float(threshold))  # bit-exact np.where order
     mv = max(int(min_votes), 1)
     pr = _problems_per_class(idx, cnt, mv) if instances is None else _problems_per_instance(ctx, boxes3D, scores, idx, cnt, mv, instances)
@@ -132,7 +129,6 @@ def poses_from_outputs(boxes3D, scores, threeD_boxes, K, threshold=0.5, min_vote
     pr.obj = corners[pr.c_of].reshape(-1, 3).contiguous()
     pr.offs = torch.zeros((pr.k.numel() + 1,), dtype=torch.int32, device="cuda")
     pr.offs[1:] = (8 * torch.cumsum(pr.k, 0)).to(torch.int32)
-    K_all = torch.as_tensor(np.stack([[Kb[0, 0], Kb[1, 1], Kb[0, 2], Kb[1, 2]] for Kb in Ks]), dtype=torch.float64, device="cuda")
     pr.K_p = K_all[pr.pb].contiguous()
     R, t, _n_in, mask, ok = ops.pnp_ransac(ctx, pr.offs, pr.obj, pr.img, pr.K_p, iterations, reproj_error, seed, 8)
     extra = None

@@ -10,6 +10,7 @@ import torch
 
 from .. import ops
 from ..runtime import default_context
+from ._host import k4, per_pose, to_device
 
 
 def transform_pts_Rt(pts, R, t):
@@ -20,12 +21,11 @@ def transform_pts_Rt(pts, R, t):
 
 
 def _one(R_est, t_est, R_gt, t_gt, pts, symmetric):
-    dev = lambda a, shape: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64).reshape(shape))).cuda()
     pts = np.asarray(pts)
     if pts.ndim != 2 or pts.shape[1] != 3:
         raise ValueError("pts must be n x 3")
-    out = ops.pose_errors(default_context(), dev(pts, (-1, 3)), dev(R_est, (1, 3, 3)), dev(t_est, (1, 3)), dev(R_gt, (1, 3, 3)),
-                          dev(t_gt, (1, 3)), symmetric)
+    out = ops.pose_errors(default_context(), to_device(pts), to_device(R_est, shape=(1, 3, 3)), to_device(t_est, shape=(1, 3)),
+                          to_device(R_gt, shape=(1, 3, 3)), to_device(t_gt, shape=(1, 3)), symmetric)
     return float(out.cpu()[0])
 
 
@@ -41,22 +41,8 @@ def adi(R_est, t_est, R_gt, t_gt, pts):
 
 def add_batch(R_est, t_est, R_gt, t_gt, pts, symmetric=False):
     """n poses of one object in one launch: R_* [n,3,3], t_* [n,3] -> float64 [n]."""
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.float64))).cuda()
-    return ops.pose_errors(default_context(), dev(pts), dev(R_est), dev(np.reshape(t_est, (-1, 3))), dev(R_gt),
-                           dev(np.reshape(t_gt, (-1, 3))), symmetric).cpu().numpy()
-
-
-def _dev(a, shape=None):
-    a = np.array(a, np.float64)  # a copy: broadcast views are read-only
-    return torch.from_numpy(a if shape is None else np.ascontiguousarray(a.reshape(shape))).cuda()
-
-
-def _stack(a, n, shape):
-    """one array per pose, or one shared by all n poses -> float64 [n, *shape]"""
-    a = np.asarray(a, np.float64)
-    if a.size == int(np.prod(shape)):
-        return np.broadcast_to(a.reshape(shape), (n,) + shape)
-    return a.reshape((n,) + shape)
+    return ops.pose_errors(default_context(), to_device(pts), to_device(R_est), to_device(t_est, shape=(-1, 3)), to_device(R_gt),
+                           to_device(t_gt, shape=(-1, 3)), symmetric).cpu().numpy()
 
 
 def _poses(R_est, t_est, R_gt, t_gt):
@@ -74,9 +60,8 @@ def reproj_batch(K, R_est, t_est, R_gt, t_gt, pts):
     if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
         raise ValueError("pts must be n x 3")
     R_est, t_est, R_gt, t_gt = _poses(R_est, t_est, R_gt, t_gt)
-    n = R_est.shape[0]
-    K9 = _stack(K, n, (3, 3))
-    return ops.pose_reproj(default_context(), _dev(pts), _dev(K9), _dev(R_est), _dev(t_est), _dev(R_gt), _dev(t_gt)).cpu().numpy()
+    poses = [to_device(a) for a in (per_pose(K, R_est.shape[0], (3, 3)), R_est, t_est, R_gt, t_gt)]
+    return ops.pose_reproj(default_context(), to_device(pts), *poses).cpu().numpy()
 
 
 def reproj(K, R_est, t_est, R_gt, t_gt, pts):
@@ -91,10 +76,10 @@ def _sym_batch(op, R_est, t_est, R_gt, t_gt, pts, syms, K, return_sym):
         raise ValueError("pts must be n x 3")
     S_R, S_t = stack_symmetries(syms)
     R_est, t_est, R_gt, t_gt = _poses(R_est, t_est, R_gt, t_gt)
-    poses = [_dev(a) for a in (R_est, t_est, R_gt, t_gt)]
+    poses = [to_device(a) for a in (R_est, t_est, R_gt, t_gt)]
     if K is not None:
-        poses.insert(0, _dev(_stack(K, R_est.shape[0], (3, 3))))
-    err, sym = op(default_context(), _dev(pts), _dev(S_R), _dev(S_t), *poses, best_sym=return_sym)
+        poses.insert(0, to_device(per_pose(K, R_est.shape[0], (3, 3))))
+    err, sym = op(default_context(), to_device(pts), to_device(S_R), to_device(S_t), *poses, best_sym=return_sym)
     return (err.cpu().numpy(), sym.cpu().numpy()) if return_sym else err.cpu().numpy()
 
 
@@ -165,22 +150,16 @@ def depth_im_to_dist_im(depth_im, K):
     return np.linalg.norm(np.dstack((X, Y, d)), axis=2)
 
 
-def _K4(K, n):
-    K = _stack(K, n, (3, 3))
-    return np.ascontiguousarray(np.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], axis=1))
-
-
 def vsd_from_depth(depth_test, depth_est, depth_gt, K, delta, tau, cost_type="step", return_counts=False):
     """VSD of n problems from depth images already rendered: depth_est / depth_gt [n,h,w] (numpy or cuda tensors),
     depth_test [h,w] shared by all of them or [n,h,w] (float32 or uint16), K 3x3 or [n,3,3] -> float64 [n]; with
     return_counts also the intersection and union pixel counts."""
-    dev32 = lambda a: (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.float32)))).cuda().float()
-    de, dg, dt = dev32(depth_est), dev32(depth_gt), dev32(depth_test)
+    de, dg, dt = (to_device(a, torch.float32) for a in (depth_est, depth_gt, depth_test))
     if de.dim() == 2:
         de, dg = de[None], dg[None]
     if de.dim() != 3 or dg.shape != de.shape:
         raise ValueError("vsd: depth_est and depth_gt must be [n,h,w] of one shape")
-    e, inter, uni = ops.vsd(default_context(), dt, de, dg, _dev(_K4(K, de.shape[0])), delta, tau, cost_type)
+    e, inter, uni = ops.vsd(default_context(), dt, de, dg, to_device(k4(K, de.shape[0])), delta, tau, cost_type)
     e = e.cpu().numpy()
     return (e, inter.cpu().numpy(), uni.cpu().numpy()) if return_counts else e
 
@@ -195,7 +174,7 @@ def vsd_batch(R_est, t_est, R_gt, t_gt, model, depth_test, K, delta, tau, cost_t
     R_est, t_est, R_gt, t_gt = _poses(R_est, t_est, R_gt, t_gt)
     n = R_est.shape[0]
     h, w = np.shape(depth_test)[-2:]
-    Ks = _stack(K, n, (3, 3))
+    Ks = per_pose(K, n, (3, 3))
     depth = render_depth_batch(model, (w, h), np.concatenate([Ks, Ks]), np.concatenate([R_est, R_gt]), np.concatenate([t_est, t_gt]),
                                clip_near=clip_near, clip_far=clip_far)
     return vsd_from_depth(depth_test, depth[:n], depth[n:], Ks, delta, tau, cost_type, return_counts)

@@ -7,6 +7,7 @@ import torch
 
 from .. import ops
 from ..runtime import default_context
+from ._host import k4, to_device
 
 
 def _mesh(model):
@@ -29,12 +30,8 @@ def render_depth_batch(model, im_size, K, R, t, clip_near=100, clip_far=10000, c
     pts, faces = _mesh(model)
     R = np.asarray(R, np.float64).reshape(-1, 3, 3)
     n = R.shape[0]
-    t = np.asarray(t, np.float64).reshape(n, 3)
-    K = np.asarray(K, np.float64)
-    K = np.broadcast_to(K.reshape(3, 3), (n, 3, 3)) if K.size == 9 else K.reshape(n, 3, 3)
-    K4 = np.stack([K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]], axis=1)
-    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    return ops.render_depth(ctx or default_context(), dev(pts), dev(faces), dev(R), dev(t), dev(K4), w, h, float(clip_near), float(clip_far))
+    return ops.render_depth(ctx or default_context(), to_device(pts), to_device(faces, torch.int32), to_device(R), to_device(t, shape=(n, 3)),
+                            to_device(k4(K, n)), w, h, float(clip_near), float(clip_far))
 
 
 def render(model, im_size, K, R, t, clip_near=100, clip_far=10000, mode="depth", ambient_weight=0.5, surf_color=None,

@@ -12,13 +12,9 @@ import torch
 from .. import ops
 from ..runtime import default_context
 from . import pnp
+from ._host import k4, pack_ragged, to_device
 
 STATUS_NAMES = ("converged", "max_iterations", "too_few", "singular", "behind")
-
-
-def _k4(K):
-    K = np.asarray(K, np.float64).reshape(3, 3)
-    return [K[0, 0], K[1, 1], K[0, 2], K[1, 2]]
 
 
 def uncertainty_pnp_batch(problems, init=None, max_iterations=50, gradient_tol=1e-10, parameter_tol=1e-8, function_tol=1e-6,
@@ -40,21 +36,20 @@ def uncertainty_pnp_batch(problems, init=None, max_iterations=50, gradient_tol=1
         wts, pts3 = np.asarray(wts, np.float64), np.asarray(pts3, np.float64).reshape(-1, 3)
         if wts.shape != (pts2.shape[0], 3) or pts3.shape[0] != pts2.shape[0]:
             raise ValueError("uncertainty_pnp_batch: need points_2d [pn,2], weights_2d [pn,3], points_3d [pn,3]")
-        p2.append(pts2); w2.append(wts); p3.append(pts3); Ks.append(_k4(K))
+        p2.append(pts2); w2.append(wts); p3.append(pts3); Ks.append(k4(K))
     need = [p for p in range(P) if init[p] is None]
     seeded = [True] * P
     if need:
         live = [(w2[p] != 0).any(1) for p in need]
-        got = pnp.solve_pnp_batch([(p3[p][m], p2[p][m], np.asarray(problems[p][3], np.float64).reshape(3, 3)) for p, m in zip(need, live)],
+        got = pnp.solve_pnp_batch([(p3[p][m], p2[p][m], problems[p][3]) for p, m in zip(need, live)],
                                   seed=seed, points_per_vote=0, ctx=ctx)
         for p, (ok, R, t, _inl) in zip(need, got):
             init[p], seeded[p] = (R, t), bool(ok)
     R0 = np.stack([np.asarray(i[0], np.float64).reshape(3, 3) for i in init])
     t0 = np.stack([np.asarray(i[1], np.float64).reshape(3) for i in init])
-    offs = np.concatenate([[0], np.cumsum([len(a) for a in p2])]).astype(np.int32)
-    dev = lambda a, dt=torch.float64: torch.from_numpy(np.ascontiguousarray(a)).to(dt).cuda()
-    r = ops.pnp_refine_weighted(ctx, dev(offs, torch.int32), dev(np.concatenate(p3)), dev(np.concatenate(p2)), dev(np.concatenate(w2)),
-                                dev(np.asarray(Ks)), dev(R0), dev(t0), max_iterations, gradient_tol, parameter_tol, function_tol)
+    offs, obj = pack_ragged(p3)
+    r = ops.pnp_refine_weighted(ctx, to_device(offs, torch.int32), to_device(obj), to_device(np.concatenate(p2)), to_device(np.concatenate(w2)),
+                                to_device(Ks), to_device(R0), to_device(t0), max_iterations, gradient_tol, parameter_tol, function_tol)
     r = {k: v.cpu().numpy() for k, v in r.items()}
     out = []
     for p in range(P):
