@@ -501,6 +501,26 @@ size_t pp_vsd_workspace_bytes(int n, int width, int height);
 int pp_vsd_f64(pp_ctx* ctx, int n, int width, int height, const float* depth_test, long long test_stride, const float* depth_est,
                const float* depth_gt, const double* K4, double delta, double tau, int cost_type, void* workspace, double* e,
                long long* inter, long long* uni);
+/* VSD at n_tau misalignment tolerances in one pass over the pixels -- what BOP's AR_VSD needs (ten taus of 0.05 ... 0.5 x the
+ * object diameter, delta = 15 mm, thresholds of correctness 0.05 ... 0.5) -- plus the counts behind the visible fraction of
+ * the ground-truth object.  depth_*, test_stride, K4, delta and cost_type as in pp_vsd_f64.  taus: HOST array of n_tau
+ * (1 ... 16) positive, strictly increasing tolerances in depth units, shared by the launch and passed to the kernel by value.
+ * visib_mode 0: the rule of pp_vsd_f64 (the reference's estimate_visib_mask: a pixel without sensor depth is never
+ * visible).  visib_mode 1: BOP 2019's rule (bop_toolkit's visibility.estimate_visib_mask with visib_mode 'bop19'; parity with
+ * bop_toolkit unpinned: its definition restated, tests/vsd_bop_np.py): a model pixel is visible when d_model > 0 and
+ * (float32(d_model) - float32(d_test) <= delta or d_test == 0).  In both modes the estimate's mask is then widened by
+ * visib_gt && d_est > 0.  A pixel's three distances and both masks are computed once and serve every tau; the 'step' cost is
+ * a histogram in integer arithmetic (a pixel of the intersection falls into the one bin that counts the taus <= |d_gt - d_est|).
+ * Out e [n,n_tau] float64: (cost_t + (union - inter)) / union, 1.0 at every tau when the union is empty; column t carries the
+ * bits pp_vsd_f64 returns at taus[t] in mode 0 (same blocks and summation order).  inter, uni, visib_gt (pixels in the
+ * ground-truth visibility mask), px_gt (pixels with d_gt > 0): [n] int64 each, NULL = skip; visib_gt / px_gt is BOP's
+ * visib_fract.  Fixed-order reductions and integer counts only: bit-identical run to run.
+ * workspace >= pp_vsd_multi_workspace_bytes (0: bad shape). */
+size_t pp_vsd_multi_workspace_bytes(int n, int width, int height, int n_tau);
+int pp_vsd_multi_f64(pp_ctx* ctx, int n, int width, int height, const float* depth_test, long long test_stride,
+                     const float* depth_est, const float* depth_gt, const double* K4, double delta, int n_tau, const double* taus,
+                     int cost_type, int visib_mode, void* workspace, double* e, long long* inter, long long* uni,
+                     long long* visib_gt, long long* px_gt);
 /* reproj() of pose_error.py:179-207: mean over pts [n_pts,3] of the distance in pixels between K (R_est p + t_est) and
  * K (R_gt p + t_gt), each projection rounded to float32 and the norm taken in float32 as there (the mean is summed in float64:
  * within 1e-5 relative of the reference's float32 mean).  K9 [n_pose,3,3] row-major float64, the rest as pp_pose_add_f64;

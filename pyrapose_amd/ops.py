@@ -806,6 +806,35 @@ def vsd(ctx, depth_test, depth_est, depth_gt, K4, delta, tau, cost_type="step"):
     return e, inter, uni
 
 
+VSD_VISIB = {"bop18": 0, "bop19": 1}
+
+
+def vsd_multi(ctx, depth_test, depth_est, depth_gt, K4, delta, taus, cost_type="step", visib_mode="bop19"):
+    """VSD of n problems at T misalignment tolerances in one pass over the pixels (pp_vsd_multi_f64): tensors as in vsd();
+    taus: T = 1 ... 16 positive, strictly increasing host values; visib_mode 'bop18' (the rule of vsd()) or 'bop19' (a rendered
+    pixel without sensor depth counts as visible) -> (e float64 [n,T], intersection, union, visib_gt, px_gt: int64 [n] each;
+    visib_gt / px_gt is the visible fraction of the ground-truth object)."""
+    if cost_type not in VSD_COSTS:
+        raise ValueError("vsd_multi: unknown pixel matching cost %r (step | tlinear)" % (cost_type,))
+    if visib_mode not in VSD_VISIB:
+        raise ValueError("vsd_multi: unknown visibility rule %r (bop18 | bop19)" % (visib_mode,))
+    taus = np.ascontiguousarray(np.asarray(taus, np.float64).reshape(-1))
+    T = int(taus.size)
+    de = _arg("vsd_multi", "depth_est", depth_est, _F32, (None, None, None))
+    n, h, w = (int(s) for s in de.shape)
+    dg = _arg("vsd_multi", "depth_gt", depth_gt, _F32, (n, h, w))
+    shared = torch.is_tensor(depth_test) and depth_test.dim() == 2  # one scene [h,w] for all problems, else [n,h,w]
+    dt = _arg("vsd_multi", "depth_test", depth_test, _F32, (h, w) if shared else (n, h, w))
+    K4 = _arg("vsd_multi", "K4", K4, _F64, (n, 4))
+    ws = _workspace(lib.pp_vsd_multi_workspace_bytes(n, w, h, T))
+    e = _out(de, (n, T))
+    inter, uni, vis, px = (_out(de, (n,), torch.int64) for _ in range(4))
+    check(lib.pp_vsd_multi_f64(ctx.handle, n, w, h, _ptr(dt), 0 if shared else h * w, _ptr(de), _ptr(dg), _ptr(K4), float(delta), T,
+                               taus.ctypes.data_as(C.POINTER(C.c_double)), VSD_COSTS[cost_type], VSD_VISIB[visib_mode], _ptr(ws),
+                               _ptr(e), _ptr(inter), _ptr(uni), _ptr(vis), _ptr(px)), ctx.handle, "pp_vsd_multi_f64")
+    return e, inter, uni, vis, px
+
+
 ICP_MODES = {"point_to_point": 0, "point_to_plane": 1}
 ICP_STATUS = {0: "ok", 1: "too_few_correspondences", 2: "singular"}
 

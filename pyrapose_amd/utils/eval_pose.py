@@ -157,7 +157,7 @@ BOP_PIXELS = tuple(5 * k for k in range(1, 11))
 
 def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, model_diameters, load_depth, K, threshold=0.5, min_votes=10,
                           delta=0.3, tau=20.0, vsd_threshold=0.3, cost_type="step", symmetric_classes=(), gt_translation_scale=0.001,
-                          depth_scale=1000.0, seed=0, refine=None, weighting=None, instances=None, symmetries=None):
+                          depth_scale=1000.0, seed=0, refine=None, weighting=None, instances=None, symmetries=None, bop_vsd=None):
     """The metric block of tless_eval.py:470-725 (also in occlusion_eval.py / ycbv_eval.py / homebrewed_eval.py) on top of the
     loop of evaluate_add: per detected, annotated class, the rotation / translation errors re / te (correct when re < 5 deg
     and te < 0.05), the reprojection error (< 5 px), VSD against the image's depth (< vsd_threshold) and ADD (ADI for
@@ -177,6 +177,14 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
     'sym_mssd', 'sym_mspd' (the symmetry that attains each); the result gains mssd_less / mspd_less [10, C+1] (ok detections
     with MSSD < BOP_FRACTIONS x the model diameter, MSPD < BOP_PIXELS x depth image width / 640 pixels), their _rate arrays,
     ar_mssd / ar_mspd [C+1] (the mean of the rates over the ten thresholds) and bop_fractions / bop_pixels.
+    bop_vsd: None (nothing below is computed or returned), or a dict of delta (15.0, depth units), visib_mode ('bop19') and
+    cost_type ('step'): BOP's VSD over its tolerance range, taus = BOP_FRACTIONS x the model diameter x depth_scale, in one
+    launch per (image, class) on the two renders the single-tau VSD uses (pose_error.vsd_multi_from_depth).  Each error dict
+    gains 'vsd_bop' (ten values) and 'visib_fract' (the visible fraction of the annotation); the result gains vsd_bop_less
+    [10 taus, 10 thresholds, C+1] (ok detections with vsd_bop < BOP_FRACTIONS as thresholds of correctness), vsd_bop_less_rate
+    and ar_vsd [C+1], its mean over both axes; with symmetries also ar = (ar_vsd + ar_mssd + ar_mspd) / 3, BOP's average recall.
+    Annotations are not dropped from allPoses by their visible fraction (BOP keeps those of at least 10 %): filter in the
+    generator, on scene_gt_info.json or on pose_error.visib_fract_batch.
     Returns dict(allPoses, trueDets, less5, rep_less5, vsd_less_t, add_less [len(ADD_FRACTIONS), C+1], add_fractions, the
     matching rates (counter / allPoses) and errors: one dict per scored detection); index = class id + 1 as in evaluate_add."""
     C = len(model_diameters)
@@ -191,6 +199,12 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
         symmetries = [stack_symmetries(s) for s in symmetries]
         mssd_less = np.zeros((len(BOP_FRACTIONS), C + 1), np.uint32)
         mspd_less = np.zeros((len(BOP_PIXELS), C + 1), np.uint32)
+    if bop_vsd is not None:
+        unknown = set(bop_vsd) - {"delta", "visib_mode", "cost_type"}
+        if unknown:
+            raise ValueError("bop_vsd: unknown keys %s (delta | visib_mode | cost_type)" % sorted(unknown))
+        bop_vsd = dict(dict(delta=15.0, visib_mode="bop19", cost_type="step"), **bop_vsd)
+        vsd_bop_less = np.zeros((len(BOP_FRACTIONS), len(BOP_FRACTIONS), C + 1), np.uint32)
     decode_kw = dict(threeD_boxes=threeD_boxes, threshold=threshold, min_votes=min_votes, seed=seed, weighting=weighting)
     refine = None if refine is None else dict(refine, depth_scale=depth_scale)
     for index, labels, anno, Kc, depth, _mask, pairs_by_class in _scored_images(
@@ -208,7 +222,14 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
             xyz = pose_error.te_batch(t_g, t_est)
             rep = pose_error.reproj_batch(Kc, R_est, t_est, R_g, t_g, model["pts"])
             mm = dict(model, pts=np.asarray(model["pts"], np.float64) * depth_scale)
-            e_vsd = pose_error.vsd_batch(R_est, t_est * depth_scale, R_g, t_g * depth_scale, mm, depth, Kc, delta, tau, cost_type)
+            if bop_vsd is None:
+                e_vsd = pose_error.vsd_batch(R_est, t_est * depth_scale, R_g, t_g * depth_scale, mm, depth, Kc, delta, tau, cost_type)
+            else:  # the two renders of vsd_batch, made once for both VSD launches
+                d_est, d_gt, Ks = pose_error.render_pairs(R_est, t_est * depth_scale, R_g, t_g * depth_scale, mm, depth, Kc)
+                e_vsd = pose_error.vsd_from_depth(depth, d_est, d_gt, Ks, delta, tau, cost_type)
+                taus = np.array(BOP_FRACTIONS) * model_diameters[cls] * depth_scale
+                e_bop, _inter, _uni, n_vis, n_px = pose_error.vsd_multi_from_depth(
+                    depth, d_est, d_gt, Ks, bop_vsd["delta"], taus, bop_vsd["cost_type"], bop_vsd["visib_mode"], return_counts=True)
             e_add = pose_error.add_batch(R_est, t_est, R_g, t_g, model["pts"], symmetric=cls in symmetric_classes)
             if symmetries is not None:
                 e_mssd, s_mssd = pose_error.mssd_batch(R_est, t_est, R_g, t_g, model["pts"], symmetries[cls], return_sym=True)
@@ -224,6 +245,8 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
                     errors[-1].update(instance=d["instance"], gt=pairs[k][1])
                 if symmetries is not None:
                     errors[-1].update(mssd=float(e_mssd[k]), mspd=float(e_mspd[k]), sym_mssd=int(s_mssd[k]), sym_mspd=int(s_mspd[k]))
+                if bop_vsd is not None:
+                    errors[-1].update(vsd_bop=e_bop[k].tolist(), visib_fract=float(n_vis[k]) / float(n_px[k]) if n_px[k] > 0 else 0.0)
                 if not d["ok"]:
                     continue
                 out["less5"][cls + 1] += bool(rd[k] < 5.0 and xyz[k] < 0.05)
@@ -236,6 +259,8 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
                         mssd_less[j, cls + 1] += bool(e_mssd[k] < f * model_diameters[cls])
                     for j, p in enumerate(BOP_PIXELS):
                         mspd_less[j, cls + 1] += bool(e_mspd[k] < p * width / 640.0)
+                if bop_vsd is not None:
+                    vsd_bop_less[:, :, cls + 1] += e_bop[k][:, None] < np.array(BOP_FRACTIONS)[None, :]
     all_f = out["allPoses"].astype(np.float64)
     with np.errstate(divide="ignore", invalid="ignore"):
         for k in counters[1:]:
@@ -246,5 +271,11 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
                        mspd_less_rate=np.nan_to_num(mspd_less / all_f[None]), bop_fractions=np.array(BOP_FRACTIONS),
                        bop_pixels=np.array(BOP_PIXELS, np.float64))
             out.update(ar_mssd=out["mssd_less_rate"].mean(axis=0), ar_mspd=out["mspd_less_rate"].mean(axis=0))
+        if bop_vsd is not None:
+            out.update(vsd_bop_less=vsd_bop_less, vsd_bop_less_rate=np.nan_to_num(vsd_bop_less / all_f[None, None]),
+                       bop_fractions=np.array(BOP_FRACTIONS))
+            out["ar_vsd"] = out["vsd_bop_less_rate"].mean(axis=(0, 1))
+            if symmetries is not None:
+                out["ar"] = (out["ar_vsd"] + out["ar_mssd"] + out["ar_mspd"]) / 3.0
     out.update(add_less=add_less, add_fractions=np.array(ADD_FRACTIONS), errors=errors)
     return out

@@ -2,7 +2,8 @@
 utils/linemod_eval.py:525-531, tless_eval.py:470-471, 651-662): same names, arguments and float return values, computed by the
 HIP kernels (ADD / ADI / reproj in csrc/pose.hip, VSD in csrc/render.hip on depth images from utils.renderer); re / te and
 depth_im_to_dist_im stay on the host in numpy.  mssd / mspd are BOP's symmetry-aware errors (bop_toolkit_lib.pose_error), also
-in csrc/pose.hip, over the symmetry sets of utils/symmetry.py."""
+in csrc/pose.hip, over the symmetry sets of utils/symmetry.py; vsd_multi_* score VSD at up to 16 misalignment tolerances in one
+pass with BOP 2019's visibility rule (AR_VSD), and visib_fract_batch gives the visible fraction of an annotation."""
 import math
 
 import numpy as np
@@ -164,20 +165,27 @@ def vsd_from_depth(depth_test, depth_est, depth_gt, K, delta, tau, cost_type="st
     return (e, inter.cpu().numpy(), uni.cpu().numpy()) if return_counts else e
 
 
-def vsd_batch(R_est, t_est, R_gt, t_gt, model, depth_test, K, delta, tau, cost_type="step", clip_near=100, clip_far=10000,
-              return_counts=False):
-    """vsd() of n poses of one object: both depth renderings of every pose in one launch, then one VSD launch.  depth_test
-    [h,w] (one scene) or [n,h,w]; K 3x3 or [n,3,3]; R_* [n,3,3], t_* [n,3] -> float64 [n]."""
+def render_pairs(R_est, t_est, R_gt, t_gt, model, depth_test, K, clip_near=100, clip_far=10000):
+    """The two depth renderings VSD needs of each of n poses of one object, in one render launch at the size of depth_test
+    ([h,w] or [n,h,w]) -> (depth_est, depth_gt: cuda float32 [n,h,w], K as float64 [n,3,3])."""
     from .renderer import render_depth_batch
-    if cost_type not in ops.VSD_COSTS:
-        raise ValueError("vsd: unknown pixel matching cost %r (step | tlinear)" % (cost_type,))
     R_est, t_est, R_gt, t_gt = _poses(R_est, t_est, R_gt, t_gt)
     n = R_est.shape[0]
     h, w = np.shape(depth_test)[-2:]
     Ks = per_pose(K, n, (3, 3))
     depth = render_depth_batch(model, (w, h), np.concatenate([Ks, Ks]), np.concatenate([R_est, R_gt]), np.concatenate([t_est, t_gt]),
                                clip_near=clip_near, clip_far=clip_far)
-    return vsd_from_depth(depth_test, depth[:n], depth[n:], Ks, delta, tau, cost_type, return_counts)
+    return depth[:n], depth[n:], Ks
+
+
+def vsd_batch(R_est, t_est, R_gt, t_gt, model, depth_test, K, delta, tau, cost_type="step", clip_near=100, clip_far=10000,
+              return_counts=False):
+    """vsd() of n poses of one object: both depth renderings of every pose in one launch, then one VSD launch.  depth_test
+    [h,w] (one scene) or [n,h,w]; K 3x3 or [n,3,3]; R_* [n,3,3], t_* [n,3] -> float64 [n]."""
+    if cost_type not in ops.VSD_COSTS:
+        raise ValueError("vsd: unknown pixel matching cost %r (step | tlinear)" % (cost_type,))
+    depth_est, depth_gt, Ks = render_pairs(R_est, t_est, R_gt, t_gt, model, depth_test, K, clip_near, clip_far)
+    return vsd_from_depth(depth_test, depth_est, depth_gt, Ks, delta, tau, cost_type, return_counts)
 
 
 def vsd(R_est, t_est, R_gt, t_gt, model, depth_test, K, delta, tau, cost_type="step"):
@@ -185,3 +193,48 @@ def vsd(R_est, t_est, R_gt, t_gt, model, depth_test, K, delta, tau, cost_type="s
     depth_test: the scene's depth image [h,w]; delta, tau in its unit (the reference calls it with 0.3 and 20, millimetres,
     and renders with clip_near=100, clip_far=10000)."""
     return float(vsd_batch(R_est, t_est, R_gt, t_gt, model, depth_test, K, delta, tau, cost_type)[0])
+
+
+def vsd_multi_from_depth(depth_test, depth_est, depth_gt, K, delta, taus, cost_type="step", visib_mode="bop19", return_counts=False):
+    """VSD of n problems at T misalignment tolerances (1 ... 16, positive, strictly increasing) from depth images already
+    rendered, one pass over the pixels for all of them; arrays as in vsd_from_depth.  visib_mode 'bop18': the visibility rule
+    of vsd(); 'bop19': BOP 2019's, under which a rendered pixel without sensor depth counts as visible -> float64 [n,T]; with
+    return_counts also (intersection, union, visib_gt, px_gt), int64 [n] each: the last two are the pixels of the
+    ground-truth visibility mask and of the ground-truth render."""
+    de, dg, dt = (to_device(a, torch.float32) for a in (depth_est, depth_gt, depth_test))
+    if de.dim() == 2:
+        de, dg = de[None], dg[None]
+    if de.dim() != 3 or dg.shape != de.shape:
+        raise ValueError("vsd_multi: depth_est and depth_gt must be [n,h,w] of one shape")
+    out = ops.vsd_multi(default_context(), dt, de, dg, to_device(k4(K, de.shape[0])), delta, taus, cost_type, visib_mode)
+    e = out[0].cpu().numpy()
+    return (e,) + tuple(c.cpu().numpy() for c in out[1:]) if return_counts else e
+
+
+def vsd_multi_batch(R_est, t_est, R_gt, t_gt, model, depth_test, K, delta, taus, cost_type="step", visib_mode="bop19",
+                    clip_near=100, clip_far=10000, return_counts=False):
+    """vsd_batch at T tolerances: both depth renderings of every pose in one render launch, then one VSD launch for all taus
+    -> float64 [n,T] (and the counts of vsd_multi_from_depth with return_counts)."""
+    if cost_type not in ops.VSD_COSTS:
+        raise ValueError("vsd_multi: unknown pixel matching cost %r (step | tlinear)" % (cost_type,))
+    if visib_mode not in ops.VSD_VISIB:
+        raise ValueError("vsd_multi: unknown visibility rule %r (bop18 | bop19)" % (visib_mode,))
+    depth_est, depth_gt, Ks = render_pairs(R_est, t_est, R_gt, t_gt, model, depth_test, K, clip_near, clip_far)
+    return vsd_multi_from_depth(depth_test, depth_est, depth_gt, Ks, delta, taus, cost_type, visib_mode, return_counts)
+
+
+def visib_fract_batch(R_gt, t_gt, model, depth_test, K, delta=15.0, visib_mode="bop19", clip_near=100, clip_far=10000):
+    """Visible fraction of n ground-truth poses of one object (what BOP's scene_gt_info.json calls visib_fract): pixels of the
+    ground-truth visibility mask / pixels of the ground-truth render -> float64 [n], 0.0 where nothing is rendered.  One render
+    launch and one VSD launch, the ground-truth render in both model slots."""
+    from .renderer import render_depth_batch
+    if visib_mode not in ops.VSD_VISIB:
+        raise ValueError("visib_fract: unknown visibility rule %r (bop18 | bop19)" % (visib_mode,))
+    R_gt = np.asarray(R_gt, np.float64).reshape(-1, 3, 3)
+    n = R_gt.shape[0]
+    t_gt = np.asarray(t_gt, np.float64).reshape(n, 3)
+    h, w = np.shape(depth_test)[-2:]
+    Ks = per_pose(K, n, (3, 3))
+    depth = render_depth_batch(model, (w, h), Ks, R_gt, t_gt, clip_near=clip_near, clip_far=clip_far)
+    _e, _inter, _uni, vis, px = vsd_multi_from_depth(depth_test, depth, depth, Ks, delta, [1.0], "step", visib_mode, True)
+    return np.where(px > 0, vis / np.maximum(px, 1).astype(np.float64), 0.0)
