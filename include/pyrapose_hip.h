@@ -521,6 +521,34 @@ int pp_vsd_multi_f64(pp_ctx* ctx, int n, int width, int height, const float* dep
                      const float* depth_est, const float* depth_gt, const double* K4, double delta, int n_tau, const double* taus,
                      int cost_type, int visib_mode, void* workspace, double* e, long long* inter, long long* uni,
                      long long* visib_gt, long long* px_gt);
+/* Ground truth of n_scene scenes from the depth renders of their instances: what the training path reads besides the image.
+ * depth_stack [n_inst,canvas_h,canvas_w] float32: pp_render_depth_f32 outputs (one call per distinct mesh), instances
+ * scene_offsets[s] .. scene_offsets[s+1] belong to scene s (the offsets convention of pp_pnp_ransac_f64; given twice, as a
+ * HOST array that is checked before anything is launched and as its device copy that the kernels read; a scene may be
+ * empty and holds at most 255 instances: PP_ERR_SHAPE).  The image is the width x height window of the canvas at
+ * (off_x, off_y) (PP_ERR_SHAPE unless it lies inside); K4 [n_inst,4] = (fx, fy, cx, cy) float64 in IMAGE coordinates.
+ * depth_test: sensor depth float32 at depth_test + s * test_stride (0: one image shared by the scenes, or width * height)
+ * with scene_depth NULL; or NULL, then scene_depth [n_scene,height,width] float32 is written -- per pixel the smallest
+ * positive instance depth, 0 where there is none (a synthetic scene's depth image) -- and stands in for it.
+ * Per instance, with d_gt its depth and d_test the scene's (in-image pixels only):
+ *   px_count [n_inst,3] int64 = px_count_all (d_gt > 0, whole canvas), px_count_valid (in image, d_gt > 0 and d_test > 0),
+ *     px_count_visib (in image, in the 'bop19' mask of pp_vsd_multi_f64 visib_mode 1, compared in float32 as there)
+ *   bbox_obj [n_inst,4] int32: (x, y, w, h) of the d_gt > 0 pixels of the whole canvas in image coordinates (may be negative
+ *     or reach past the image), w = x_max - x_min, h = y_max - y_min;  bbox_visib [n_inst,4]: the same of the visible mask;
+ *     both are (-1, -1, -1, -1) when px_count_visib is 0
+ *   mask_full / mask_visib [n_inst,height,width] uint8 0 / 255 (NULL = skip): d_gt > 0 and the visible mask.
+ * The counts and boxes restate bop_toolkit's calc_gt_info and the masks its calc_gt_masks (parity with bop_toolkit unpinned:
+ * the definitions restated, tests/scene_gt_np.py).  id_image [n_scene,height,width] uint8: the 1-based index within its scene
+ * of the LAST instance whose visible mask holds the pixel, 0 where none does: annotation_scripts/annotate_BOP.py:363-374
+ * (mask_img = np.where(obj_mask > 0, mask_id, mask_img) in instance order, later instances overwrite earlier ones).
+ * Integer counts, minima and maxima only: bit-identical run to run.  workspace_bytes >= pp_scene_gt_workspace_bytes (0: bad
+ * shape). */
+size_t pp_scene_gt_workspace_bytes(int n_inst, int canvas_w, int canvas_h);
+int pp_scene_gt_info(pp_ctx* ctx, int n_inst, int n_scene, const int* scene_offsets_host, const int* scene_offsets_dev,
+                     int canvas_w, int canvas_h, int width, int height, int off_x, int off_y, const float* depth_stack,
+                     const double* K4, const float* depth_test, long long test_stride, double delta, void* workspace,
+                     size_t workspace_bytes, float* scene_depth, unsigned char* id_image, long long* px_count, int* bbox_obj,
+                     int* bbox_visib, unsigned char* mask_full, unsigned char* mask_visib);
 /* reproj() of pose_error.py:179-207: mean over pts [n_pts,3] of the distance in pixels between K (R_est p + t_est) and
  * K (R_gt p + t_gt), each projection rounded to float32 and the norm taken in float32 as there (the mean is summed in float64:
  * within 1e-5 relative of the reference's float32 mean).  K9 [n_pose,3,3] row-major float64, the rest as pp_pose_add_f64;

@@ -173,6 +173,9 @@ _SIGS = {
     "pp_vsd_f64": (_i, [_p, _i, _i, _i, _p, _ll, _p, _p, _p, _d, _d, _i, _p, _p, _p, _p]),
     "pp_vsd_multi_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "pp_vsd_multi_f64": (_i, [_p, _i, _i, _i, _p, _ll, _p, _p, _p, _d, _i, C.POINTER(_d), _i, _i, _p, _p, _p, _p, _p, _p]),
+    "pp_scene_gt_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pp_scene_gt_info": (_i, [_p, _i, _i, C.POINTER(_i), _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _ll, _d, _p, _sz, _p, _p, _p, _p, _p,
+                              _p, _p]),
     "pp_pose_reproj_f64": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pp_pose_sym_workspace_bytes": (_sz, [_i, _i, _i]),
     "pp_pose_mssd_f64": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

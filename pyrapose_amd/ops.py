@@ -3,6 +3,7 @@
 Every function takes CUDA(ROCm) float32/float64/int tensors, hands raw device pointers to the HIP
 library on the ctx stream, and raises on a non-zero status.  torch is used only for memory and streams.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -833,6 +834,42 @@ def vsd_multi(ctx, depth_test, depth_est, depth_gt, K4, delta, taus, cost_type="
                                taus.ctypes.data_as(C.POINTER(C.c_double)), VSD_COSTS[cost_type], VSD_VISIB[visib_mode], _ptr(ws),
                                _ptr(e), _ptr(inter), _ptr(uni), _ptr(vis), _ptr(px)), ctx.handle, "pp_vsd_multi_f64")
     return e, inter, uni, vis, px
+
+
+SCENE_GT_MAX_INSTANCES = 255  # per scene: the id image is uint8 and 0 is the background
+SceneGT = collections.namedtuple("SceneGT", "px_count bbox_obj bbox_visib id_image scene_depth mask_full mask_visib")
+
+
+def scene_gt_info(ctx, depth_stack, scene_offsets, K4, depth_test=None, delta=15.0, window=None, masks=False):
+    """Ground truth of S scenes from the depth renders of their instances (pp_scene_gt_info): cuda float32 depth_stack
+    [n,ch,cw] (render_depth outputs stacked in scene order), scene_offsets: S+1 HOST integers rising from 0 to n (scene s owns
+    the instances scene_offsets[s] .. scene_offsets[s+1], at most 255), K4 float64 [n,4] in image coordinates; window
+    (off_x, off_y, w, h): the image inside the canvas, None = the whole canvas; depth_test: cuda float32 sensor depth [h,w]
+    (shared by the scenes) or [S,h,w], None = compose the scene depth from the instances -> SceneGT(px_count int64 [n,3] =
+    (all, valid, visib), bbox_obj int32 [n,4], bbox_visib int32 [n,4] as (x, y, w, h), id_image uint8 [S,h,w], scene_depth
+    float32 [S,h,w] (None with depth_test), mask_full, mask_visib uint8 [n,h,w] 0 / 255 (None without masks))."""
+    stack = _arg("scene_gt_info", "depth_stack", depth_stack, _F32, (None, None, None))
+    n, ch, cw = (int(s) for s in stack.shape)
+    off = np.ascontiguousarray(np.asarray(scene_offsets).reshape(-1), np.int32)
+    if off.size < 2 or not np.array_equal(off, np.asarray(scene_offsets).reshape(-1)):
+        raise ValueError("scene_gt_info: scene_offsets must hold S+1 >= 2 integers")
+    S = int(off.size) - 1
+    ox, oy, w, h = (int(v) for v in (window if window is not None else (0, 0, cw, ch)))
+    K4 = _arg("scene_gt_info", "K4", K4, _F64, (n, 4))
+    shared = torch.is_tensor(depth_test) and depth_test.dim() == 2
+    dt = _arg("scene_gt_info", "depth_test", depth_test, _F32, (h, w) if shared else (S, h, w), optional=True)
+    nbytes = lib.pp_scene_gt_workspace_bytes(n, cw, ch)
+    ws = _workspace(nbytes)
+    shape = (S, max(h, 0), max(w, 0))
+    out = SceneGT(_out(stack, (n, 3), torch.int64), _out(stack, (n, 4), _I32), _out(stack, (n, 4), _I32), _out(stack, shape, _U8),
+                  _out(stack, shape, _F32) if dt is None else None,
+                  *((_out(stack, (n,) + shape[1:], _U8) for _ in range(2)) if masks else (None, None)))
+    off_dev = torch.from_numpy(off).to(stack.device)
+    check(lib.pp_scene_gt_info(ctx.handle, n, S, off.ctypes.data_as(C.POINTER(C.c_int)), _ptr(off_dev), cw, ch, w, h, ox, oy, _ptr(stack),
+                               _ptr(K4), _ptr(dt), 0 if shared else h * w, float(delta), _ptr(ws), nbytes, _ptr(out.scene_depth),
+                               _ptr(out.id_image), _ptr(out.px_count), _ptr(out.bbox_obj), _ptr(out.bbox_visib), _ptr(out.mask_full),
+                               _ptr(out.mask_visib)), ctx.handle, "pp_scene_gt_info")
+    return out
 
 
 ICP_MODES = {"point_to_point": 0, "point_to_plane": 1}
