@@ -490,6 +490,31 @@ size_t pp_render_workspace_bytes(int n_pose, int n_vert, int n_tri, int width, i
 int pp_render_depth_f32(pp_ctx* ctx, int n_pose, int n_vert, const double* verts, int n_tri, const int* faces, const double* R,
                         const double* t, const double* K4, int width, int height, double clip_near, double clip_far, void* workspace,
                         size_t workspace_bytes, float* depth);
+/* Colour renderer: the 'rgb' / 'rgb+depth' modes of utils/hodan_renderer.py (shaders :22-103, _draw_rgb :480-518) beside the
+ * depth pass above.  Mesh, poses, K4, image size and clip range as in pp_render_depth_f32; colors [n_vert,3] float64 in
+ * [0, 1] (may be NULL when no colour output is asked for); normals [n_vert,3] float64, NULL allowed only with flat shading;
+ * shading 0 = flat, 1 = phong; ambient_weight in [0, 1]; light_cam_pos and bg_color: HOST arrays of 3 (passed to the kernels by
+ * value), the light in the OpenCV camera frame, bg_color in [0, 1].
+ * Outputs, each optional (NULL = skip), at least one required:
+ *   depth   [n_pose,height,width] float32: the bits pp_render_depth_f32 gives on the same inputs
+ *   tri_id  [n_pose,height,width] int32: the triangle shown, -1 where there is none.  The nearest fragment wins and, among
+ *           fragments of equal float32 depth, the smallest triangle index (one 64-bit key per pixel, (depth bits) << 32 | index,
+ *           resolved with an integer minimum): bit-identical run to run
+ *   rgb_f32 [n_pose,height,width,3] float32 and rgb_u8 [...] uint8 = rintf(rgb_f32 * 255.0f), channel order RGB.
+ * Shading, float64, evaluated by the raster workgroup on its resolved tile: with the winning triangle's edge weights w_i,
+ * q_i = w_i / Z_i / sum_j (w_j / Z_j) (perspective-correct) and an attribute a = (q0 a0 + q1 a1) + q2 a2; c = interpolated
+ * colour; per vertex P = R p + t, N = normalize(R n), L = normalize(light - P); l = normalize(interp L); phong: n =
+ * normalize(interp N) (back-facing normals are not flipped: ambient only); flat: n = normalize((P1 - P0) x (P2 - P0)), sign
+ * chosen so that n . P0 < 0 (facing the viewer whatever the winding); d = max(l . n, 0) (0 for a zero-length n or l);
+ * rgb = (float)(min(ambient_weight + d, 1) * c).  A pixel without a fragment holds bg_color, id -1 and depth 0.
+ * Deviations from the reference: textures are not rendered; the 3-vector normal is normalised (the reference normalises
+ * u_nm * vec4(normal, 1) over four components); parity with an OpenGL driver unpinned (restated: tests/render_rgb_np.py).
+ * workspace_bytes >= pp_render_rgbd_workspace_bytes (0: bad shape). */
+size_t pp_render_rgbd_workspace_bytes(int n_pose, int n_vert, int n_tri, int width, int height);
+int pp_render_rgbd(pp_ctx* ctx, int n_pose, int n_vert, const double* verts, const double* colors, const double* normals, int n_tri,
+                   const int* faces, const double* R, const double* t, const double* K4, int width, int height, double clip_near,
+                   double clip_far, int shading, double ambient_weight, const double* light_cam_pos, const double* bg_color,
+                   void* workspace, size_t workspace_bytes, float* depth, int* tri_id, float* rgb_f32, unsigned char* rgb_u8);
 /* vsd() of pose_error.py:105-176 (with depth_im_to_dist_im :43-61 and the visibility masks :15-40) on rendered depth images:
  * n problems, depth_est / depth_gt [n,height,width] float32, depth_test float32 (uint16 sensor depth converts exactly) at
  * depth_test + i * test_stride (0: one scene depth shared by all problems, or width * height), K4 [n,4] = (fx, fy, cx, cy)
@@ -549,6 +574,15 @@ int pp_scene_gt_info(pp_ctx* ctx, int n_inst, int n_scene, const int* scene_offs
                      const double* K4, const float* depth_test, long long test_stride, double delta, void* workspace,
                      size_t workspace_bytes, float* scene_depth, unsigned char* id_image, long long* px_count, int* bbox_obj,
                      int* bbox_visib, unsigned char* mask_full, unsigned char* mask_visib);
+/* A scene's image from its instances' colour renders: id_image [n_scene,height,width] uint8 of pp_scene_gt_info (window =
+ * the whole canvas), colors [n_inst,height,width,3] uint8 (pp_render_rgbd's rgb_u8 in scene order), scene_offsets as in
+ * pp_scene_gt_info (same checks, same codes).  A pixel with id k > 0 takes the colour of instance scene_offsets[s] + k - 1,
+ * any other pixel the background: background [n_scene,height,width,3] uint8 or, when that is NULL, the HOST constant
+ * bg_const [3].  Inputs are RGB; channel_order 0 writes RGB, 1 BGR (every pixel reversed).  out [n_scene,height,width,3]
+ * uint8.  Bytes are selected, never computed: byte-identical to its numpy restatement. */
+int pp_scene_compose_u8(pp_ctx* ctx, int n_inst, int n_scene, const int* scene_offsets_host, const int* scene_offsets_dev, int width,
+                        int height, const unsigned char* id_image, const unsigned char* colors, const unsigned char* background,
+                        const unsigned char* bg_const, int channel_order, unsigned char* out);
 /* reproj() of pose_error.py:179-207: mean over pts [n_pts,3] of the distance in pixels between K (R_est p + t_est) and
  * K (R_gt p + t_gt), each projection rounded to float32 and the norm taken in float32 as there (the mean is summed in float64:
  * within 1e-5 relative of the reference's float32 mean).  K9 [n_pose,3,3] row-major float64, the rest as pp_pose_add_f64;

@@ -27,6 +27,8 @@
 // VSD: pose_error.py:15-61 + 105-176 per problem on the rendered depth images, float64 where the reference is; per-block
 // partial counts / sums, then one ordered pass per problem.
 // Scene ground truth (at the end of the file): masks, boxes, pixel counts and the id image of a scene from its instances' renders.
+// Colour renderer (after the depth pass): shaded RGB, depth and triangle ids; a scene's image from its instances' colour renders
+// (at the end of the file).
 // Compiled with -ffp-contract=off: the host restatements (tests/render_np.py, utils/pose_error.py) evaluate the same
 // expressions in the same order.
 #include <limits.h>
@@ -324,6 +326,328 @@ extern "C" int pp_render_depth_f32(pp_ctx* ctx, int n_pose, int n_vert, const do
                      (const rvtx*)w.vtx, n_tri, width, height, tiles_x, n_tiles, (const int*)w.offsets, (const int*)w.list,
                      (const int*)w.big_n, (const int*)w.big, clip_near, clip_far, depth);
   PP_CHECK_LAUNCH(ctx, "pp_render_depth_f32");
+  return PP_OK;
+}
+
+// ---- colour renderer: shaded RGB, depth and triangle ids ------------------------------------------------------------------
+// The 'rgb' / 'rgb+depth' modes of utils/hodan_renderer.py (shaders :22-103, _draw_rgb :480-518) beside the depth pass, which
+// stays as it is.  Passes 1-4 are the depth pass's.  Then:
+//   4b. attributes: per (pose, vertex) the eye position P = R p + t, the normal N = R n normalised (phong) and the direction to
+//                   the light L = normalize(light - P), float64 (only when a colour output is asked for)
+//   5.  raster:     the tile's z-buffer holds 64-bit keys (bits of the positive float32 depth) << 32 | triangle index, resolved
+//                   with the 64-bit LDS integer minimum: the nearest fragment wins and, among fragments of equal float32 depth,
+//                   the smallest triangle index.  The key is a pure function of (triangle, pixel), so the image is the same bits
+//                   whatever order the lists and atomics run in, and the key's high word is the depth pass's value bit for bit.
+//                   The same workgroup then shades the resolved tile -- a thread owns the 4 pixels of a row it stores -- so no
+//                   id image goes through memory between raster and shade.
+// Shading rule (the reference's shaders restated in the OpenCV camera frame; tests/render_rgb_np.py evaluates the same
+// expressions in the same order): with the winning triangle's edge weights w_i as shade() computes them, q_i = w_i iz_i /
+// ((w0 iz0 + w1 iz1) + w2 iz2) and an attribute is a = (q0 a0 + q1 a1) + q2 a2.  c = interpolated vertex colour, l =
+// normalize(interp L); phong: n = normalize(interp N) (back-facing normals are not flipped: ambient light only); flat: n =
+// normalize((P1 - P0) x (P2 - P0)) with its sign chosen so that n . P0 < 0 (the shader's cross(dFdx, dFdy) faces the viewer
+// whatever the winding).  d = max(l . n, 0), 0 for a zero-length n or l; light_w = min(ambient + d, 1); out = (float)(light_w c);
+// uint8 = rintf(out * 255.0f) (np.round(rgb * 255).astype(np.uint8), :516).  No fragment: bg_color, id -1, depth 0.
+// Deviations: textures are not rendered; the 3-vector normal is normalised (the reference normalises u_nm * vec4(normal, 1)
+// over four components); light_cam_pos is in the OpenCV camera frame; parity with an OpenGL driver is unpinned.
+#define ZKEY_EMPTY 0xFFFFFFFFFFFFFFFFull
+
+struct __align__(8) rattr {
+  double P[3], N[3], L[3];
+};
+
+struct rgb_params {
+  double light[3], bg[3], ambient;
+  int phong;
+};
+
+// v / |v|, or 0 when the length is 0 (or not a number)
+__device__ __forceinline__ void normalize3(double x, double y, double z, double* o) {
+  const double len = sqrt((x * x + y * y) + z * z);
+  const bool ok = len > 0.0;
+  o[0] = ok ? x / len : 0.0;
+  o[1] = ok ? y / len : 0.0;
+  o[2] = ok ? z / len : 0.0;
+}
+
+__global__ void render_attr_kernel(int n_vert, const double* __restrict__ verts, const double* __restrict__ normals,
+                                   const double* __restrict__ R, const double* __restrict__ t, rgb_params prm, rattr* __restrict__ attr) {
+  const int pose = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_vert) return;
+  const double* r = R + 9 * pose;
+  const double* tt = t + 3 * pose;
+  const double px = verts[3 * i], py = verts[3 * i + 1], pz = verts[3 * i + 2];
+  rattr a;
+  a.P[0] = r[0] * px + r[1] * py + r[2] * pz + tt[0];
+  a.P[1] = r[3] * px + r[4] * py + r[5] * pz + tt[1];
+  a.P[2] = r[6] * px + r[7] * py + r[8] * pz + tt[2];
+  a.N[0] = a.N[1] = a.N[2] = 0.0;
+  if (prm.phong) {
+    const double nx = normals[3 * i], ny = normals[3 * i + 1], nz = normals[3 * i + 2];
+    normalize3(r[0] * nx + r[1] * ny + r[2] * nz, r[3] * nx + r[4] * ny + r[5] * nz, r[6] * nx + r[7] * ny + r[8] * nz, a.N);
+  }
+  normalize3(prm.light[0] - a.P[0], prm.light[1] - a.P[1], prm.light[2] - a.P[2], a.L);
+  attr[(size_t)pose * n_vert + i] = a;
+}
+
+__device__ __forceinline__ void raster_px(unsigned long long* zb, const tri_setup& T, int tri, int r, int c, int r0, int c0, double zn,
+                                          double zf) {
+  const float z = shade(T, r, c, zn, zf);
+  if (z > 0.0f) atomicMin(&zb[(r - r0) * RT + (c - c0)], ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)tri);
+}
+
+__device__ void raster_queue(unsigned long long* zb, const int* queue, int qn, const rvtx* vtx, int n_vert, const int* faces, int width,
+                             int height, int r0, int c0, double zn, double zf) {
+  for (int q = 0; q < qn; ++q) {
+    tri_setup T;
+    setup_triangle(vtx, n_vert, faces, queue[q], width, height, &T);  // queued triangles passed it already
+    const int a0 = max(T.c0, c0), a1 = min(T.c1, c0 + RT - 1), b0 = max(T.r0, r0), b1 = min(T.r1, r0 + RT - 1);
+    const int bw = a1 - a0 + 1, n = bw * (b1 - b0 + 1);
+    for (int k = threadIdx.x; k < n; k += RASTER_THREADS) raster_px(zb, T, queue[q], b0 + k / bw, a0 + k % bw, r0, c0, zn, zf);
+  }
+}
+
+// what shading needs of the triangle a pixel shows: kept while the thread's next pixel shows the same one
+struct tri_shading {
+  tri_setup T;
+  double L[3][3], N[3][3], C[3][3];  // per vertex; flat shading: N[0] is the face normal
+};
+
+__device__ void load_tri_shading(const rvtx* __restrict__ vtx, const rattr* __restrict__ attr, const double* __restrict__ colors,
+                                 int n_vert, const int* __restrict__ faces, int tri, int width, int height, int phong, tri_shading* S) {
+  setup_triangle(vtx, n_vert, faces, tri, width, height, &S->T);  // the triangle won a pixel: it passed already
+  double P[3][3];
+  for (int v = 0; v < 3; ++v) {
+    const int i = faces[3 * tri + v];
+    const rattr* a = attr + i;
+    for (int k = 0; k < 3; ++k) {
+      P[v][k] = a->P[k];
+      S->L[v][k] = a->L[k];
+      S->N[v][k] = a->N[k];
+      S->C[v][k] = colors[3 * (size_t)i + k];
+    }
+  }
+  if (!phong) {
+    const double ux = P[1][0] - P[0][0], uy = P[1][1] - P[0][1], uz = P[1][2] - P[0][2];
+    const double vx = P[2][0] - P[0][0], vy = P[2][1] - P[0][1], vz = P[2][2] - P[0][2];
+    double* n = S->N[0];
+    normalize3(uy * vz - uz * vy, uz * vx - ux * vz, ux * vy - uy * vx, n);
+    if ((n[0] * P[0][0] + n[1] * P[0][1]) + n[2] * P[0][2] > 0.0) {
+      n[0] = -n[0];
+      n[1] = -n[1];
+      n[2] = -n[2];
+    }
+  }
+}
+
+__device__ __forceinline__ void shade_rgb_px(const tri_shading& S, int r, int c, const rgb_params& prm, float* out) {
+  const tri_setup& T = S.T;
+  const double px = c + 0.5, py = r + 0.5;
+  const double w0 = T.s * edge_fn(T.x[1], T.y[1], T.x[2], T.y[2], px, py);
+  const double w1 = T.s * edge_fn(T.x[2], T.y[2], T.x[0], T.y[0], px, py);
+  const double w2 = T.s * edge_fn(T.x[0], T.y[0], T.x[1], T.y[1], px, py);
+  const double b0 = w0 * T.iz[0], b1 = w1 * T.iz[1], b2 = w2 * T.iz[2];
+  const double den = (b0 + b1) + b2;
+  const double q0 = b0 / den, q1 = b1 / den, q2 = b2 / den;
+  double l[3], n[3];
+  normalize3((q0 * S.L[0][0] + q1 * S.L[1][0]) + q2 * S.L[2][0], (q0 * S.L[0][1] + q1 * S.L[1][1]) + q2 * S.L[2][1],
+             (q0 * S.L[0][2] + q1 * S.L[1][2]) + q2 * S.L[2][2], l);
+  if (prm.phong) {
+    normalize3((q0 * S.N[0][0] + q1 * S.N[1][0]) + q2 * S.N[2][0], (q0 * S.N[0][1] + q1 * S.N[1][1]) + q2 * S.N[2][1],
+               (q0 * S.N[0][2] + q1 * S.N[1][2]) + q2 * S.N[2][2], n);
+  } else {
+    n[0] = S.N[0][0];
+    n[1] = S.N[0][1];
+    n[2] = S.N[0][2];
+  }
+  const double dot = (l[0] * n[0] + l[1] * n[1]) + l[2] * n[2];
+  const double d = dot > 0.0 ? dot : 0.0;
+  const double sum = prm.ambient + d;
+  const double light_w = sum > 1.0 ? 1.0 : sum;
+  for (int k = 0; k < 3; ++k) out[k] = (float)(light_w * ((q0 * S.C[0][k] + q1 * S.C[1][k]) + q2 * S.C[2][k]));
+}
+
+__device__ __forceinline__ unsigned char rgb_to_u8(float v) { return (unsigned char)fminf(fmaxf(rintf(v * 255.0f), 0.0f), 255.0f); }
+
+__global__ void __launch_bounds__(RASTER_THREADS)
+render_rgbd_raster_kernel(int n_vert, const int* __restrict__ faces, const rvtx* __restrict__ vtx_all, int n_tri, int width, int height,
+                          int tiles_x, int n_tiles, const int* __restrict__ offsets, const int* __restrict__ list,
+                          const int* __restrict__ big_n, const int* __restrict__ big, double zn, double zf,
+                          const rattr* __restrict__ attr_all, const double* __restrict__ colors, rgb_params prm, float* __restrict__ depth,
+                          int* __restrict__ tri_id, float* __restrict__ rgb_f32, unsigned char* __restrict__ rgb_u8) {
+  __shared__ unsigned long long zb[RT * RT];
+  __shared__ int queue[RASTER_THREADS];
+  __shared__ int qn;
+  const int pose = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
+  const int r0 = (tile / tiles_x) * RT, c0 = (tile % tiles_x) * RT;
+  const rvtx* vtx = vtx_all + (size_t)pose * n_vert;
+  for (int k = tid; k < RT * RT; k += RASTER_THREADS) zb[k] = ZKEY_EMPTY;
+  if (tid == 0) qn = 0;
+  __syncthreads();
+  const size_t b = (size_t)pose * n_tiles + tile;
+  const int l0 = offsets[b], l1 = offsets[b + 1];
+  for (int base = l0; base < l1; base += RASTER_THREADS) {
+    if (base + tid < l1) {
+      const int tri = list[base + tid];
+      tri_setup T;
+      if (setup_triangle(vtx, n_vert, faces, tri, width, height, &T)) {
+        const int a0 = max(T.c0, c0), a1 = min(T.c1, c0 + RT - 1), b0 = max(T.r0, r0), b1 = min(T.r1, r0 + RT - 1);
+        const int area = (a1 - a0 + 1) * (b1 - b0 + 1);
+        if (a0 <= a1 && b0 <= b1) {
+          if (area <= RASTER_SMALL_PX) {
+            for (int r = b0; r <= b1; ++r)
+              for (int c = a0; c <= a1; ++c) raster_px(zb, T, tri, r, c, r0, c0, zn, zf);
+          } else {
+            queue[atomicAdd(&qn, 1)] = tri;
+          }
+        }
+      }
+    }
+    __syncthreads();
+    raster_queue(zb, queue, qn, vtx, n_vert, faces, width, height, r0, c0, zn, zf);
+    __syncthreads();
+    if (tid == 0) qn = 0;
+    __syncthreads();
+  }
+  const int nb = big_n[pose];
+  for (int base = 0; base < nb; base += RASTER_THREADS) {
+    if (base + tid < nb) {
+      const int tri = big[(size_t)pose * n_tri + base + tid];
+      tri_setup T;
+      if (setup_triangle(vtx, n_vert, faces, tri, width, height, &T) && T.c0 < c0 + RT && T.c1 >= c0 && T.r0 < r0 + RT && T.r1 >= r0)
+        queue[atomicAdd(&qn, 1)] = tri;
+    }
+    __syncthreads();
+    raster_queue(zb, queue, qn, vtx, n_vert, faces, width, height, r0, c0, zn, zf);
+    __syncthreads();
+    if (tid == 0) qn = 0;
+    __syncthreads();
+  }
+  // the tile, 4 pixels of one row per thread
+  const int r = r0 + tid / (RT / 4), c = c0 + (tid % (RT / 4)) * 4;
+  if (r >= height || c >= width) return;
+  float z[4];
+  int id[4];
+  for (int k = 0; k < 4; ++k) {
+    const unsigned long long key = zb[(tid / (RT / 4)) * RT + (tid % (RT / 4)) * 4 + k];
+    const unsigned hi = (unsigned)(key >> 32);
+    const bool hit = hi < 0x7F800000u;  // a depth that rounded to +inf is no fragment, as in the depth pass
+    z[k] = hit ? __uint_as_float(hi) : 0.0f;
+    id[k] = hit ? (int)(unsigned)key : -1;
+  }
+  const size_t px0 = ((size_t)pose * height + r) * width + c;
+  const bool full = (width & 3) == 0;  // then c + 3 < width and px0 is a multiple of 4
+  if (depth) {
+    if (full && (reinterpret_cast<uintptr_t>(depth) & 15u) == 0) {
+      *(float4*)(depth + px0) = make_float4(z[0], z[1], z[2], z[3]);
+    } else {
+      for (int k = 0; k < 4; ++k)
+        if (c + k < width) depth[px0 + k] = z[k];
+    }
+  }
+  if (tri_id) {
+    if (full && (reinterpret_cast<uintptr_t>(tri_id) & 15u) == 0) {
+      *(int4*)(tri_id + px0) = make_int4(id[0], id[1], id[2], id[3]);
+    } else {
+      for (int k = 0; k < 4; ++k)
+        if (c + k < width) tri_id[px0 + k] = id[k];
+    }
+  }
+  if (!rgb_f32 && !rgb_u8) return;
+  float v[12];
+  tri_shading S;
+  int held = -1;
+  for (int k = 0; k < 4; ++k) {
+    if (id[k] < 0) {
+      for (int j = 0; j < 3; ++j) v[3 * k + j] = (float)prm.bg[j];
+      continue;
+    }
+    if (id[k] != held) {
+      held = id[k];
+      load_tri_shading(vtx, attr_all + (size_t)pose * n_vert, colors, n_vert, faces, held, width, height, prm.phong, &S);
+    }
+    shade_rgb_px(S, r, c + k, prm, v + 3 * k);
+  }
+  if (rgb_f32) {
+    float* o = rgb_f32 + 3 * px0;
+    if (full && (reinterpret_cast<uintptr_t>(rgb_f32) & 15u) == 0) {
+      for (int j = 0; j < 3; ++j) ((float4*)o)[j] = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
+    } else {
+      for (int k = 0; k < 12; ++k)
+        if (c + k / 3 < width) o[k] = v[k];
+    }
+  }
+  if (rgb_u8) {
+    unsigned char* o = rgb_u8 + 3 * px0;
+    unsigned char u[12];
+    for (int k = 0; k < 12; ++k) u[k] = rgb_to_u8(v[k]);
+    if (full && (reinterpret_cast<uintptr_t>(rgb_u8) & 3u) == 0) {
+      for (int j = 0; j < 3; ++j)
+        ((unsigned*)o)[j] = (unsigned)u[4 * j] | ((unsigned)u[4 * j + 1] << 8) | ((unsigned)u[4 * j + 2] << 16) | ((unsigned)u[4 * j + 3] << 24);
+    } else {
+      for (int k = 0; k < 12; ++k)
+        if (c + k / 3 < width) o[k] = u[k];
+    }
+  }
+}
+
+static size_t render_rgbd_layout(int n_pose, int n_vert, int n_tri, int width, int height, char* base, render_ws* w, rattr** attr) {
+  const size_t head = render_layout(n_pose, n_vert, n_tri, width, height, base, w);
+  if (attr) *attr = (rattr*)(base + head);
+  return head + pp_align256((size_t)n_pose * n_vert * sizeof(rattr));
+}
+
+extern "C" size_t pp_render_rgbd_workspace_bytes(int n_pose, int n_vert, int n_tri, int width, int height) {
+  if (!render_shape_ok(n_pose, n_vert, n_tri, width, height)) return 0;
+  return render_rgbd_layout(n_pose, n_vert, n_tri, width, height, nullptr, nullptr, nullptr);
+}
+
+extern "C" int pp_render_rgbd(pp_ctx* ctx, int n_pose, int n_vert, const double* verts, const double* colors, const double* normals,
+                              int n_tri, const int* faces, const double* R, const double* t, const double* K4, int width, int height,
+                              double clip_near, double clip_far, int shading, double ambient_weight, const double* light_cam_pos,
+                              const double* bg_color, void* workspace, size_t workspace_bytes, float* depth, int* tri_id,
+                              float* rgb_f32, unsigned char* rgb_u8) {
+  PP_REQUIRE_CTX(ctx);
+  PP_CHECK_ARG(ctx, render_shape_ok(n_pose, n_vert, n_tri, width, height), PP_ERR_SHAPE,
+               "pp_render_rgbd: need 1..65535 poses, vertices, triangles, a 1..16384 image and n_pose * n_tri * 4 < 2^31");
+  PP_CHECK_ARG(ctx, verts && faces && R && t && K4 && workspace && light_cam_pos && bg_color, PP_ERR_ARG, "pp_render_rgbd: null argument");
+  PP_CHECK_ARG(ctx, depth || tri_id || rgb_f32 || rgb_u8, PP_ERR_ARG, "pp_render_rgbd: no output requested");
+  const bool rgb = rgb_f32 || rgb_u8;
+  PP_CHECK_ARG(ctx, shading == 0 || shading == 1, PP_ERR_ARG, "pp_render_rgbd: shading must be 0 (flat) or 1 (phong)");
+  PP_CHECK_ARG(ctx, !rgb || colors, PP_ERR_ARG, "pp_render_rgbd: a colour output needs vertex colours");
+  PP_CHECK_ARG(ctx, !rgb || shading == 0 || normals, PP_ERR_ARG, "pp_render_rgbd: phong shading needs vertex normals");
+  PP_CHECK_ARG(ctx, clip_near >= 0.0 && clip_far >= clip_near, PP_ERR_ARG, "pp_render_rgbd: need 0 <= clip_near <= clip_far");
+  PP_CHECK_ARG(ctx, ambient_weight >= 0.0 && ambient_weight <= 1.0, PP_ERR_ARG, "pp_render_rgbd: ambient_weight must lie in [0, 1]");
+  rgb_params prm;
+  for (int k = 0; k < 3; ++k) {
+    PP_CHECK_ARG(ctx, isfinite(light_cam_pos[k]), PP_ERR_ARG, "pp_render_rgbd: light_cam_pos must be finite");
+    PP_CHECK_ARG(ctx, bg_color[k] >= 0.0 && bg_color[k] <= 1.0, PP_ERR_ARG, "pp_render_rgbd: bg_color must lie in [0, 1]");
+    prm.light[k] = light_cam_pos[k];
+    prm.bg[k] = bg_color[k];
+  }
+  prm.ambient = ambient_weight;
+  prm.phong = shading;
+  render_ws w;
+  rattr* attr = nullptr;
+  const size_t need = render_rgbd_layout(n_pose, n_vert, n_tri, width, height, (char*)workspace, &w, &attr);
+  PP_CHECK_ARG(ctx, workspace_bytes >= need, PP_ERR_ARG, "pp_render_rgbd: workspace of %zu bytes, need %zu", workspace_bytes, need);
+  const int tiles_x = (width + RT - 1) / RT, n_tiles = tiles_x * ((height + RT - 1) / RT);
+  const size_t nb = (size_t)n_pose * n_tiles;
+  hipMemsetAsync(w.counts, 0, nb * sizeof(int), ctx->stream);
+  hipMemsetAsync(w.big_n, 0, (size_t)n_pose * sizeof(int), ctx->stream);
+  const dim3 vg((n_vert + 255) / 256, n_pose);
+  hipLaunchKernelGGL(render_vertex_kernel, vg, dim3(256), 0, ctx->stream, n_vert, verts, R, t, K4, w.vtx);
+  if (rgb) hipLaunchKernelGGL(render_attr_kernel, vg, dim3(256), 0, ctx->stream, n_vert, verts, normals, R, t, prm, attr);
+  const dim3 tg((n_tri + 255) / 256, n_pose);
+  hipLaunchKernelGGL(render_bin_kernel, tg, dim3(256), 0, ctx->stream, 0, n_vert, n_tri, faces, (const rvtx*)w.vtx, width, height,
+                     tiles_x, n_tiles, w.counts, w.cursor, w.list, w.big_n, w.big);
+  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, (int)nb, (const int*)w.counts, w.offsets, w.cursor);
+  hipLaunchKernelGGL(render_bin_kernel, tg, dim3(256), 0, ctx->stream, 1, n_vert, n_tri, faces, (const rvtx*)w.vtx, width, height,
+                     tiles_x, n_tiles, w.counts, w.cursor, w.list, w.big_n, w.big);
+  hipLaunchKernelGGL(render_rgbd_raster_kernel, dim3(n_tiles, n_pose), dim3(RASTER_THREADS), 0, ctx->stream, n_vert, faces,
+                     (const rvtx*)w.vtx, n_tri, width, height, tiles_x, n_tiles, (const int*)w.offsets, (const int*)w.list,
+                     (const int*)w.big_n, (const int*)w.big, clip_near, clip_far, (const rattr*)attr, colors, prm, depth, tri_id, rgb_f32,
+                     rgb_u8);
+  PP_CHECK_LAUNCH(ctx, "pp_render_rgbd");
   return PP_OK;
 }
 
@@ -932,5 +1256,80 @@ extern "C" int pp_scene_gt_info(pp_ctx* ctx, int n_inst, int n_scene, const int*
   hipLaunchKernelGGL(scene_gt_final_kernel, dim3(n_inst), dim3(64), 0, ctx->stream, (int)nblk, (const int*)workspace, px_count, bbox_obj,
                      bbox_visib);
   PP_CHECK_LAUNCH(ctx, "pp_scene_gt_info");
+  return PP_OK;
+}
+
+// ---- a scene's image from its instances' colour renders ---------------------------------------------------------------------
+// Per (scene, pixel): id k > 0 of pp_scene_gt_info's id image selects the colour of instance scene_offsets[scene] + k - 1 of
+// the uint8 stack (pp_render_rgbd outputs in scene order), anything else the background -- the scene's image or a constant.
+// Inputs are RGB; the output is RGB or, reversed per pixel, BGR.  A thread owns four pixels of a row (one packed load of the
+// ids, three packed stores where the addresses allow).  Bytes are selected, never computed.
+__global__ void __launch_bounds__(SGT_THREADS)
+scene_compose_kernel(int n_inst, int width, int height, const int* __restrict__ scene_offsets, const unsigned char* __restrict__ id_image,
+                     const unsigned char* __restrict__ colors, const unsigned char* __restrict__ background, unsigned bg_const, int bgr,
+                     unsigned char* __restrict__ out) {
+  const int groups = (width + 3) / 4, gi = blockIdx.x * SGT_THREADS + threadIdx.x, scene = blockIdx.y;
+  if (gi >= height * groups) return;
+  const int r = gi / groups, c0 = (gi - r * groups) * 4;
+  int i0, i1;
+  scene_range(scene_offsets, scene, n_inst, &i0, &i1);
+  const size_t hw = (size_t)width * height, p0 = (size_t)r * width + c0;
+  const unsigned char* ids = id_image + scene * hw + p0;
+  const bool whole = c0 + 3 < width;
+  unsigned packed = 0;
+  if (whole && (reinterpret_cast<uintptr_t>(ids) & 3u) == 0) {
+    packed = *reinterpret_cast<const unsigned*>(ids);
+  } else {
+    for (int k = 0; k < 4; ++k)
+      if (c0 + k < width) packed |= (unsigned)ids[k] << (8 * k);
+  }
+  unsigned char v[12];
+  for (int k = 0; k < 4; ++k) {
+    const int id = (int)((packed >> (8 * k)) & 255u);
+    const unsigned char* src = nullptr;
+    if (c0 + k < width) {
+      if (id > 0 && id <= i1 - i0)
+        src = colors + ((size_t)(i0 + id - 1) * hw + p0 + k) * 3;
+      else if (background)
+        src = background + (scene * hw + p0 + k) * 3;
+    }
+    for (int j = 0; j < 3; ++j) {
+      const int jj = bgr ? 2 - j : j;
+      v[3 * k + j] = src ? src[jj] : (unsigned char)((bg_const >> (8 * jj)) & 255u);
+    }
+  }
+  unsigned char* o = out + (scene * hw + p0) * 3;
+  if (whole && (reinterpret_cast<uintptr_t>(o) & 3u) == 0) {
+    for (int j = 0; j < 3; ++j)
+      reinterpret_cast<unsigned*>(o)[j] = (unsigned)v[4 * j] | ((unsigned)v[4 * j + 1] << 8) | ((unsigned)v[4 * j + 2] << 16) | ((unsigned)v[4 * j + 3] << 24);
+  } else {
+    for (int k = 0; k < 12; ++k)
+      if (c0 + k / 3 < width) o[k] = v[k];
+  }
+}
+
+extern "C" int pp_scene_compose_u8(pp_ctx* ctx, int n_inst, int n_scene, const int* scene_offsets_host, const int* scene_offsets_dev,
+                                   int width, int height, const unsigned char* id_image, const unsigned char* colors,
+                                   const unsigned char* background, const unsigned char* bg_const, int channel_order,
+                                   unsigned char* out) {
+  PP_REQUIRE_CTX(ctx);
+  PP_CHECK_ARG(ctx, scene_gt_shape_ok(n_inst, width, height) && n_scene > 0 && n_scene <= 65535, PP_ERR_SHAPE,
+               "pp_scene_compose_u8: need 1..65535 instances, 1..65535 scenes and a 1..16384 image");
+  PP_CHECK_ARG(ctx, scene_offsets_host && scene_offsets_dev && id_image && colors && out && (background || bg_const), PP_ERR_ARG,
+               "pp_scene_compose_u8: null argument (give a background image or a constant)");
+  PP_CHECK_ARG(ctx, channel_order == 0 || channel_order == 1, PP_ERR_ARG, "pp_scene_compose_u8: channel_order must be 0 (RGB) or 1 (BGR)");
+  PP_CHECK_ARG(ctx, scene_offsets_host[0] == 0 && scene_offsets_host[n_scene] == n_inst, PP_ERR_ARG,
+               "pp_scene_compose_u8: scene_offsets must run from 0 to n_inst");
+  for (int s = 0; s < n_scene; ++s) {
+    const int m = scene_offsets_host[s + 1] - scene_offsets_host[s];
+    PP_CHECK_ARG(ctx, m >= 0, PP_ERR_ARG, "pp_scene_compose_u8: scene_offsets must not decrease (scene %d)", s);
+    PP_CHECK_ARG(ctx, m <= SGT_MAX_PER_SCENE, PP_ERR_SHAPE, "pp_scene_compose_u8: scene %d has %d instances, the uint8 id image holds %d",
+                 s, m, SGT_MAX_PER_SCENE);
+  }
+  const unsigned bg = background ? 0u : (unsigned)bg_const[0] | ((unsigned)bg_const[1] << 8) | ((unsigned)bg_const[2] << 16);
+  const int blocks = (int)((((size_t)width + 3) / 4 * height + SGT_THREADS - 1) / SGT_THREADS);
+  hipLaunchKernelGGL(scene_compose_kernel, dim3(blocks, n_scene), dim3(SGT_THREADS), 0, ctx->stream, n_inst, width, height,
+                     scene_offsets_dev, id_image, colors, background, bg, channel_order, out);
+  PP_CHECK_LAUNCH(ctx, "pp_scene_compose_u8");
   return PP_OK;
 }

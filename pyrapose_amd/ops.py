@@ -786,6 +786,43 @@ def render_depth(ctx, verts, faces, R, t, K4, width, height, clip_near=100.0, cl
     return out
 
 
+RENDER_SHADING = {"flat": 0, "phong": 1}
+RENDER_OUTPUTS = {"depth": _F32, "tri_id": _I32, "rgb_f32": _F32, "rgb": _U8}  # in the ABI's order
+
+
+def render_rgbd(ctx, verts, faces, R, t, K4, width, height, colors=None, normals=None, clip_near=100.0, clip_far=10000.0,
+                shading="phong", ambient_weight=0.5, light_cam_pos=(0.0, 0.0, 0.0), bg_color=(0.0, 0.0, 0.0), outputs=("rgb", "depth")):
+    """Shaded colour, depth and triangle ids of one mesh at n poses (pp_render_rgbd): cuda tensors as in render_depth plus
+    colors float64 [n_vert,3] in [0, 1] (needed for 'rgb' / 'rgb_f32') and normals float64 [n_vert,3] (needed for phong
+    shading); shading 'flat' | 'phong'; light_cam_pos in the OpenCV camera frame; outputs: any of 'rgb' (uint8 [n,h,w,3], RGB),
+    'rgb_f32' (float32 [n,h,w,3]), 'depth' (float32 [n,h,w], the bits of render_depth), 'tri_id' (int32 [n,h,w], -1 = none)
+    -> dict of the requested outputs."""
+    if shading not in RENDER_SHADING:
+        raise ValueError("render_rgbd: unknown shading %r (flat | phong)" % (shading,))
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    unknown = [o for o in outputs if o not in RENDER_OUTPUTS]
+    if unknown or not outputs:
+        raise ValueError("render_rgbd: outputs must name at least one of %s, got %r" % (" | ".join(RENDER_OUTPUTS), outputs))
+    verts = _arg("render_rgbd", "verts", verts, _F64, (None, 3))
+    faces = _arg("render_rgbd", "faces", faces, _I32, (None, 3))
+    R = _arg("render_rgbd", "R", R, _F64, (None, 3, 3))
+    n, nv, nt = int(R.shape[0]), int(verts.shape[0]), int(faces.shape[0])
+    t = _arg("render_rgbd", "t", t, _F64, (n, 3))
+    K4 = _arg("render_rgbd", "K4", K4, _F64, (n, 4))
+    colors = _arg("render_rgbd", "colors", colors, _F64, (nv, 3), optional=True)
+    normals = _arg("render_rgbd", "normals", normals, _F64, (nv, 3), optional=True)
+    light = (C.c_double * 3)(*(float(v) for v in np.asarray(light_cam_pos, np.float64).reshape(3)))
+    bg = (C.c_double * 3)(*(float(v) for v in np.asarray(bg_color, np.float64).reshape(3)))
+    nbytes = lib.pp_render_rgbd_workspace_bytes(n, nv, nt, int(width), int(height))
+    ws = _workspace(nbytes, "render_rgbd: unsupported shape (n=%d, vertices=%d, triangles=%d, %dx%d)" % (n, nv, nt, width, height))
+    out = {k: _out(verts, (n, int(height), int(width)) + ((3,) if k.startswith("rgb") else ()), dt)
+           for k, dt in RENDER_OUTPUTS.items() if k in outputs}
+    check(lib.pp_render_rgbd(ctx.handle, n, nv, _ptr(verts), _ptr(colors), _ptr(normals), nt, _ptr(faces), _ptr(R), _ptr(t), _ptr(K4),
+                             int(width), int(height), float(clip_near), float(clip_far), RENDER_SHADING[shading], float(ambient_weight),
+                             light, bg, _ptr(ws), nbytes, *[_ptr(out.get(k)) for k in RENDER_OUTPUTS]), ctx.handle, "pp_render_rgbd")
+    return out
+
+
 VSD_COSTS = {"step": 0, "tlinear": 1}
 
 
@@ -869,6 +906,38 @@ def scene_gt_info(ctx, depth_stack, scene_offsets, K4, depth_test=None, delta=15
                                _ptr(K4), _ptr(dt), 0 if shared else h * w, float(delta), _ptr(ws), nbytes, _ptr(out.scene_depth),
                                _ptr(out.id_image), _ptr(out.px_count), _ptr(out.bbox_obj), _ptr(out.bbox_visib), _ptr(out.mask_full),
                                _ptr(out.mask_visib)), ctx.handle, "pp_scene_gt_info")
+    return out
+
+
+CHANNEL_ORDERS = {"rgb": 0, "bgr": 1}
+
+
+def scene_compose(ctx, id_image, colors, scene_offsets, background=(0, 0, 0), channel_order="bgr"):
+    """The images of S scenes from their instances' colour renders (pp_scene_compose_u8): cuda uint8 id_image [S,h,w]
+    (scene_gt_info's, whole canvas), colors [n,h,w,3] (render_rgbd's 'rgb' in scene order), scene_offsets as in scene_gt_info;
+    background: a cuda uint8 tensor [S,h,w,3] or three HOST values 0 ... 255 (RGB, as the colours); channel_order of the
+    result 'rgb' | 'bgr' -> cuda uint8 [S,h,w,3]."""
+    if channel_order not in CHANNEL_ORDERS:
+        raise ValueError("scene_compose: unknown channel order %r (rgb | bgr)" % (channel_order,))
+    ids = _arg("scene_compose", "id_image", id_image, _U8, (None, None, None))
+    S, h, w = (int(s) for s in ids.shape)
+    colors = _arg("scene_compose", "colors", colors, _U8, (None, h, w, 3))
+    n = int(colors.shape[0])
+    off = np.ascontiguousarray(np.asarray(scene_offsets).reshape(-1), np.int32)
+    if off.size != S + 1 or not np.array_equal(off, np.asarray(scene_offsets).reshape(-1)):
+        raise ValueError("scene_compose: scene_offsets must hold S+1 = %d integers" % (S + 1))
+    bg_image, bg_const = None, None
+    if torch.is_tensor(background):
+        bg_image = _arg("scene_compose", "background", background, _U8, (S, h, w, 3))
+    else:
+        bg = np.asarray(background).reshape(-1)
+        if bg.size != 3 or not np.array_equal(bg, bg.astype(np.uint8)):
+            raise ValueError("scene_compose: a constant background is three values 0 ... 255")
+        bg_const = (C.c_ubyte * 3)(*(int(v) for v in bg))
+    out = _out(ids, (S, h, w, 3), _U8)
+    off_dev = torch.from_numpy(off).to(ids.device)
+    check(lib.pp_scene_compose_u8(ctx.handle, n, S, off.ctypes.data_as(C.POINTER(C.c_int)), _ptr(off_dev), w, h, _ptr(ids), _ptr(colors),
+                                  _ptr(bg_image), bg_const, CHANNEL_ORDERS[channel_order], _ptr(out)), ctx.handle, "pp_scene_compose_u8")
     return out
 
 

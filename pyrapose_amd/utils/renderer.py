@@ -1,7 +1,12 @@
-"""Depth rendering of a triangle mesh on the device, in place of the OpenGL depth pass of utils/hodan_renderer.py that the
-reference's vsd() calls as render(model, im_size, K, R, t, clip_near=100, clip_far=10000, mode='depth')
+"""Rendering of a triangle mesh on the device, in place of the OpenGL passes of utils/hodan_renderer.py.
+Depth: what the reference's vsd() calls as render(model, im_size, K, R, t, clip_near=100, clip_far=10000, mode='depth')
 (utils/pose_error.py:124-128).  Pixel (r, c) holds the camera-frame Z of the nearest surface point through (c + 0.5, r + 0.5)
-in OpenCV pixel coordinates, 0 where the mesh does not cover it (csrc/render.hip).  Only mode='depth' exists."""
+in OpenCV pixel coordinates, 0 where the mesh does not cover it (csrc/render.hip).  render() has only mode='depth'.
+Colour: render_rgbd_batch / render_object give the renderer's 'rgb' and 'rgb+depth' modes (flat or phong shaded vertex
+colours, :22-103, :309-352, :473-518) from pp_render_rgbd.  Textures are not rendered; light_cam_pos is given in the OpenCV
+camera frame; the defaults ambient_weight=0.5 and a light at the camera origin are those of bop_toolkit's renderer base
+class, which is not part of the reference checkout; parity with an OpenGL driver is unpinned (tests/render_rgb_np.py
+restates the shading rule)."""
 import numpy as np
 import torch
 
@@ -41,3 +46,74 @@ def render(model, im_size, K, R, t, clip_near=100, clip_far=10000, mode="depth",
     if mode != "depth":
         raise ValueError("render: only mode='depth' is implemented (got %r)" % (mode,))
     return render_depth_batch(model, im_size, K, R, t, clip_near, clip_far)[0].cpu().numpy()
+
+
+RGBD_OUTPUTS = ("rgb", "rgb_f32", "depth", "tri_id")
+
+
+def _colors(model, n_vert, surf_color):
+    """vertex colours as hodan_renderer.py:309-352 picks them: surf_color, else model['colors'] (divided by 255 when its
+    maximum exceeds 1), else grey 0.5 -> float64 [n_vert,3] in [0, 1]"""
+    if surf_color is not None:
+        c = np.asarray(surf_color, np.float64).reshape(-1)
+        if c.size != 3:
+            raise ValueError("surf_color must hold 3 values, got %d" % c.size)
+        colors = np.tile(c, (n_vert, 1))
+    elif "texture_file" in model:
+        raise ValueError("render_rgbd_batch: the model has a texture, and textures are not rendered: give surf_color")
+    elif "colors" in model:
+        colors = np.array(model["colors"], np.float64)
+        if colors.ndim != 2 or colors.shape[0] != n_vert or colors.shape[1] < 3:
+            raise ValueError("model['colors'] must be %d x 3, got %s" % (n_vert, colors.shape))
+        colors = colors[:, :3]
+        if colors.size and colors.max() > 1.0:
+            colors = colors / 255.0
+    else:
+        colors = np.full((n_vert, 3), 0.5)
+    if not (np.isfinite(colors).all() and colors.min() >= 0.0 and colors.max() <= 1.0):
+        raise ValueError("vertex colours must lie in [0, 1] (or in [0, 255])")
+    return np.ascontiguousarray(colors)
+
+
+def render_rgbd_batch(model, im_size, K, R, t, clip_near=100, clip_far=10000, shading="phong", ambient_weight=0.5,
+                      light_cam_pos=(0, 0, 0), surf_color=None, bg_color=(0, 0, 0), outputs=("rgb", "depth"), ctx=None):
+    """n poses of one mesh in one launch: model dict ('pts', 'faces', optionally 'colors' [n_v,3] and 'normals' [n_v,3]),
+    im_size (w, h), K 3x3 or [n,3,3], R [n,3,3], t [n,3]; shading 'phong' (needs model['normals']) or 'flat'; light_cam_pos in
+    the OpenCV camera frame; outputs: any of 'rgb' (uint8 [n,h,w,3], RGB), 'rgb_f32' (float32), 'depth' (float32 [n,h,w]),
+    'tri_id' (int32 [n,h,w], -1 = none) -> dict of cuda tensors."""
+    w, h = (int(v) for v in im_size)
+    pts, faces = _mesh(model)
+    if shading not in ops.RENDER_SHADING:
+        raise ValueError("render_rgbd_batch: unknown shading %r (flat | phong)" % (shading,))
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    if not outputs or any(o not in RGBD_OUTPUTS for o in outputs):
+        raise ValueError("render_rgbd_batch: outputs must name at least one of %s, got %r" % (" | ".join(RGBD_OUTPUTS), outputs))
+    colors = normals = None
+    if any(o.startswith("rgb") for o in outputs):
+        colors = _colors(model, pts.shape[0], surf_color)
+        if shading == "phong":
+            if model.get("normals") is None:
+                raise ValueError("render_rgbd_batch: shading='phong' needs model['normals'] (use shading='flat' without them)")
+            normals = np.asarray(model["normals"], np.float64)
+            if normals.shape != pts.shape:
+                raise ValueError("model['normals'] must be %d x 3, got %s" % (pts.shape[0], normals.shape))
+    R = np.asarray(R, np.float64).reshape(-1, 3, 3)
+    n = R.shape[0]
+    dev = lambda a: None if a is None else to_device(a)
+    return ops.render_rgbd(ctx or default_context(), to_device(pts), to_device(faces, torch.int32), to_device(R), to_device(t, shape=(n, 3)),
+                           to_device(k4(K, n)), w, h, dev(colors), dev(normals), float(clip_near), float(clip_far), shading,
+                           float(ambient_weight), light_cam_pos, bg_color, outputs)
+
+
+RENDER_MODES = {"rgb": ("rgb",), "depth": ("depth",), "rgb+depth": ("rgb", "depth")}
+
+
+def render_object(model, im_size, K, R, t, mode="rgb+depth", clip_near=100, clip_far=10000, shading="phong", ambient_weight=0.5,
+                  light_cam_pos=(0, 0, 0), surf_color=None, bg_color=(0, 0, 0)):
+    """One pose of one mesh, as the reference's RendererPython.render_object returns it for the renderer's mode
+    (hodan_renderer.py:473-478): {'rgb': uint8 [h,w,3]} | {'depth': float32 [h,w]} | both, numpy arrays."""
+    if mode not in RENDER_MODES:
+        raise ValueError("render_object: unknown mode %r (rgb | depth | rgb+depth)" % (mode,))
+    out = render_rgbd_batch(model, im_size, K, np.asarray(R, np.float64).reshape(1, 3, 3), np.asarray(t, np.float64).reshape(1, 3),
+                            clip_near, clip_far, shading, ambient_weight, light_cam_pos, surf_color, bg_color, RENDER_MODES[mode])
+    return {k: v[0].cpu().numpy() for k, v in out.items()}

@@ -75,6 +75,20 @@ def _scene_depth(depth, n_scene, im_size):
     return None, w, h
 
 
+def _info(plan, out):
+    """the counts and boxes of ops.scene_gt_info -> per scene a list of dicts with the keys of BOP's scene_gt_info.json"""
+    counts, box_obj, box_visib = (a.cpu().numpy() for a in (out.px_count, out.bbox_obj, out.bbox_visib))
+    info = []
+    for s in range(len(plan.scene_offsets) - 1):
+        rows = []
+        for i in range(plan.scene_offsets[s], plan.scene_offsets[s + 1]):
+            n_all, n_valid, n_visib = (int(v) for v in counts[i])
+            rows.append({"bbox_obj": [int(v) for v in box_obj[i]], "bbox_visib": [int(v) for v in box_visib[i]], "px_count_all": n_all,
+                         "px_count_valid": n_valid, "px_count_visib": n_visib, "visib_fract": n_visib / float(n_all) if n_all > 0 else 0.0})
+        info.append(rows)
+    return info
+
+
 def scene_gt_info(scenes, models, K, depth=None, im_size=None, delta=15.0, extent="image", masks=False, clip_near=100,
                   clip_far=10000):
     """Ground truth of S images from the meshes and poses of their instances.  scenes: see plan_instances; models: obj_id ->
@@ -122,19 +136,73 @@ def scene_gt_info(scenes, models, K, depth=None, im_size=None, delta=15.0, exten
     stack = torch.cat(renders)[torch.from_numpy(plan.order).to(renders[0].device)] if len(renders) > 1 else renders[0]
     out = ops.scene_gt_info(ctx, stack, plan.scene_offsets, to_device(k4(K_inst, n)), None if depth is None else to_device(depth, torch.float32),
                             delta, window, masks)
-    counts, box_obj, box_visib = (a.cpu().numpy() for a in (out.px_count, out.bbox_obj, out.bbox_visib))
-    info = []
-    for s in range(S):
-        rows = []
-        for i in range(plan.scene_offsets[s], plan.scene_offsets[s + 1]):
-            n_all, n_valid, n_visib = (int(v) for v in counts[i])
-            rows.append({"bbox_obj": [int(v) for v in box_obj[i]], "bbox_visib": [int(v) for v in box_visib[i]], "px_count_all": n_all,
-                         "px_count_valid": n_valid, "px_count_visib": n_visib, "visib_fract": n_visib / float(n_all) if n_all > 0 else 0.0})
-        info.append(rows)
+    info = _info(plan, out)
     per_scene = lambda m: [m[plan.scene_offsets[s]:plan.scene_offsets[s + 1]] for s in range(S)]
     return SceneGroundTruth(info, out.id_image.cpu().numpy(), None if out.scene_depth is None else out.scene_depth.cpu().numpy(),
                             per_scene(out.mask_full.cpu().numpy()) if masks else None,
                             per_scene(out.mask_visib.cpu().numpy()) if masks else None)
+
+
+def _background(background, S, h, w):
+    """None, three values 0 ... 255 or uint8 images [h,w,3] / [S,h,w,3] (RGB) -> what ops.scene_compose takes"""
+    if background is None:
+        return (0, 0, 0)
+    if not torch.is_tensor(background):
+        background = np.asarray(background)
+        if background.ndim == 1:
+            return background
+        if background.dtype != np.uint8:
+            raise ValueError("render_scenes: a background image must be uint8, got %s" % background.dtype)
+    if background.ndim == 3:
+        background = background[None].expand(S, -1, -1, -1) if torch.is_tensor(background) else np.broadcast_to(background, (S,) + background.shape)
+    if tuple(background.shape) != (S, h, w, 3):
+        raise ValueError("render_scenes: background must be [%d,%d,3] or [%d,%d,%d,3], got %s" % (h, w, S, h, w, tuple(background.shape)))
+    return to_device(background, torch.uint8)
+
+
+def render_scenes(scenes, models, K, im_size, background=None, channel_order="bgr", **shading):
+    """Synthetic images of S scenes from the meshes and poses of their instances, with their ground truth.  scenes, models, K:
+    see scene_gt_info (models also carry 'colors' / 'normals': utils.renderer.render_rgbd_batch); im_size (w, h); background:
+    None (black), three values 0 ... 255, or uint8 images [h,w,3] (shared) / [S,h,w,3], RGB, host or device; channel_order of
+    the images 'bgr' (what engine.forward_u8 and the device augmentation take) or 'rgb'; **shading: shading, ambient_weight,
+    light_cam_pos, surf_color of render_rgbd_batch, and delta, clip_near, clip_far of scene_gt_info.  Every mesh is rendered
+    once at all its poses (colour and depth in one pass), scene_gt_info(extent='image') runs on the depth renders against the
+    depth composed from them, and its id image selects each pixel's instance colour (pp_scene_compose_u8).
+    -> (images uint8 [S,h,w,3] on the device, info: as scene_gt_info's)."""
+    from .renderer import render_rgbd_batch
+    if channel_order not in ops.CHANNEL_ORDERS:
+        raise ValueError("render_scenes: unknown channel order %r (rgb | bgr)" % (channel_order,))
+    delta, clip_near, clip_far = shading.pop("delta", 15.0), shading.pop("clip_near", 100), shading.pop("clip_far", 10000)
+    unknown = sorted(set(shading) - {"shading", "ambient_weight", "light_cam_pos", "surf_color"})
+    if unknown:
+        raise TypeError("render_scenes: unexpected argument %s" % ", ".join(unknown))
+    if not float(delta) >= 0.0:
+        raise ValueError("render_scenes: delta must not be negative, got %r" % (delta,))
+    scenes = list(scenes)
+    S = len(scenes)
+    if S < 1:
+        raise ValueError("render_scenes: no scenes")
+    plan = plan_instances(scenes)
+    missing = [o for o in plan.groups if o not in models]
+    if missing:
+        raise ValueError("render_scenes: no model for obj_id %s" % ", ".join(repr(o) for o in missing))
+    _, w, h = _scene_depth(None, S, im_size)
+    Ks = per_pose(K, S, (3, 3))
+    background = _background(background, S, h, w)
+    n = len(plan.obj_ids)
+    ctx = default_context()
+    if n == 0:  # nothing to render: the background alone (one empty stand-in instance, no id refers to it)
+        ids, colors = torch.zeros((S, h, w), dtype=torch.uint8, device="cuda"), torch.zeros((1, h, w, 3), dtype=torch.uint8, device="cuda")
+        offsets = np.zeros(S + 1, np.int32)
+        offsets[-1] = 1
+        return ops.scene_compose(ctx, ids, colors, offsets, background, channel_order), [[] for _ in scenes]
+    K_inst = Ks[plan.scene_of]
+    renders = [render_rgbd_batch(models[o], (w, h), K_inst[idx], plan.R[idx], plan.t[idx], clip_near, clip_far, ctx=ctx, **shading)
+               for o, idx in plan.groups.items()]
+    depth, rgb = (r[0][k] if len(r) == 1 else torch.cat([x[k] for x in r])[torch.from_numpy(plan.order).to(r[0][k].device)]
+                  for r, k in ((renders, "depth"), (renders, "rgb")))
+    out = ops.scene_gt_info(ctx, depth, plan.scene_offsets, to_device(k4(K_inst, n)), None, delta)
+    return ops.scene_compose(ctx, out.id_image, rgb, plan.scene_offsets, background, channel_order), _info(plan, out)
 
 
 def annotations_from_scene(info, id_row, skip=()):
