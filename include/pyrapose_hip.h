@@ -507,14 +507,46 @@ int pp_render_depth_f32(pp_ctx* ctx, int n_pose, int n_vert, const double* verts
  * normalize(interp N) (back-facing normals are not flipped: ambient only); flat: n = normalize((P1 - P0) x (P2 - P0)), sign
  * chosen so that n . P0 < 0 (facing the viewer whatever the winding); d = max(l . n, 0) (0 for a zero-length n or l);
  * rgb = (float)(min(ambient_weight + d, 1) * c).  A pixel without a fragment holds bg_color, id -1 and depth 0.
- * Deviations from the reference: textures are not rendered; the 3-vector normal is normalised (the reference normalises
- * u_nm * vec4(normal, 1) over four components); parity with an OpenGL driver unpinned (restated: tests/render_rgb_np.py).
+ * Deviations from the reference: the 3-vector normal is normalised (the reference normalises u_nm * vec4(normal, 1) over four
+ * components); parity with an OpenGL driver unpinned (restated: tests/render_rgb_np.py).  Textured meshes: pp_render_rgbd_tex.
  * workspace_bytes >= pp_render_rgbd_workspace_bytes (0: bad shape). */
 size_t pp_render_rgbd_workspace_bytes(int n_pose, int n_vert, int n_tri, int width, int height);
 int pp_render_rgbd(pp_ctx* ctx, int n_pose, int n_vert, const double* verts, const double* colors, const double* normals, int n_tri,
                    const int* faces, const double* R, const double* t, const double* K4, int width, int height, double clip_near,
                    double clip_far, int shading, double ambient_weight, const double* light_cam_pos, const double* bg_color,
                    void* workspace, size_t workspace_bytes, float* depth, int* tri_id, float* rgb_f32, unsigned char* rgb_u8);
+/* Textured variant of pp_render_rgbd: the other branch of the reference's fragment shaders (hodan_renderer.py:56-57, 72-76,
+ * 98-102, set up at :319-332 and :398-403), rgb = light_w * texture2D(u_texture, v_texcoord).  Everything as in pp_render_rgbd --
+ * same passes, one launch of the same raster kernel text compiled with the sampler, the same depth and tri_id bits -- except that
+ * the vertex colours are replaced by
+ *   uv   [n_vert,2] float64 on the device, texture coordinates (not per pose: read as they are)
+ *   tex  [tex_h,tex_w,4] uint8 RGBX on the device, 4-byte aligned, rows in the order of the image file (top row first); the
+ *        fourth byte is ignored, a texel is one aligned 32-bit load at a 32-bit offset: tex_w, tex_h in 1 ... 16384 and
+ *        tex_w * tex_h <= 2^28 (PP_ERR_SHAPE otherwise, and 0 from pp_render_rgbd_tex_workspace_bytes)
+ *   filter 0 = nearest, 1 = bilinear; wrap 0 = clamp to edge, 1 = repeat.
+ * A call with only depth / tri_id outputs needs neither uv nor tex (filter, wrap and the size are then not looked at when tex
+ * is NULL).  Sampling rule, float64 without contraction, in exactly this order (tests/render_tex_np.py restates it):
+ *   u = (q0 u0 + q1 u1) + q2 u2 and likewise v, with the perspective-correct weights q_i above;
+ *   x = u * tex_w, y = v * tex_h: GL texel space.  The reference uploads np.flipud(image) and GL's t = 0 is the first uploaded
+ *     row, so v = 0 is the BOTTOM row of the image file: GL texel (i, j) is tex[tex_h - 1 - j][i].  The kernel does the flip;
+ *   x or y not finite (bad input only): x = y = 0.5, the centre of GL texel (0, 0) -- no index is computed from a NaN;
+ *   wrap(i, n): clamp min(max(i, 0), n - 1); repeat i - n * floor(i / n) on integers, so negative coordinates wrap correctly.
+ *     The floors are converted to integers after clamping them to +-2^30;
+ *   nearest: texel (wrap(floor(x), tex_w), wrap(floor(y), tex_h));
+ *   bilinear: xs = x - 0.5, i0 = floor(xs), fx = xs - i0, i1 = i0 + 1, both wrapped independently; the same for y (ys, j0, fy,
+ *     j1); per channel, with cab = (double)byte / 255.0 of texel (ia, jb):
+ *       c = ((1 - fx) * c00 + fx * c10) * (1 - fy) + ((1 - fx) * c01 + fx * c11) * fy;
+ *   rgb = (float)(light_w * c), light_w = min(ambient_weight + d, 1) exactly as in pp_render_rgbd; uint8, bg_color, id -1 and
+ *   depth 0 as there.
+ * No mip-mapping and no anisotropic filtering: glumpy's default texture object has none, and to our reading its defaults are
+ * GL_NEAREST with clamp-to-edge -- that reading is unpinned (glumpy is not at hand), as parity with an OpenGL driver is for
+ * the rest of the pass.  The alpha channel is not used. */
+size_t pp_render_rgbd_tex_workspace_bytes(int n_pose, int n_vert, int n_tri, int width, int height, int tex_w, int tex_h);
+int pp_render_rgbd_tex(pp_ctx* ctx, int n_pose, int n_vert, const double* verts, const double* uv, const unsigned char* tex, int tex_w,
+                       int tex_h, int filter, int wrap, const double* normals, int n_tri, const int* faces, const double* R,
+                       const double* t, const double* K4, int width, int height, double clip_near, double clip_far, int shading,
+                       double ambient_weight, const double* light_cam_pos, const double* bg_color, void* workspace,
+                       size_t workspace_bytes, float* depth, int* tri_id, float* rgb_f32, unsigned char* rgb_u8);
 /* vsd() of pose_error.py:105-176 (with depth_im_to_dist_im :43-61 and the visibility masks :15-40) on rendered depth images:
  * n problems, depth_est / depth_gt [n,height,width] float32, depth_test float32 (uint16 sensor depth converts exactly) at
  * depth_test + i * test_stride (0: one scene depth shared by all problems, or width * height), K4 [n,4] = (fx, fy, cx, cy)

@@ -172,6 +172,9 @@ _SIGS = {
     "pp_render_rgbd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "pp_render_rgbd": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _d, _d, _i, _d, C.POINTER(_d), C.POINTER(_d), _p, _sz,
                             _p, _p, _p, _p]),
+    "pp_render_rgbd_tex_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i]),
+    "pp_render_rgbd_tex": (_i, [_p, _i, _i, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _i, _i, _d, _d, _i, _d, C.POINTER(_d),
+                                C.POINTER(_d), _p, _sz, _p, _p, _p, _p]),
     "pp_scene_compose_u8": (_i, [_p, _i, _i, C.POINTER(_i), _p, _i, _i, _p, _p, _p, C.POINTER(C.c_ubyte), _i, _p]),
     "pp_vsd_workspace_bytes": (_sz, [_i, _i, _i]),
     "pp_vsd_f64": (_i, [_p, _i, _i, _i, _p, _ll, _p, _p, _p, _d, _d, _i, _p, _p, _p, _p]),

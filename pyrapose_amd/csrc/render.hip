@@ -347,9 +347,20 @@ extern "C" int pp_render_depth_f32(pp_ctx* ctx, int n_pose, int n_vert, const do
 // normalize((P1 - P0) x (P2 - P0)) with its sign chosen so that n . P0 < 0 (the shader's cross(dFdx, dFdy) faces the viewer
 // whatever the winding).  d = max(l . n, 0), 0 for a zero-length n or l; light_w = min(ambient + d, 1); out = (float)(light_w c);
 // uint8 = rintf(out * 255.0f) (np.round(rgb * 255).astype(np.uint8), :516).  No fragment: bg_color, id -1, depth 0.
-// Deviations: textures are not rendered; the 3-vector normal is normalised (the reference normalises u_nm * vec4(normal, 1)
-// over four components); light_cam_pos is in the OpenCV camera frame; parity with an OpenGL driver is unpinned.
+// Deviations: the 3-vector normal is normalised (the reference normalises u_nm * vec4(normal, 1) over four components);
+// light_cam_pos is in the OpenCV camera frame; parity with an OpenGL driver is unpinned.
+// Textured variant (pp_render_rgbd_tex; the shaders' other branch, hodan_renderer.py:56-57, 72-76, 98-102): the same kernel
+// text (render_rgbd_raster.inc) compiled with TEX, in which c = texture(u, v) replaces the interpolated vertex colour.  (u, v) = the vertices' UVs
+// interpolated like any attribute, read straight from uv (they do not depend on the pose); tri_shading holds them where the
+// untextured kernel holds the vertex colours.  With x = u tex_w and y = v tex_h in GL texel space (GL row j is row
+// tex_h - 1 - j of tex, which is given top row first as on disk; non-finite x or y: x = y = 0.5, the centre of GL texel (0, 0)):
+//   nearest:  texel (wrap(floor(x)), wrap(floor(y)))
+//   bilinear: xs = x - 0.5, i0 = floor(xs), fx = xs - i0, i1 = i0 + 1, likewise ys, j0, fy, j1, each index wrapped on its own;
+//             per channel c = ((1 - fx) c00 + fx c10) (1 - fy) + ((1 - fx) c01 + fx c11) fy, cab = texel (ia, jb)
+//   wrap:     clamp min(max(i, 0), n - 1) or repeat i - n floor(i / n), on integers (floors beyond +-2^30 are taken as +-2^30)
+// and a channel is (double)byte / 255.0.  tests/render_tex_np.py evaluates the same expressions in the same order.  No mip-maps.
 #define ZKEY_EMPTY 0xFFFFFFFFFFFFFFFFull
+#define TEX_INDEX_MAX 1073741824.0  // 2^30
 
 struct __align__(8) rattr {
   double P[3], N[3], L[3];
@@ -407,13 +418,24 @@ __device__ void raster_queue(unsigned long long* zb, const int* queue, int qn, c
 }
 
 // what shading needs of the triangle a pixel shows: kept while the thread's next pixel shows the same one
+// TEX: C holds the vertices' (u, v) in place of their colours
+template <bool TEX>
 struct tri_shading {
   tri_setup T;
-  double L[3][3], N[3][3], C[3][3];  // per vertex; flat shading: N[0] is the face normal
+  double L[3][3], N[3][3], C[3][TEX ? 2 : 3];  // per vertex; flat shading: N[0] is the face normal
 };
 
+// the texture of the textured kernel, passed by value
+struct tex_params {
+  const unsigned* tex;  // [h,w] RGBX texels, one 32-bit word each (R in the low byte), top row first
+  int w, h, bilinear, repeat;
+};
+
+// colors: [n_vert,3] vertex colours or, TEX, [n_vert,2] texture coordinates
+template <bool TEX>
 __device__ void load_tri_shading(const rvtx* __restrict__ vtx, const rattr* __restrict__ attr, const double* __restrict__ colors,
-                                 int n_vert, const int* __restrict__ faces, int tri, int width, int height, int phong, tri_shading* S) {
+                                 int n_vert, const int* __restrict__ faces, int tri, int width, int height, int phong,
+                                 tri_shading<TEX>* S) {
   setup_triangle(vtx, n_vert, faces, tri, width, height, &S->T);  // the triangle won a pixel: it passed already
   double P[3][3];
   for (int v = 0; v < 3; ++v) {
@@ -423,7 +445,11 @@ __device__ void load_tri_shading(const rvtx* __restrict__ vtx, const rattr* __re
       P[v][k] = a->P[k];
       S->L[v][k] = a->L[k];
       S->N[v][k] = a->N[k];
-      S->C[v][k] = colors[3 * (size_t)i + k];
+      if (!TEX) S->C[v][k] = colors[3 * (size_t)i + k];
+    }
+    if (TEX) {
+      S->C[v][0] = colors[2 * (size_t)i];
+      S->C[v][1] = colors[2 * (size_t)i + 1];
     }
   }
   if (!phong) {
@@ -439,7 +465,49 @@ __device__ void load_tri_shading(const rvtx* __restrict__ vtx, const rattr* __re
   }
 }
 
-__device__ __forceinline__ void shade_rgb_px(const tri_shading& S, int r, int c, const rgb_params& prm, float* out) {
+// texel index i (any integer) -> [0, n): clamp to edge, or repeat (i - n floor(i / n) on integers)
+__device__ __forceinline__ int tex_wrap(int i, int n, int repeat) {
+  if (repeat) {
+    const int m = i % n;
+    return m < 0 ? m + n : m;
+  }
+  return min(max(i, 0), n - 1);
+}
+
+// texel (i, j) of GL texel space, both in range: row tex_h - 1 - j of the image as given.  tex_w * tex_h <= 2^28: 32-bit offsets
+__device__ __forceinline__ unsigned tex_fetch(const tex_params& tp, int i, int j) {
+  return tp.tex[(unsigned)(tp.h - 1 - j) * (unsigned)tp.w + (unsigned)i];
+}
+
+// floor value f of a texel coordinate as an integer; floors beyond +-2^30 are taken as +-2^30, so no conversion overflows
+__device__ __forceinline__ int tex_int(double f) { return (int)fmin(fmax(f, -TEX_INDEX_MAX), TEX_INDEX_MAX); }
+
+// the texture at (u, v), three channels in [0, 1]; the rule is in the comment at the head of the colour renderer
+__device__ __forceinline__ void sample_tex(const tex_params& tp, double u, double v, double* c) {
+  double x = u * tp.w, y = v * tp.h;
+  if (!(isfinite(x) && isfinite(y))) x = y = 0.5;  // no index is computed from a NaN
+  if (!tp.bilinear) {
+    const unsigned p = tex_fetch(tp, tex_wrap(tex_int(floor(x)), tp.w, tp.repeat), tex_wrap(tex_int(floor(y)), tp.h, tp.repeat));
+    for (int k = 0; k < 3; ++k) c[k] = (double)((p >> (8 * k)) & 0xFFu) / 255.0;
+    return;
+  }
+  const double xs = x - 0.5, ys = y - 0.5;
+  const double fi = floor(xs), fj = floor(ys);
+  const double fx = xs - fi, fy = ys - fj;
+  const int i = tex_int(fi), j = tex_int(fj);
+  const int i0 = tex_wrap(i, tp.w, tp.repeat), i1 = tex_wrap(i + 1, tp.w, tp.repeat);
+  const int j0 = tex_wrap(j, tp.h, tp.repeat), j1 = tex_wrap(j + 1, tp.h, tp.repeat);
+  const unsigned p00 = tex_fetch(tp, i0, j0), p10 = tex_fetch(tp, i1, j0), p01 = tex_fetch(tp, i0, j1), p11 = tex_fetch(tp, i1, j1);
+  for (int k = 0; k < 3; ++k) {
+    const double c00 = (double)((p00 >> (8 * k)) & 0xFFu) / 255.0, c10 = (double)((p10 >> (8 * k)) & 0xFFu) / 255.0;
+    const double c01 = (double)((p01 >> (8 * k)) & 0xFFu) / 255.0, c11 = (double)((p11 >> (8 * k)) & 0xFFu) / 255.0;
+    c[k] = ((1.0 - fx) * c00 + fx * c10) * (1.0 - fy) + ((1.0 - fx) * c01 + fx * c11) * fy;
+  }
+}
+
+template <bool TEX>
+__device__ __forceinline__ void shade_rgb_px(const tri_shading<TEX>& S, int r, int c, const rgb_params& prm, const tex_params& tp,
+                                             float* out) {
   const tri_setup& T = S.T;
   const double px = c + 0.5, py = r + 0.5;
   const double w0 = T.s * edge_fn(T.x[1], T.y[1], T.x[2], T.y[2], px, py);
@@ -463,132 +531,31 @@ __device__ __forceinline__ void shade_rgb_px(const tri_shading& S, int r, int c,
   const double d = dot > 0.0 ? dot : 0.0;
   const double sum = prm.ambient + d;
   const double light_w = sum > 1.0 ? 1.0 : sum;
-  for (int k = 0; k < 3; ++k) out[k] = (float)(light_w * ((q0 * S.C[0][k] + q1 * S.C[1][k]) + q2 * S.C[2][k]));
+  if (TEX) {
+    double t[3];
+    sample_tex(tp, (q0 * S.C[0][0] + q1 * S.C[1][0]) + q2 * S.C[2][0], (q0 * S.C[0][1] + q1 * S.C[1][1]) + q2 * S.C[2][1], t);
+    for (int k = 0; k < 3; ++k) out[k] = (float)(light_w * t[k]);
+  } else {
+    for (int k = 0; k < 3; ++k) out[k] = (float)(light_w * ((q0 * S.C[0][k] + q1 * S.C[1][k]) + q2 * S.C[2][k]));
+  }
 }
 
 __device__ __forceinline__ unsigned char rgb_to_u8(float v) { return (unsigned char)fminf(fmaxf(rintf(v * 255.0f), 0.0f), 255.0f); }
 
+// The untextured kernel, and the declaration of the textured one, which is defined at the end of the file: the code object then
+// holds the kernels that were there before it at the places they had.
+#define RASTER_KERNEL render_rgbd_raster_kernel
+#define RASTER_TEX false
+#define RASTER_TP_PARAM
+#define RASTER_TP tex_params()
+#include "render_rgbd_raster.inc"
+
 __global__ void __launch_bounds__(RASTER_THREADS)
-render_rgbd_raster_kernel(int n_vert, const int* __restrict__ faces, const rvtx* __restrict__ vtx_all, int n_tri, int width, int height,
-                          int tiles_x, int n_tiles, const int* __restrict__ offsets, const int* __restrict__ list,
-                          const int* __restrict__ big_n, const int* __restrict__ big, double zn, double zf,
-                          const rattr* __restrict__ attr_all, const double* __restrict__ colors, rgb_params prm, float* __restrict__ depth,
-                          int* __restrict__ tri_id, float* __restrict__ rgb_f32, unsigned char* __restrict__ rgb_u8) {
-  __shared__ unsigned long long zb[RT * RT];
-  __shared__ int queue[RASTER_THREADS];
-  __shared__ int qn;
-  const int pose = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
-  const int r0 = (tile / tiles_x) * RT, c0 = (tile % tiles_x) * RT;
-  const rvtx* vtx = vtx_all + (size_t)pose * n_vert;
-  for (int k = tid; k < RT * RT; k += RASTER_THREADS) zb[k] = ZKEY_EMPTY;
-  if (tid == 0) qn = 0;
-  __syncthreads();
-  const size_t b = (size_t)pose * n_tiles + tile;
-  const int l0 = offsets[b], l1 = offsets[b + 1];
-  for (int base = l0; base < l1; base += RASTER_THREADS) {
-    if (base + tid < l1) {
-      const int tri = list[base + tid];
-      tri_setup T;
-      if (setup_triangle(vtx, n_vert, faces, tri, width, height, &T)) {
-        const int a0 = max(T.c0, c0), a1 = min(T.c1, c0 + RT - 1), b0 = max(T.r0, r0), b1 = min(T.r1, r0 + RT - 1);
-        const int area = (a1 - a0 + 1) * (b1 - b0 + 1);
-        if (a0 <= a1 && b0 <= b1) {
-          if (area <= RASTER_SMALL_PX) {
-            for (int r = b0; r <= b1; ++r)
-              for (int c = a0; c <= a1; ++c) raster_px(zb, T, tri, r, c, r0, c0, zn, zf);
-          } else {
-            queue[atomicAdd(&qn, 1)] = tri;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    raster_queue(zb, queue, qn, vtx, n_vert, faces, width, height, r0, c0, zn, zf);
-    __syncthreads();
-    if (tid == 0) qn = 0;
-    __syncthreads();
-  }
-  const int nb = big_n[pose];
-  for (int base = 0; base < nb; base += RASTER_THREADS) {
-    if (base + tid < nb) {
-      const int tri = big[(size_t)pose * n_tri + base + tid];
-      tri_setup T;
-      if (setup_triangle(vtx, n_vert, faces, tri, width, height, &T) && T.c0 < c0 + RT && T.c1 >= c0 && T.r0 < r0 + RT && T.r1 >= r0)
-        queue[atomicAdd(&qn, 1)] = tri;
-    }
-    __syncthreads();
-    raster_queue(zb, queue, qn, vtx, n_vert, faces, width, height, r0, c0, zn, zf);
-    __syncthreads();
-    if (tid == 0) qn = 0;
-    __syncthreads();
-  }
-  // the tile, 4 pixels of one row per thread
-  const int r = r0 + tid / (RT / 4), c = c0 + (tid % (RT / 4)) * 4;
-  if (r >= height || c >= width) return;
-  float z[4];
-  int id[4];
-  for (int k = 0; k < 4; ++k) {
-    const unsigned long long key = zb[(tid / (RT / 4)) * RT + (tid % (RT / 4)) * 4 + k];
-    const unsigned hi = (unsigned)(key >> 32);
-    const bool hit = hi < 0x7F800000u;  // a depth that rounded to +inf is no fragment, as in the depth pass
-    z[k] = hit ? __uint_as_float(hi) : 0.0f;
-    id[k] = hit ? (int)(unsigned)key : -1;
-  }
-  const size_t px0 = ((size_t)pose * height + r) * width + c;
-  const bool full = (width & 3) == 0;  // then c + 3 < width and px0 is a multiple of 4
-  if (depth) {
-    if (full && (reinterpret_cast<uintptr_t>(depth) & 15u) == 0) {
-      *(float4*)(depth + px0) = make_float4(z[0], z[1], z[2], z[3]);
-    } else {
-      for (int k = 0; k < 4; ++k)
-        if (c + k < width) depth[px0 + k] = z[k];
-    }
-  }
-  if (tri_id) {
-    if (full && (reinterpret_cast<uintptr_t>(tri_id) & 15u) == 0) {
-      *(int4*)(tri_id + px0) = make_int4(id[0], id[1], id[2], id[3]);
-    } else {
-      for (int k = 0; k < 4; ++k)
-        if (c + k < width) tri_id[px0 + k] = id[k];
-    }
-  }
-  if (!rgb_f32 && !rgb_u8) return;
-  float v[12];
-  tri_shading S;
-  int held = -1;
-  for (int k = 0; k < 4; ++k) {
-    if (id[k] < 0) {
-      for (int j = 0; j < 3; ++j) v[3 * k + j] = (float)prm.bg[j];
-      continue;
-    }
-    if (id[k] != held) {
-      held = id[k];
-      load_tri_shading(vtx, attr_all + (size_t)pose * n_vert, colors, n_vert, faces, held, width, height, prm.phong, &S);
-    }
-    shade_rgb_px(S, r, c + k, prm, v + 3 * k);
-  }
-  if (rgb_f32) {
-    float* o = rgb_f32 + 3 * px0;
-    if (full && (reinterpret_cast<uintptr_t>(rgb_f32) & 15u) == 0) {
-      for (int j = 0; j < 3; ++j) ((float4*)o)[j] = make_float4(v[4 * j], v[4 * j + 1], v[4 * j + 2], v[4 * j + 3]);
-    } else {
-      for (int k = 0; k < 12; ++k)
-        if (c + k / 3 < width) o[k] = v[k];
-    }
-  }
-  if (rgb_u8) {
-    unsigned char* o = rgb_u8 + 3 * px0;
-    unsigned char u[12];
-    for (int k = 0; k < 12; ++k) u[k] = rgb_to_u8(v[k]);
-    if (full && (reinterpret_cast<uintptr_t>(rgb_u8) & 3u) == 0) {
-      for (int j = 0; j < 3; ++j)
-        ((unsigned*)o)[j] = (unsigned)u[4 * j] | ((unsigned)u[4 * j + 1] << 8) | ((unsigned)u[4 * j + 2] << 16) | ((unsigned)u[4 * j + 3] << 24);
-    } else {
-      for (int k = 0; k < 12; ++k)
-        if (c + k / 3 < width) o[k] = u[k];
-    }
-  }
-}
+render_rgbd_tex_raster_kernel(int n_vert, const int* __restrict__ faces, const rvtx* __restrict__ vtx_all, int n_tri, int width, int height,
+                              int tiles_x, int n_tiles, const int* __restrict__ offsets, const int* __restrict__ list,
+                              const int* __restrict__ big_n, const int* __restrict__ big, double zn, double zf,
+                              const rattr* __restrict__ attr_all, const double* __restrict__ uv, rgb_params prm, float* __restrict__ depth,
+                              int* __restrict__ tri_id, float* __restrict__ rgb_f32, unsigned char* __restrict__ rgb_u8, tex_params tp);
 
 static size_t render_rgbd_layout(int n_pose, int n_vert, int n_tri, int width, int height, char* base, render_ws* w, rattr** attr) {
   const size_t head = render_layout(n_pose, n_vert, n_tri, width, height, base, w);
@@ -601,26 +568,32 @@ extern "C" size_t pp_render_rgbd_workspace_bytes(int n_pose, int n_vert, int n_t
   return render_rgbd_layout(n_pose, n_vert, n_tri, width, height, nullptr, nullptr, nullptr);
 }
 
-extern "C" int pp_render_rgbd(pp_ctx* ctx, int n_pose, int n_vert, const double* verts, const double* colors, const double* normals,
-                              int n_tri, const int* faces, const double* R, const double* t, const double* K4, int width, int height,
-                              double clip_near, double clip_far, int shading, double ambient_weight, const double* light_cam_pos,
-                              const double* bg_color, void* workspace, size_t workspace_bytes, float* depth, int* tri_id,
-                              float* rgb_f32, unsigned char* rgb_u8) {
+// pp_render_rgbd (tp null; colors [n_vert,3]) and pp_render_rgbd_tex (colors: the texture coordinates [n_vert,2])
+static int render_rgbd_run(pp_ctx* ctx, const char* what, int n_pose, int n_vert, const double* verts, const double* colors,
+                           const double* normals, int n_tri, const int* faces, const double* R, const double* t, const double* K4,
+                           int width, int height, double clip_near, double clip_far, int shading, double ambient_weight,
+                           const double* light_cam_pos, const double* bg_color, void* workspace, size_t workspace_bytes, float* depth,
+                           int* tri_id, float* rgb_f32, unsigned char* rgb_u8, const tex_params* tp) {
   PP_REQUIRE_CTX(ctx);
   PP_CHECK_ARG(ctx, render_shape_ok(n_pose, n_vert, n_tri, width, height), PP_ERR_SHAPE,
-               "pp_render_rgbd: need 1..65535 poses, vertices, triangles, a 1..16384 image and n_pose * n_tri * 4 < 2^31");
-  PP_CHECK_ARG(ctx, verts && faces && R && t && K4 && workspace && light_cam_pos && bg_color, PP_ERR_ARG, "pp_render_rgbd: null argument");
-  PP_CHECK_ARG(ctx, depth || tri_id || rgb_f32 || rgb_u8, PP_ERR_ARG, "pp_render_rgbd: no output requested");
+               "%s: need 1..65535 poses, vertices, triangles, a 1..16384 image and n_pose * n_tri * 4 < 2^31", what);
+  PP_CHECK_ARG(ctx, verts && faces && R && t && K4 && workspace && light_cam_pos && bg_color, PP_ERR_ARG, "%s: null argument", what);
+  PP_CHECK_ARG(ctx, depth || tri_id || rgb_f32 || rgb_u8, PP_ERR_ARG, "%s: no output requested", what);
   const bool rgb = rgb_f32 || rgb_u8;
-  PP_CHECK_ARG(ctx, shading == 0 || shading == 1, PP_ERR_ARG, "pp_render_rgbd: shading must be 0 (flat) or 1 (phong)");
-  PP_CHECK_ARG(ctx, !rgb || colors, PP_ERR_ARG, "pp_render_rgbd: a colour output needs vertex colours");
-  PP_CHECK_ARG(ctx, !rgb || shading == 0 || normals, PP_ERR_ARG, "pp_render_rgbd: phong shading needs vertex normals");
-  PP_CHECK_ARG(ctx, clip_near >= 0.0 && clip_far >= clip_near, PP_ERR_ARG, "pp_render_rgbd: need 0 <= clip_near <= clip_far");
-  PP_CHECK_ARG(ctx, ambient_weight >= 0.0 && ambient_weight <= 1.0, PP_ERR_ARG, "pp_render_rgbd: ambient_weight must lie in [0, 1]");
+  PP_CHECK_ARG(ctx, shading == 0 || shading == 1, PP_ERR_ARG, "%s: shading must be 0 (flat) or 1 (phong)", what);
+  if (tp) {
+    PP_CHECK_ARG(ctx, !rgb || (colors && tp->tex), PP_ERR_ARG, "%s: a colour output needs uv and tex", what);
+    PP_CHECK_ARG(ctx, (reinterpret_cast<uintptr_t>(tp->tex) & 3u) == 0, PP_ERR_ALIGN, "%s: tex must be aligned to 4 bytes", what);
+  } else {
+    PP_CHECK_ARG(ctx, !rgb || colors, PP_ERR_ARG, "%s: a colour output needs vertex colours", what);
+  }
+  PP_CHECK_ARG(ctx, !rgb || shading == 0 || normals, PP_ERR_ARG, "%s: phong shading needs vertex normals", what);
+  PP_CHECK_ARG(ctx, clip_near >= 0.0 && clip_far >= clip_near, PP_ERR_ARG, "%s: need 0 <= clip_near <= clip_far", what);
+  PP_CHECK_ARG(ctx, ambient_weight >= 0.0 && ambient_weight <= 1.0, PP_ERR_ARG, "%s: ambient_weight must lie in [0, 1]", what);
   rgb_params prm;
   for (int k = 0; k < 3; ++k) {
-    PP_CHECK_ARG(ctx, isfinite(light_cam_pos[k]), PP_ERR_ARG, "pp_render_rgbd: light_cam_pos must be finite");
-    PP_CHECK_ARG(ctx, bg_color[k] >= 0.0 && bg_color[k] <= 1.0, PP_ERR_ARG, "pp_render_rgbd: bg_color must lie in [0, 1]");
+    PP_CHECK_ARG(ctx, isfinite(light_cam_pos[k]), PP_ERR_ARG, "%s: light_cam_pos must be finite", what);
+    PP_CHECK_ARG(ctx, bg_color[k] >= 0.0 && bg_color[k] <= 1.0, PP_ERR_ARG, "%s: bg_color must lie in [0, 1]", what);
     prm.light[k] = light_cam_pos[k];
     prm.bg[k] = bg_color[k];
   }
@@ -629,7 +602,7 @@ extern "C" int pp_render_rgbd(pp_ctx* ctx, int n_pose, int n_vert, const double*
   render_ws w;
   rattr* attr = nullptr;
   const size_t need = render_rgbd_layout(n_pose, n_vert, n_tri, width, height, (char*)workspace, &w, &attr);
-  PP_CHECK_ARG(ctx, workspace_bytes >= need, PP_ERR_ARG, "pp_render_rgbd: workspace of %zu bytes, need %zu", workspace_bytes, need);
+  PP_CHECK_ARG(ctx, workspace_bytes >= need, PP_ERR_ARG, "%s: workspace of %zu bytes, need %zu", what, workspace_bytes, need);
   const int tiles_x = (width + RT - 1) / RT, n_tiles = tiles_x * ((height + RT - 1) / RT);
   const size_t nb = (size_t)n_pose * n_tiles;
   hipMemsetAsync(w.counts, 0, nb * sizeof(int), ctx->stream);
@@ -643,12 +616,64 @@ extern "C" int pp_render_rgbd(pp_ctx* ctx, int n_pose, int n_vert, const double*
   hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, (int)nb, (const int*)w.counts, w.offsets, w.cursor);
   hipLaunchKernelGGL(render_bin_kernel, tg, dim3(256), 0, ctx->stream, 1, n_vert, n_tri, faces, (const rvtx*)w.vtx, width, height,
                      tiles_x, n_tiles, w.counts, w.cursor, w.list, w.big_n, w.big);
-  hipLaunchKernelGGL(render_rgbd_raster_kernel, dim3(n_tiles, n_pose), dim3(RASTER_THREADS), 0, ctx->stream, n_vert, faces,
-                     (const rvtx*)w.vtx, n_tri, width, height, tiles_x, n_tiles, (const int*)w.offsets, (const int*)w.list,
-                     (const int*)w.big_n, (const int*)w.big, clip_near, clip_far, (const rattr*)attr, colors, prm, depth, tri_id, rgb_f32,
-                     rgb_u8);
-  PP_CHECK_LAUNCH(ctx, "pp_render_rgbd");
+  if (tp && rgb) {
+    hipLaunchKernelGGL(render_rgbd_tex_raster_kernel, dim3(n_tiles, n_pose), dim3(RASTER_THREADS), 0, ctx->stream, n_vert, faces,
+                       (const rvtx*)w.vtx, n_tri, width, height, tiles_x, n_tiles, (const int*)w.offsets, (const int*)w.list,
+                       (const int*)w.big_n, (const int*)w.big, clip_near, clip_far, (const rattr*)attr, colors, prm, depth, tri_id, rgb_f32,
+                       rgb_u8, *tp);
+  } else {  // (without a colour output the shading tail is not reached: the untextured kernel serves both entry points)
+    hipLaunchKernelGGL(render_rgbd_raster_kernel, dim3(n_tiles, n_pose), dim3(RASTER_THREADS), 0, ctx->stream, n_vert, faces,
+                       (const rvtx*)w.vtx, n_tri, width, height, tiles_x, n_tiles, (const int*)w.offsets, (const int*)w.list,
+                       (const int*)w.big_n, (const int*)w.big, clip_near, clip_far, (const rattr*)attr, colors, prm, depth, tri_id, rgb_f32,
+                       rgb_u8);
+  }
+  PP_CHECK_LAUNCH(ctx, what);
   return PP_OK;
+}
+
+extern "C" int pp_render_rgbd(pp_ctx* ctx, int n_pose, int n_vert, const double* verts, const double* colors, const double* normals,
+                              int n_tri, const int* faces, const double* R, const double* t, const double* K4, int width, int height,
+                              double clip_near, double clip_far, int shading, double ambient_weight, const double* light_cam_pos,
+                              const double* bg_color, void* workspace, size_t workspace_bytes, float* depth, int* tri_id,
+                              float* rgb_f32, unsigned char* rgb_u8) {
+  return render_rgbd_run(ctx, "pp_render_rgbd", n_pose, n_vert, verts, colors, normals, n_tri, faces, R, t, K4, width, height, clip_near,
+                         clip_far, shading, ambient_weight, light_cam_pos, bg_color, workspace, workspace_bytes, depth, tri_id, rgb_f32,
+                         rgb_u8, nullptr);
+}
+
+#define TEX_MAX_TEXELS (1 << 28)  // texels are fetched at 32-bit offsets
+
+static bool render_tex_ok(int tex_w, int tex_h) {
+  return tex_w >= 1 && tex_w <= 16384 && tex_h >= 1 && tex_h <= 16384 && (long long)tex_w * tex_h <= TEX_MAX_TEXELS;
+}
+
+extern "C" size_t pp_render_rgbd_tex_workspace_bytes(int n_pose, int n_vert, int n_tri, int width, int height, int tex_w, int tex_h) {
+  if (!render_tex_ok(tex_w, tex_h)) return 0;
+  return pp_render_rgbd_workspace_bytes(n_pose, n_vert, n_tri, width, height);
+}
+
+extern "C" int pp_render_rgbd_tex(pp_ctx* ctx, int n_pose, int n_vert, const double* verts, const double* uv, const unsigned char* tex,
+                                  int tex_w, int tex_h, int filter, int wrap, const double* normals, int n_tri, const int* faces,
+                                  const double* R, const double* t, const double* K4, int width, int height, double clip_near,
+                                  double clip_far, int shading, double ambient_weight, const double* light_cam_pos,
+                                  const double* bg_color, void* workspace, size_t workspace_bytes, float* depth, int* tri_id,
+                                  float* rgb_f32, unsigned char* rgb_u8) {
+  PP_REQUIRE_CTX(ctx);
+  if (tex || rgb_f32 || rgb_u8) {  // a call for depth / tri_id alone needs no texture
+    PP_CHECK_ARG(ctx, render_tex_ok(tex_w, tex_h), PP_ERR_SHAPE,
+                 "pp_render_rgbd_tex: need a texture of 1..16384 x 1..16384 and at most 2^28 texels, got %d x %d", tex_w, tex_h);
+    PP_CHECK_ARG(ctx, filter == 0 || filter == 1, PP_ERR_ARG, "pp_render_rgbd_tex: filter must be 0 (nearest) or 1 (bilinear)");
+    PP_CHECK_ARG(ctx, wrap == 0 || wrap == 1, PP_ERR_ARG, "pp_render_rgbd_tex: wrap must be 0 (clamp to edge) or 1 (repeat)");
+  }
+  tex_params tp;
+  tp.tex = (const unsigned*)tex;
+  tp.w = tex_w;
+  tp.h = tex_h;
+  tp.bilinear = filter;
+  tp.repeat = wrap;
+  return render_rgbd_run(ctx, "pp_render_rgbd_tex", n_pose, n_vert, verts, uv, normals, n_tri, faces, R, t, K4, width, height, clip_near,
+                         clip_far, shading, ambient_weight, light_cam_pos, bg_color, workspace, workspace_bytes, depth, tri_id, rgb_f32,
+                         rgb_u8, &tp);
 }
 
 // ---- VSD ----------------------------------------------------------------------------------------------------------------
@@ -1333,3 +1358,10 @@ extern "C" int pp_scene_compose_u8(pp_ctx* ctx, int n_inst, int n_scene, const i
   PP_CHECK_LAUNCH(ctx, "pp_scene_compose_u8");
   return PP_OK;
 }
+
+// ---- the textured raster kernel of the colour renderer (declared there) ---------------------------------------------------------
+#define RASTER_KERNEL render_rgbd_tex_raster_kernel
+#define RASTER_TEX true
+#define RASTER_TP_PARAM , tex_params tp
+#define RASTER_TP tp
+#include "render_rgbd_raster.inc"

@@ -823,6 +823,50 @@ def render_rgbd(ctx, verts, faces, R, t, K4, width, height, colors=None, normals
     return out
 
 
+RENDER_FILTER = {"nearest": 0, "bilinear": 1}
+RENDER_WRAP = {"clamp": 0, "repeat": 1}
+
+
+def render_rgbd_tex(ctx, verts, faces, R, t, K4, width, height, uv=None, tex=None, filter="nearest", wrap="clamp", normals=None,
+                    clip_near=100.0, clip_far=10000.0, shading="phong", ambient_weight=0.5, light_cam_pos=(0.0, 0.0, 0.0),
+                    bg_color=(0.0, 0.0, 0.0), outputs=("rgb", "depth")):
+    """render_rgbd of a textured mesh (pp_render_rgbd_tex): in place of colors, uv float64 [n_vert,2] and tex, a cuda uint8
+    tensor [th,tw,4] (RGBX, the rows in the image file's order: v = 0 is its bottom row; the fourth byte is ignored), both
+    needed for 'rgb' / 'rgb_f32'; filter 'nearest' | 'bilinear'; wrap 'clamp' | 'repeat'.  Everything else as in render_rgbd."""
+    if shading not in RENDER_SHADING:
+        raise ValueError("render_rgbd_tex: unknown shading %r (flat | phong)" % (shading,))
+    if filter not in RENDER_FILTER:
+        raise ValueError("render_rgbd_tex: unknown filter %r (nearest | bilinear)" % (filter,))
+    if wrap not in RENDER_WRAP:
+        raise ValueError("render_rgbd_tex: unknown wrap %r (clamp | repeat)" % (wrap,))
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    unknown = [o for o in outputs if o not in RENDER_OUTPUTS]
+    if unknown or not outputs:
+        raise ValueError("render_rgbd_tex: outputs must name at least one of %s, got %r" % (" | ".join(RENDER_OUTPUTS), outputs))
+    verts = _arg("render_rgbd_tex", "verts", verts, _F64, (None, 3))
+    faces = _arg("render_rgbd_tex", "faces", faces, _I32, (None, 3))
+    R = _arg("render_rgbd_tex", "R", R, _F64, (None, 3, 3))
+    n, nv, nt = int(R.shape[0]), int(verts.shape[0]), int(faces.shape[0])
+    t = _arg("render_rgbd_tex", "t", t, _F64, (n, 3))
+    K4 = _arg("render_rgbd_tex", "K4", K4, _F64, (n, 4))
+    uv = _arg("render_rgbd_tex", "uv", uv, _F64, (nv, 2), optional=True)
+    tex = _arg("render_rgbd_tex", "tex", tex, _U8, (None, None, 4), optional=True)
+    normals = _arg("render_rgbd_tex", "normals", normals, _F64, (nv, 3), optional=True)
+    th, tw = (int(tex.shape[0]), int(tex.shape[1])) if tex is not None else (1, 1)
+    light = (C.c_double * 3)(*(float(v) for v in np.asarray(light_cam_pos, np.float64).reshape(3)))
+    bg = (C.c_double * 3)(*(float(v) for v in np.asarray(bg_color, np.float64).reshape(3)))
+    nbytes = lib.pp_render_rgbd_tex_workspace_bytes(n, nv, nt, int(width), int(height), tw, th)
+    ws = _workspace(nbytes, "render_rgbd_tex: unsupported shape (n=%d, vertices=%d, triangles=%d, %dx%d, texture %dx%d)" %
+                    (n, nv, nt, width, height, tw, th))
+    out = {k: _out(verts, (n, int(height), int(width)) + ((3,) if k.startswith("rgb") else ()), dt)
+           for k, dt in RENDER_OUTPUTS.items() if k in outputs}
+    check(lib.pp_render_rgbd_tex(ctx.handle, n, nv, _ptr(verts), _ptr(uv), _ptr(tex), tw, th, RENDER_FILTER[filter], RENDER_WRAP[wrap],
+                                 _ptr(normals), nt, _ptr(faces), _ptr(R), _ptr(t), _ptr(K4), int(width), int(height), float(clip_near),
+                                 float(clip_far), RENDER_SHADING[shading], float(ambient_weight), light, bg, _ptr(ws), nbytes,
+                                 *[_ptr(out.get(k)) for k in RENDER_OUTPUTS]), ctx.handle, "pp_render_rgbd_tex")
+    return out
+
+
 VSD_COSTS = {"step": 0, "tlinear": 1}
 
 

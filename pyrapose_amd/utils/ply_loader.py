@@ -1,6 +1,10 @@
 """PLY mesh loader with the dictionary layout of the reference's utils/ply_loader.py:11 load_ply: 'pts' [n,3], 'faces' [m,3]
 (when the file has faces) and, when present, 'normals' [n,3], 'colors' [n,3] and 'texture_uv' [n,2], all float64 arrays like
-there (face indices are whole numbers stored as floats).  ASCII and binary little-endian files; triangles only."""
+there (face indices are whole numbers stored as floats).  ASCII and binary little-endian files; triangles only.
+load_ply(path, texture=True) also reads the texture image the header names (comment TextureFile NAME, as BOP's UV-mapped
+models carry it) from beside the PLY: 'texture_file' and 'texture' (uint8 [h,w,3], rows as in the file)."""
+import os
+
 import numpy as np
 
 _TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
@@ -11,13 +15,15 @@ _TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2
 def _header(f):
     if f.readline().strip() != b"ply":
         raise ValueError("not a PLY file")
-    fmt, elements = None, []
+    fmt, elements, texture_file = None, [], None
     while True:
         line = f.readline()
         if not line:
             raise ValueError("PLY header without end_header")
         words = line.decode("ascii", "replace").split()
         if not words or words[0] in ("comment", "obj_info"):
+            if len(words) >= 3 and words[0] == "comment" and words[1] == "TextureFile":
+                texture_file = line.decode("utf-8", "replace").split(None, 2)[2].strip()
             continue
         if words[0] == "format":
             fmt = words[1]
@@ -34,7 +40,22 @@ def _header(f):
             break
     if fmt not in ("ascii", "binary_little_endian"):
         raise ValueError("PLY format %r is not supported (ascii, binary_little_endian)" % (fmt,))
-    return fmt, elements
+    return fmt, elements, texture_file
+
+
+def _load_texture(path, texture_file):
+    """the image NAME of the header's comment TextureFile NAME, beside the PLY -> uint8 [h,w,3]"""
+    if texture_file is None:
+        raise ValueError("load_ply: texture=True, but %s has no 'comment TextureFile NAME' in its header" % path)
+    image_path = os.path.join(os.path.dirname(os.path.abspath(path)), texture_file)
+    if not os.path.isfile(image_path):
+        raise ValueError("load_ply: the texture file %s named by %s does not exist" % (image_path, path))
+    try:
+        from PIL import Image
+    except ImportError:
+        raise ImportError("load_ply: texture=True reads the texture image with PIL (Pillow), which is not installed")
+    with Image.open(image_path) as im:
+        return np.ascontiguousarray(np.asarray(im.convert("RGB"), np.uint8))
 
 
 def _read_binary(f, count, props):
@@ -77,10 +98,11 @@ def _column(data, name):
     return np.array([r[name] for r in data], np.float64)
 
 
-def load_ply(path):
-    """Mesh from a PLY file -> dict(pts, faces[, normals, colors, texture_uv]) of float64 arrays."""
+def load_ply(path, texture=False):
+    """Mesh from a PLY file -> dict(pts, faces[, normals, colors, texture_uv]) of float64 arrays; with texture also
+    texture_file (the NAME of the header's comment TextureFile NAME) and texture (that image, uint8 [h,w,3])."""
     with open(path, "rb") as f:
-        fmt, elements = _header(f)
+        fmt, elements, texture_file = _header(f)
         model = {}
         for name, count, props in elements:
             data = _read_binary(f, count, props) if fmt == "binary_little_endian" else _read_ascii(f, count, props)
@@ -101,4 +123,7 @@ def load_ply(path):
                 model["faces"] = np.array(idx, np.float64).reshape(count, 3)
     if "pts" not in model:
         raise ValueError("PLY file without vertices")
+    if texture:
+        model["texture"] = _load_texture(path, texture_file)
+        model["texture_file"] = texture_file
     return model

@@ -162,10 +162,11 @@ def _background(background, S, h, w):
 
 def render_scenes(scenes, models, K, im_size, background=None, channel_order="bgr", **shading):
     """Synthetic images of S scenes from the meshes and poses of their instances, with their ground truth.  scenes, models, K:
-    see scene_gt_info (models also carry 'colors' / 'normals': utils.renderer.render_rgbd_batch); im_size (w, h); background:
+    see scene_gt_info (models also carry 'colors' / 'normals' or, textured, 'texture' / 'texture_uv', each model its own, and
+    a scene may mix both kinds: utils.renderer.render_rgbd_batch); im_size (w, h); background:
     None (black), three values 0 ... 255, or uint8 images [h,w,3] (shared) / [S,h,w,3], RGB, host or device; channel_order of
     the images 'bgr' (what engine.forward_u8 and the device augmentation take) or 'rgb'; **shading: shading, ambient_weight,
-    light_cam_pos, surf_color of render_rgbd_batch, and delta, clip_near, clip_far of scene_gt_info.  Every mesh is rendered
+    light_cam_pos, surf_color, tex_filter, tex_wrap of render_rgbd_batch, and delta, clip_near, clip_far of scene_gt_info.  Every mesh is rendered
     once at all its poses (colour and depth in one pass), scene_gt_info(extent='image') runs on the depth renders against the
     depth composed from them, and its id image selects each pixel's instance colour (pp_scene_compose_u8).
     -> (images uint8 [S,h,w,3] on the device, info: as scene_gt_info's)."""
@@ -173,7 +174,7 @@ def render_scenes(scenes, models, K, im_size, background=None, channel_order="bg
     if channel_order not in ops.CHANNEL_ORDERS:
         raise ValueError("render_scenes: unknown channel order %r (rgb | bgr)" % (channel_order,))
     delta, clip_near, clip_far = shading.pop("delta", 15.0), shading.pop("clip_near", 100), shading.pop("clip_far", 10000)
-    unknown = sorted(set(shading) - {"shading", "ambient_weight", "light_cam_pos", "surf_color"})
+    unknown = sorted(set(shading) - {"shading", "ambient_weight", "light_cam_pos", "surf_color", "tex_filter", "tex_wrap"})
     if unknown:
         raise TypeError("render_scenes: unexpected argument %s" % ", ".join(unknown))
     if not float(delta) >= 0.0:
