@@ -1,5 +1,6 @@
-// Pieces shared by the evaluation tail (pose.hip, render.hip, icp.hip): the 256-wide tile sum with its mean over tiles, the
-// tile maximum, the one-workgroup exclusive scan and the workspace alignment.  Every includer is compiled with -ffp-contract=off.
+// Pieces shared by the evaluation tail (pose.hip, render.hip, vsd.hip, icp.hip): the 256-wide tile sum with its mean over tiles,
+// the tile maximum, the one-workgroup exclusive scan (the renderer's bins, the ICP cloud) and the workspace alignment.  Every
+// includer is compiled with -ffp-contract=off.  What VSD and scene ground truth share is in visib_common.h.
 // Not here, on purpose: the small-matrix code of pnp.hip / wpnp.hip / icp.hip (solve6 vs wpnp_ldlt, so3_exp_mul vs
 // wpnp_rot_and_jl, the point accumulators) -- each is pinned operation by operation to its own numpy restatement.
 #pragma once

@@ -1,5 +1,5 @@
-// Depth renderer and the VSD pose error of the evaluation tail (tless_eval.py:470-471, 651-662 and the
-// same calls in occlusion_eval.py / ycbv_eval.py / homebrewed_eval.py / linemod_eval.py).
+// Depth and colour renderer of the evaluation tail: the images the VSD pose error (vsd.hip; tless_eval.py:470-471, 651-662 and the
+// same calls in occlusion_eval.py / ycbv_eval.py / homebrewed_eval.py / linemod_eval.py) and scene ground truth (scene_gt.hip) read.
 //
 // Renderer: the depth pass of utils/hodan_renderer.py (mode='depth'), which the reference's vsd() (utils/pose_error.py:105-176)
 // calls twice per detection.  Per pixel the value is the eye depth Z (camera-frame z of the nearest surface point,
@@ -24,14 +24,9 @@
 // Every fragment's depth is a pure function of (triangle, pixel) and the z-buffer keeps the minimum, so the image is the same
 // bits whatever order the lists and the atomics run in.
 //
-// VSD: pose_error.py:15-61 + 105-176 per problem on the rendered depth images, float64 where the reference is; per-block
-// partial counts / sums, then one ordered pass per problem.
-// Scene ground truth (at the end of the file): masks, boxes, pixel counts and the id image of a scene from its instances' renders.
-// Colour renderer (after the depth pass): shaded RGB, depth and triangle ids; a scene's image from its instances' colour renders
-// (at the end of the file).
-// Compiled with -ffp-contract=off: the host restatements (tests/render_np.py, utils/pose_error.py) evaluate the same
-// expressions in the same order.
-#include <limits.h>
+// Colour renderer (after the depth pass): shaded RGB, depth and triangle ids on the same passes 1-4 and the same raster phase.
+// Compiled with -ffp-contract=off: the host restatements (tests/render_np.py, tests/render_rgb_np.py, tests/render_tex_np.py)
+// evaluate the same expressions in the same order.
 #include <math.h>
 #include <stdint.h>
 #include "pose_common.h"
@@ -40,9 +35,6 @@
 #define RASTER_THREADS 256
 #define RASTER_SMALL_PX 64     // larger per-tile boxes are rasterised by the whole workgroup
 #define BIN_MAX_TILES 4        // triangles on more tiles go to the pose's big list
-#define VSD_THREADS 256
-#define VSD_PER_THREAD 4
-#define VSD_BLOCK (VSD_THREADS * VSD_PER_THREAD)
 
 struct __align__(16) rvtx {
   float x, y;   // screen position (OpenCV pixel coordinates)
@@ -176,20 +168,29 @@ __global__ void render_bin_kernel(int mode, int n_vert, int n_tri, const int* __
     }
 }
 
-__device__ __forceinline__ void raster_px(unsigned* zb, const tri_setup& T, int r, int c, int r0, int c0, double zn, double zf) {
+// The z-buffer word Z of a fragment: unsigned, the bits of its positive float32 depth (the depth pass), or unsigned long long,
+// those bits << 32 | triangle index (the colour pass).  Both order like (depth, triangle), so the integer minimum resolves them.
+template <class Z>
+__device__ __forceinline__ void raster_px(Z* zb, const tri_setup& T, int tri, int r, int c, int r0, int c0, double zn, double zf) {
   const float z = shade(T, r, c, zn, zf);
-  if (z > 0.0f) atomicMin(&zb[(r - r0) * RT + (c - c0)], __float_as_uint(z));
+  if (z > 0.0f) {
+    if constexpr (sizeof(Z) == 4)
+      atomicMin(&zb[(r - r0) * RT + (c - c0)], __float_as_uint(z));
+    else
+      atomicMin(&zb[(r - r0) * RT + (c - c0)], ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)tri);
+  }
 }
 
 // the queued triangles, each spread over the whole workgroup
-__device__ void raster_queue(unsigned* zb, const int* queue, int qn, const rvtx* vtx, int n_vert, const int* faces, int width,
-                             int height, int r0, int c0, double zn, double zf) {
+template <class Z>
+__device__ void raster_queue(Z* zb, const int* queue, int qn, const rvtx* vtx, int n_vert, const int* faces, int width, int height,
+                             int r0, int c0, double zn, double zf) {
   for (int q = 0; q < qn; ++q) {
     tri_setup T;
     setup_triangle(vtx, n_vert, faces, queue[q], width, height, &T);  // queued triangles passed it already
     const int a0 = max(T.c0, c0), a1 = min(T.c1, c0 + RT - 1), b0 = max(T.r0, r0), b1 = min(T.r1, r0 + RT - 1);
     const int bw = a1 - a0 + 1, n = bw * (b1 - b0 + 1);
-    for (int k = threadIdx.x; k < n; k += RASTER_THREADS) raster_px(zb, T, b0 + k / bw, a0 + k % bw, r0, c0, zn, zf);
+    for (int k = threadIdx.x; k < n; k += RASTER_THREADS) raster_px(zb, T, queue[q], b0 + k / bw, a0 + k % bw, r0, c0, zn, zf);
   }
 }
 
@@ -203,48 +204,8 @@ render_raster_kernel(int n_vert, const int* __restrict__ faces, const rvtx* __re
   const int pose = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
   const int r0 = (tile / tiles_x) * RT, c0 = (tile % tiles_x) * RT;
   const rvtx* vtx = vtx_all + (size_t)pose * n_vert;
-  for (int k = tid; k < RT * RT; k += RASTER_THREADS) zb[k] = 0x7F800000u;  // +inf
-  if (tid == 0) qn = 0;
-  __syncthreads();
-  const size_t b = (size_t)pose * n_tiles + tile;
-  const int l0 = offsets[b], l1 = offsets[b + 1];
-  for (int base = l0; base < l1; base += RASTER_THREADS) {
-    if (base + tid < l1) {
-      const int tri = list[base + tid];
-      tri_setup T;
-      if (setup_triangle(vtx, n_vert, faces, tri, width, height, &T)) {
-        const int a0 = max(T.c0, c0), a1 = min(T.c1, c0 + RT - 1), b0 = max(T.r0, r0), b1 = min(T.r1, r0 + RT - 1);
-        const int area = (a1 - a0 + 1) * (b1 - b0 + 1);
-        if (a0 <= a1 && b0 <= b1) {
-          if (area <= RASTER_SMALL_PX) {
-            for (int r = b0; r <= b1; ++r)
-              for (int c = a0; c <= a1; ++c) raster_px(zb, T, r, c, r0, c0, zn, zf);
-          } else {
-            queue[atomicAdd(&qn, 1)] = tri;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    raster_queue(zb, queue, qn, vtx, n_vert, faces, width, height, r0, c0, zn, zf);
-    __syncthreads();
-    if (tid == 0) qn = 0;
-    __syncthreads();
-  }
-  const int nb = big_n[pose];
-  for (int base = 0; base < nb; base += RASTER_THREADS) {
-    if (base + tid < nb) {
-      const int tri = big[(size_t)pose * n_tri + base + tid];
-      tri_setup T;
-      if (setup_triangle(vtx, n_vert, faces, tri, width, height, &T) && T.c0 < c0 + RT && T.c1 >= c0 && T.r0 < r0 + RT && T.r1 >= r0)
-        queue[atomicAdd(&qn, 1)] = tri;
-    }
-    __syncthreads();
-    raster_queue(zb, queue, qn, vtx, n_vert, faces, width, height, r0, c0, zn, zf);
-    __syncthreads();
-    if (tid == 0) qn = 0;
-    __syncthreads();
-  }
+#define RASTER_EMPTY 0x7F800000u  // +inf
+#include "render_raster_tile.inc"
   // the tile, 4 pixels of one row per thread
   const int r = r0 + tid / (RT / 4), c = c0 + (tid % (RT / 4)) * 4;
   if (r >= height) return;
@@ -265,6 +226,7 @@ render_raster_kernel(int n_vert, const int* __restrict__ faces, const rvtx* __re
 struct render_ws {
   rvtx* vtx;
   int *counts, *offsets, *cursor, *list, *big_n, *big;
+  char* end;  // the first byte behind the lists (the colour pass keeps its vertex attributes there)
 };
 
 static size_t render_layout(int n_pose, int n_vert, int n_tri, int width, int height, char* base, render_ws* w) {
@@ -286,6 +248,7 @@ static size_t render_layout(int n_pose, int n_vert, int n_tri, int width, int he
     w->list = (int*)(base + off[4]);
     w->big_n = (int*)(base + off[5]);
     w->big = (int*)(base + off[6]);
+    w->end = base + total;
   }
   return total;
 }
@@ -298,35 +261,6 @@ static bool render_shape_ok(int n_pose, int n_vert, int n_tri, int width, int he
 extern "C" size_t pp_render_workspace_bytes(int n_pose, int n_vert, int n_tri, int width, int height) {
   if (!render_shape_ok(n_pose, n_vert, n_tri, width, height)) return 0;
   return render_layout(n_pose, n_vert, n_tri, width, height, nullptr, nullptr);
-}
-
-extern "C" int pp_render_depth_f32(pp_ctx* ctx, int n_pose, int n_vert, const double* verts, int n_tri, const int* faces,
-                                   const double* R, const double* t, const double* K4, int width, int height, double clip_near,
-                                   double clip_far, void* workspace, size_t workspace_bytes, float* depth) {
-  PP_REQUIRE_CTX(ctx);
-  PP_CHECK_ARG(ctx, render_shape_ok(n_pose, n_vert, n_tri, width, height), PP_ERR_SHAPE,
-               "pp_render_depth_f32: need 1..65535 poses, vertices, triangles, a 1..16384 image and n_pose * n_tri * 4 < 2^31");
-  PP_CHECK_ARG(ctx, verts && faces && R && t && K4 && workspace && depth, PP_ERR_ARG, "pp_render_depth_f32: null argument");
-  PP_CHECK_ARG(ctx, clip_near >= 0.0 && clip_far >= clip_near, PP_ERR_ARG, "pp_render_depth_f32: need 0 <= clip_near <= clip_far");
-  render_ws w;
-  const size_t need = render_layout(n_pose, n_vert, n_tri, width, height, (char*)workspace, &w);
-  PP_CHECK_ARG(ctx, workspace_bytes >= need, PP_ERR_ARG, "pp_render_depth_f32: workspace of %zu bytes, need %zu", workspace_bytes, need);
-  const int tiles_x = (width + RT - 1) / RT, n_tiles = tiles_x * ((height + RT - 1) / RT);
-  const size_t nb = (size_t)n_pose * n_tiles;
-  hipMemsetAsync(w.counts, 0, nb * sizeof(int), ctx->stream);
-  hipMemsetAsync(w.big_n, 0, (size_t)n_pose * sizeof(int), ctx->stream);
-  hipLaunchKernelGGL(render_vertex_kernel, dim3((n_vert + 255) / 256, n_pose), dim3(256), 0, ctx->stream, n_vert, verts, R, t, K4, w.vtx);
-  const dim3 tg((n_tri + 255) / 256, n_pose);
-  hipLaunchKernelGGL(render_bin_kernel, tg, dim3(256), 0, ctx->stream, 0, n_vert, n_tri, faces, (const rvtx*)w.vtx, width, height,
-                     tiles_x, n_tiles, w.counts, w.cursor, w.list, w.big_n, w.big);
-  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, (int)nb, (const int*)w.counts, w.offsets, w.cursor);
-  hipLaunchKernelGGL(render_bin_kernel, tg, dim3(256), 0, ctx->stream, 1, n_vert, n_tri, faces, (const rvtx*)w.vtx, width, height,
-                     tiles_x, n_tiles, w.counts, w.cursor, w.list, w.big_n, w.big);
-  hipLaunchKernelGGL(render_raster_kernel, dim3(n_tiles, n_pose), dim3(RASTER_THREADS), 0, ctx->stream, n_vert, faces,
-                     (const rvtx*)w.vtx, n_tri, width, height, tiles_x, n_tiles, (const int*)w.offsets, (const int*)w.list,
-                     (const int*)w.big_n, (const int*)w.big, clip_near, clip_far, depth);
-  PP_CHECK_LAUNCH(ctx, "pp_render_depth_f32");
-  return PP_OK;
 }
 
 // ---- colour renderer: shaded RGB, depth and triangle ids ------------------------------------------------------------------
@@ -398,23 +332,6 @@ __global__ void render_attr_kernel(int n_vert, const double* __restrict__ verts,
   }
   normalize3(prm.light[0] - a.P[0], prm.light[1] - a.P[1], prm.light[2] - a.P[2], a.L);
   attr[(size_t)pose * n_vert + i] = a;
-}
-
-__device__ __forceinline__ void raster_px(unsigned long long* zb, const tri_setup& T, int tri, int r, int c, int r0, int c0, double zn,
-                                          double zf) {
-  const float z = shade(T, r, c, zn, zf);
-  if (z > 0.0f) atomicMin(&zb[(r - r0) * RT + (c - c0)], ((unsigned long long)__float_as_uint(z) << 32) | (unsigned)tri);
-}
-
-__device__ void raster_queue(unsigned long long* zb, const int* queue, int qn, const rvtx* vtx, int n_vert, const int* faces, int width,
-                             int height, int r0, int c0, double zn, double zf) {
-  for (int q = 0; q < qn; ++q) {
-    tri_setup T;
-    setup_triangle(vtx, n_vert, faces, queue[q], width, height, &T);  // queued triangles passed it already
-    const int a0 = max(T.c0, c0), a1 = min(T.c1, c0 + RT - 1), b0 = max(T.r0, r0), b1 = min(T.r1, r0 + RT - 1);
-    const int bw = a1 - a0 + 1, n = bw * (b1 - b0 + 1);
-    for (int k = threadIdx.x; k < n; k += RASTER_THREADS) raster_px(zb, T, queue[q], b0 + k / bw, a0 + k % bw, r0, c0, zn, zf);
-  }
 }
 
 // what shading needs of the triangle a pixel shows: kept while the thread's next pixel shows the same one
@@ -542,30 +459,81 @@ __device__ __forceinline__ void shade_rgb_px(const tri_shading<TEX>& S, int r, i
 
 __device__ __forceinline__ unsigned char rgb_to_u8(float v) { return (unsigned char)fminf(fmaxf(rintf(v * 255.0f), 0.0f), 255.0f); }
 
-// The untextured kernel, and the declaration of the textured one, which is defined at the end of the file: the code object then
-// holds the kernels that were there before it at the places they had.
+// the untextured kernel, then the textured one
 #define RASTER_KERNEL render_rgbd_raster_kernel
 #define RASTER_TEX false
 #define RASTER_TP_PARAM
 #define RASTER_TP tex_params()
 #include "render_rgbd_raster.inc"
+#define RASTER_KERNEL render_rgbd_tex_raster_kernel
+#define RASTER_TEX true
+#define RASTER_TP_PARAM , tex_params tp
+#define RASTER_TP tp
+#include "render_rgbd_raster.inc"
 
-__global__ void __launch_bounds__(RASTER_THREADS)
-render_rgbd_tex_raster_kernel(int n_vert, const int* __restrict__ faces, const rvtx* __restrict__ vtx_all, int n_tri, int width, int height,
-                              int tiles_x, int n_tiles, const int* __restrict__ offsets, const int* __restrict__ list,
-                              const int* __restrict__ big_n, const int* __restrict__ big, double zn, double zf,
-                              const rattr* __restrict__ attr_all, const double* __restrict__ uv, rgb_params prm, float* __restrict__ depth,
-                              int* __restrict__ tri_id, float* __restrict__ rgb_f32, unsigned char* __restrict__ rgb_u8, tex_params tp);
-
-static size_t render_rgbd_layout(int n_pose, int n_vert, int n_tri, int width, int height, char* base, render_ws* w, rattr** attr) {
-  const size_t head = render_layout(n_pose, n_vert, n_tri, width, height, base, w);
-  if (attr) *attr = (rattr*)(base + head);
-  return head + pp_align256((size_t)n_pose * n_vert * sizeof(rattr));
+// ---- host paths ---------------------------------------------------------------------------------------------------------------
+// the two checks every entry point words alike, under its own name
+static int render_check_shape(pp_ctx* ctx, const char* what, int n_pose, int n_vert, int n_tri, int width, int height) {
+  PP_CHECK_ARG(ctx, render_shape_ok(n_pose, n_vert, n_tri, width, height), PP_ERR_SHAPE,
+               "%s: need 1..65535 poses, vertices, triangles, a 1..16384 image and n_pose * n_tri * 4 < 2^31", what);
+  return PP_OK;
 }
+
+static int render_check_clip(pp_ctx* ctx, const char* what, double clip_near, double clip_far) {
+  PP_CHECK_ARG(ctx, clip_near >= 0.0 && clip_far >= clip_near, PP_ERR_ARG, "%s: need 0 <= clip_near <= clip_far", what);
+  return PP_OK;
+}
+
+// Passes 1-4 of entry point `what`: the workspace carved up into w (it must hold `extra` more bytes behind the lists), then vertex,
+// count, scan and scatter; with prm, the colour pass's attributes (4b) to w->end behind the vertex kernel.  The raster kernel
+// that follows reads w.
+static int render_bin_passes(pp_ctx* ctx, const char* what, int n_pose, int n_vert, const double* verts, int n_tri, const int* faces,
+                             const double* R, const double* t, const double* K4, int width, int height, void* workspace,
+                             size_t workspace_bytes, size_t extra, const double* normals, const rgb_params* prm, render_ws* w) {
+  const size_t need = render_layout(n_pose, n_vert, n_tri, width, height, (char*)workspace, w) + extra;
+  PP_CHECK_ARG(ctx, workspace_bytes >= need, PP_ERR_ARG, "%s: workspace of %zu bytes, need %zu", what, workspace_bytes, need);
+  const int tiles_x = (width + RT - 1) / RT, n_tiles = tiles_x * ((height + RT - 1) / RT);
+  const size_t nb = (size_t)n_pose * n_tiles;
+  hipMemsetAsync(w->counts, 0, nb * sizeof(int), ctx->stream);
+  hipMemsetAsync(w->big_n, 0, (size_t)n_pose * sizeof(int), ctx->stream);
+  const dim3 vg((n_vert + 255) / 256, n_pose);
+  hipLaunchKernelGGL(render_vertex_kernel, vg, dim3(256), 0, ctx->stream, n_vert, verts, R, t, K4, w->vtx);
+  if (prm) hipLaunchKernelGGL(render_attr_kernel, vg, dim3(256), 0, ctx->stream, n_vert, verts, normals, R, t, *prm, (rattr*)w->end);
+  const dim3 tg((n_tri + 255) / 256, n_pose);
+  hipLaunchKernelGGL(render_bin_kernel, tg, dim3(256), 0, ctx->stream, 0, n_vert, n_tri, faces, (const rvtx*)w->vtx, width, height,
+                     tiles_x, n_tiles, w->counts, w->cursor, w->list, w->big_n, w->big);
+  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, (int)nb, (const int*)w->counts, w->offsets, w->cursor);
+  hipLaunchKernelGGL(render_bin_kernel, tg, dim3(256), 0, ctx->stream, 1, n_vert, n_tri, faces, (const rvtx*)w->vtx, width, height,
+                     tiles_x, n_tiles, w->counts, w->cursor, w->list, w->big_n, w->big);
+  return PP_OK;
+}
+
+extern "C" int pp_render_depth_f32(pp_ctx* ctx, int n_pose, int n_vert, const double* verts, int n_tri, const int* faces,
+                                   const double* R, const double* t, const double* K4, int width, int height, double clip_near,
+                                   double clip_far, void* workspace, size_t workspace_bytes, float* depth) {
+  const char* what = "pp_render_depth_f32";
+  PP_REQUIRE_CTX(ctx);
+  if (const int rc = render_check_shape(ctx, what, n_pose, n_vert, n_tri, width, height)) return rc;
+  PP_CHECK_ARG(ctx, verts && faces && R && t && K4 && workspace && depth, PP_ERR_ARG, "%s: null argument", what);
+  if (const int rc = render_check_clip(ctx, what, clip_near, clip_far)) return rc;
+  render_ws w;
+  if (const int rc = render_bin_passes(ctx, what, n_pose, n_vert, verts, n_tri, faces, R, t, K4, width, height, workspace, workspace_bytes,
+                                       0, nullptr, nullptr, &w))
+    return rc;
+  const int tiles_x = (width + RT - 1) / RT, n_tiles = tiles_x * ((height + RT - 1) / RT);
+  hipLaunchKernelGGL(render_raster_kernel, dim3(n_tiles, n_pose), dim3(RASTER_THREADS), 0, ctx->stream, n_vert, faces,
+                     (const rvtx*)w.vtx, n_tri, width, height, tiles_x, n_tiles, (const int*)w.offsets, (const int*)w.list,
+                     (const int*)w.big_n, (const int*)w.big, clip_near, clip_far, depth);
+  PP_CHECK_LAUNCH(ctx, what);
+  return PP_OK;
+}
+
+// the per-(pose, vertex) attributes, behind the depth pass's layout
+static size_t render_attr_bytes(int n_pose, int n_vert) { return pp_align256((size_t)n_pose * n_vert * sizeof(rattr)); }
 
 extern "C" size_t pp_render_rgbd_workspace_bytes(int n_pose, int n_vert, int n_tri, int width, int height) {
   if (!render_shape_ok(n_pose, n_vert, n_tri, width, height)) return 0;
-  return render_rgbd_layout(n_pose, n_vert, n_tri, width, height, nullptr, nullptr, nullptr);
+  return render_layout(n_pose, n_vert, n_tri, width, height, nullptr, nullptr) + render_attr_bytes(n_pose, n_vert);
 }
 
 // pp_render_rgbd (tp null; colors [n_vert,3]) and pp_render_rgbd_tex (colors: the texture coordinates [n_vert,2])
@@ -575,8 +543,7 @@ static int render_rgbd_run(pp_ctx* ctx, const char* what, int n_pose, int n_vert
                            const double* light_cam_pos, const double* bg_color, void* workspace, size_t workspace_bytes, float* depth,
                            int* tri_id, float* rgb_f32, unsigned char* rgb_u8, const tex_params* tp) {
   PP_REQUIRE_CTX(ctx);
-  PP_CHECK_ARG(ctx, render_shape_ok(n_pose, n_vert, n_tri, width, height), PP_ERR_SHAPE,
-               "%s: need 1..65535 poses, vertices, triangles, a 1..16384 image and n_pose * n_tri * 4 < 2^31", what);
+  if (const int rc = render_check_shape(ctx, what, n_pose, n_vert, n_tri, width, height)) return rc;
   PP_CHECK_ARG(ctx, verts && faces && R && t && K4 && workspace && light_cam_pos && bg_color, PP_ERR_ARG, "%s: null argument", what);
   PP_CHECK_ARG(ctx, depth || tri_id || rgb_f32 || rgb_u8, PP_ERR_ARG, "%s: no output requested", what);
   const bool rgb = rgb_f32 || rgb_u8;
@@ -588,7 +555,7 @@ static int render_rgbd_run(pp_ctx* ctx, const char* what, int n_pose, int n_vert
     PP_CHECK_ARG(ctx, !rgb || colors, PP_ERR_ARG, "%s: a colour output needs vertex colours", what);
   }
   PP_CHECK_ARG(ctx, !rgb || shading == 0 || normals, PP_ERR_ARG, "%s: phong shading needs vertex normals", what);
-  PP_CHECK_ARG(ctx, clip_near >= 0.0 && clip_far >= clip_near, PP_ERR_ARG, "%s: need 0 <= clip_near <= clip_far", what);
+  if (const int rc = render_check_clip(ctx, what, clip_near, clip_far)) return rc;
   PP_CHECK_ARG(ctx, ambient_weight >= 0.0 && ambient_weight <= 1.0, PP_ERR_ARG, "%s: ambient_weight must lie in [0, 1]", what);
   rgb_params prm;
   for (int k = 0; k < 3; ++k) {
@@ -600,31 +567,20 @@ static int render_rgbd_run(pp_ctx* ctx, const char* what, int n_pose, int n_vert
   prm.ambient = ambient_weight;
   prm.phong = shading;
   render_ws w;
-  rattr* attr = nullptr;
-  const size_t need = render_rgbd_layout(n_pose, n_vert, n_tri, width, height, (char*)workspace, &w, &attr);
-  PP_CHECK_ARG(ctx, workspace_bytes >= need, PP_ERR_ARG, "%s: workspace of %zu bytes, need %zu", what, workspace_bytes, need);
+  if (const int rc = render_bin_passes(ctx, what, n_pose, n_vert, verts, n_tri, faces, R, t, K4, width, height, workspace, workspace_bytes,
+                                       render_attr_bytes(n_pose, n_vert), normals, rgb ? &prm : nullptr, &w))
+    return rc;
+  const rattr* attr = (const rattr*)w.end;
   const int tiles_x = (width + RT - 1) / RT, n_tiles = tiles_x * ((height + RT - 1) / RT);
-  const size_t nb = (size_t)n_pose * n_tiles;
-  hipMemsetAsync(w.counts, 0, nb * sizeof(int), ctx->stream);
-  hipMemsetAsync(w.big_n, 0, (size_t)n_pose * sizeof(int), ctx->stream);
-  const dim3 vg((n_vert + 255) / 256, n_pose);
-  hipLaunchKernelGGL(render_vertex_kernel, vg, dim3(256), 0, ctx->stream, n_vert, verts, R, t, K4, w.vtx);
-  if (rgb) hipLaunchKernelGGL(render_attr_kernel, vg, dim3(256), 0, ctx->stream, n_vert, verts, normals, R, t, prm, attr);
-  const dim3 tg((n_tri + 255) / 256, n_pose);
-  hipLaunchKernelGGL(render_bin_kernel, tg, dim3(256), 0, ctx->stream, 0, n_vert, n_tri, faces, (const rvtx*)w.vtx, width, height,
-                     tiles_x, n_tiles, w.counts, w.cursor, w.list, w.big_n, w.big);
-  hipLaunchKernelGGL(exclusive_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, ctx->stream, (int)nb, (const int*)w.counts, w.offsets, w.cursor);
-  hipLaunchKernelGGL(render_bin_kernel, tg, dim3(256), 0, ctx->stream, 1, n_vert, n_tri, faces, (const rvtx*)w.vtx, width, height,
-                     tiles_x, n_tiles, w.counts, w.cursor, w.list, w.big_n, w.big);
   if (tp && rgb) {
     hipLaunchKernelGGL(render_rgbd_tex_raster_kernel, dim3(n_tiles, n_pose), dim3(RASTER_THREADS), 0, ctx->stream, n_vert, faces,
                        (const rvtx*)w.vtx, n_tri, width, height, tiles_x, n_tiles, (const int*)w.offsets, (const int*)w.list,
-                       (const int*)w.big_n, (const int*)w.big, clip_near, clip_far, (const rattr*)attr, colors, prm, depth, tri_id, rgb_f32,
+                       (const int*)w.big_n, (const int*)w.big, clip_near, clip_far, attr, colors, prm, depth, tri_id, rgb_f32,
                        rgb_u8, *tp);
   } else {  // (without a colour output the shading tail is not reached: the untextured kernel serves both entry points)
     hipLaunchKernelGGL(render_rgbd_raster_kernel, dim3(n_tiles, n_pose), dim3(RASTER_THREADS), 0, ctx->stream, n_vert, faces,
                        (const rvtx*)w.vtx, n_tri, width, height, tiles_x, n_tiles, (const int*)w.offsets, (const int*)w.list,
-                       (const int*)w.big_n, (const int*)w.big, clip_near, clip_far, (const rattr*)attr, colors, prm, depth, tri_id, rgb_f32,
+                       (const int*)w.big_n, (const int*)w.big, clip_near, clip_far, attr, colors, prm, depth, tri_id, rgb_f32,
                        rgb_u8);
   }
   PP_CHECK_LAUNCH(ctx, what);
@@ -675,693 +631,3 @@ extern "C" int pp_render_rgbd_tex(pp_ctx* ctx, int n_pose, int n_vert, const dou
                          clip_far, shading, ambient_weight, light_cam_pos, bg_color, workspace, workspace_bytes, depth, tri_id, rgb_f32,
                          rgb_u8, &tp);
 }
-
-// ---- VSD ----------------------------------------------------------------------------------------------------------------
-
-// depth_im_to_dist_im (pose_error.py:43-61) at one pixel: || ((c - cx) d / fx, (r - cy) d / fy, d) ||, summed x, y, z in order
-__device__ __forceinline__ double dist_px(float d, int r, int c, double cx, double cy, double rfx, double rfy) {
-  const double dd = (double)d;
-  const double X = (((double)c - cx) * dd) * rfx;
-  const double Y = (((double)r - cy) * dd) * rfy;
-  return sqrt((X * X + Y * Y) + dd * dd);
-}
-
-// estimate_visib_mask (pose_error.py:15-29): both valid and float32(d_model) - float32(d_test) <= delta (in float32)
-__device__ __forceinline__ bool visib(double d_test, double d_model, float delta) {
-  return d_test > 0.0 && d_model > 0.0 && ((float)d_model - (float)d_test) <= delta;
-}
-
-__device__ void block_reduce3(double c, int inter, int uni, double* rd, int* ri, int* ru) {
-  const int tid = threadIdx.x;
-  rd[tid] = c;
-  ri[tid] = inter;
-  ru[tid] = uni;
-  __syncthreads();
-  for (int s = VSD_THREADS / 2; s > 0; s >>= 1) {
-    if (tid < s) {
-      rd[tid] += rd[tid + s];
-      ri[tid] += ri[tid + s];
-      ru[tid] += ru[tid + s];
-    }
-    __syncthreads();
-  }
-}
-
-// grid (blocks of VSD_BLOCK pixels, problems): per block the cost sum over the intersection, |inter| and |union|
-__global__ void __launch_bounds__(VSD_THREADS)
-vsd_partial_kernel(int width, int hw, const float* __restrict__ depth_test, long long test_stride, const float* __restrict__ depth_est,
-                   const float* __restrict__ depth_gt, const double* __restrict__ K4, float delta, double tau, int cost_type,
-                   double* __restrict__ part_cost, int* __restrict__ part_cnt) {
-  __shared__ double rd[VSD_THREADS];
-  __shared__ int ri[VSD_THREADS], ru[VSD_THREADS];
-  const int prob = blockIdx.y;
-  const double* k = K4 + 4 * prob;
-  const double cx = k[2], cy = k[3], rfx = 1.0 / k[0], rfy = 1.0 / k[1], rtau = 1.0 / tau;
-  const float* dt = depth_test + (size_t)prob * test_stride;
-  const float* de = depth_est + (size_t)prob * hw;
-  const float* dg = depth_gt + (size_t)prob * hw;
-  double cost = 0.0;
-  int inter = 0, uni = 0;
-  for (int j = 0; j < VSD_PER_THREAD; ++j) {
-    const int p = blockIdx.x * VSD_BLOCK + j * VSD_THREADS + threadIdx.x;
-    if (p >= hw) break;
-    const int r = p / width, c = p - r * width;
-    const double t_ = dist_px(dt[p], r, c, cx, cy, rfx, rfy);
-    const double e_ = dist_px(de[p], r, c, cx, cy, rfx, rfy);
-    const double g_ = dist_px(dg[p], r, c, cx, cy, rfx, rfy);
-    const bool vg = visib(t_, g_, delta);
-    const bool ve = visib(t_, e_, delta) || (vg && e_ > 0.0);
-    if (vg && ve) {
-      ++inter;
-      const double d = fabs(g_ - e_);
-      if (cost_type == 0) {
-        cost += d >= tau ? 1.0 : 0.0;
-      } else {
-        const double q = d * rtau;
-        cost += q > 1.0 ? 1.0 : q;
-      }
-    }
-    uni += (vg || ve) ? 1 : 0;
-  }
-  block_reduce3(cost, inter, uni, rd, ri, ru);
-  if (threadIdx.x == 0) {
-    const size_t o = (size_t)prob * gridDim.x + blockIdx.x;
-    part_cost[o] = rd[0];
-    part_cnt[2 * o] = ri[0];
-    part_cnt[2 * o + 1] = ru[0];
-  }
-}
-
-__global__ void vsd_final_kernel(int n, int nblk, const double* __restrict__ part_cost, const int* __restrict__ part_cnt,
-                                 double* __restrict__ e, long long* __restrict__ inter_out, long long* __restrict__ union_out) {
-  const int prob = blockIdx.x * blockDim.x + threadIdx.x;
-  if (prob >= n) return;
-  double cost = 0.0;
-  long long inter = 0, uni = 0;
-  for (int b = 0; b < nblk; ++b) {
-    const size_t o = (size_t)prob * nblk + b;
-    cost += part_cost[o];
-    inter += part_cnt[2 * o];
-    uni += part_cnt[2 * o + 1];
-  }
-  e[prob] = uni > 0 ? (cost + (double)(uni - inter)) / (double)uni : 1.0;
-  if (inter_out) inter_out[prob] = inter;
-  if (union_out) union_out[prob] = uni;
-}
-
-extern "C" size_t pp_vsd_workspace_bytes(int n, int width, int height) {
-  if (n <= 0 || width <= 0 || height <= 0) return 0;
-  const size_t nblk = ((size_t)width * height + VSD_BLOCK - 1) / VSD_BLOCK;
-  return pp_align256((size_t)n * nblk * sizeof(double)) + (size_t)n * nblk * 2 * sizeof(int);
-}
-
-extern "C" int pp_vsd_f64(pp_ctx* ctx, int n, int width, int height, const float* depth_test, long long test_stride,
-                          const float* depth_est, const float* depth_gt, const double* K4, double delta, double tau, int cost_type,
-                          void* workspace, double* e, long long* inter, long long* uni) {
-  PP_REQUIRE_CTX(ctx);
-  PP_CHECK_ARG(ctx, n > 0 && n <= 65535 && width > 0 && height > 0 && (long long)width * height <= 0x7FFFFFFFLL, PP_ERR_SHAPE,
-               "pp_vsd_f64: need 1..65535 problems and a non-empty image");
-  PP_CHECK_ARG(ctx, depth_test && depth_est && depth_gt && K4 && workspace && e, PP_ERR_ARG, "pp_vsd_f64: null argument");
-  PP_CHECK_ARG(ctx, test_stride == 0 || test_stride == (long long)width * height, PP_ERR_ARG,
-               "pp_vsd_f64: test_stride must be 0 (one shared scene depth) or width * height");
-  PP_CHECK_ARG(ctx, cost_type == 0 || cost_type == 1, PP_ERR_ARG, "pp_vsd_f64: cost_type must be 0 (step) or 1 (tlinear)");
-  PP_CHECK_ARG(ctx, tau > 0.0, PP_ERR_ARG, "pp_vsd_f64: tau must be positive");
-  const int hw = width * height, nblk = (hw + VSD_BLOCK - 1) / VSD_BLOCK;
-  double* part_cost = (double*)workspace;
-  int* part_cnt = (int*)((char*)workspace + pp_align256((size_t)n * nblk * sizeof(double)));
-  hipLaunchKernelGGL(vsd_partial_kernel, dim3(nblk, n), dim3(VSD_THREADS), 0, ctx->stream, width, hw, depth_test, test_stride,
-                     depth_est, depth_gt, K4, (float)delta, tau, cost_type, part_cost, part_cnt);
-  hipLaunchKernelGGL(vsd_final_kernel, dim3((n + 63) / 64), dim3(64), 0, ctx->stream, n, nblk, (const double*)part_cost,
-                     (const int*)part_cnt, e, inter, uni);
-  PP_CHECK_LAUNCH(ctx, "pp_vsd_f64");
-  return PP_OK;
-}
-
-// ---- VSD over a tolerance range (BOP's AR_VSD) ----------------------------------------------------------------------------
-// One pass over the pixels for up to VSD_MAX_TAU misalignment tolerances: a pixel's three distances, both visibility masks
-// and |d_gt - d_est| are computed once and serve every tau.  Same blocks, per-thread order and halving tree as
-// vsd_partial_kernel, so a column of e carries the bits pp_vsd_f64 gives at that tau.
-#define VSD_MAX_TAU 16
-
-struct vsd_taus {
-  double tau[VSD_MAX_TAU];  // strictly increasing; entries past n_tau are not read
-};
-
-// BOP 2019 (bop_toolkit's estimate_visib_mask with visib_mode 'bop19'; parity with bop_toolkit unpinned): a rendered pixel
-// without a sensor value counts as visible
-__device__ __forceinline__ bool visib_bop19(double d_test, double d_model, float delta) {
-  return d_model > 0.0 && (((float)d_model - (float)d_test) <= delta || d_test == 0.0);
-}
-
-struct vsd_px {
-  bool vg, ve, gt;  // the two visibility masks, d_gt > 0
-  double d;         // |d_gt - d_est|
-};
-
-// pixel p of one problem; depths of 0 (also what a pixel past the image is loaded as) are in no mask
-__device__ __forceinline__ vsd_px vsd_pixel(float dt, float de, float dg, int p, int width, double cx, double cy, double rfx,
-                                            double rfy, float delta, int visib_mode) {
-  const int r = p / width, c = p - r * width;
-  const double t_ = dist_px(dt, r, c, cx, cy, rfx, rfy);
-  const double e_ = dist_px(de, r, c, cx, cy, rfx, rfy);
-  const double g_ = dist_px(dg, r, c, cx, cy, rfx, rfy);
-  vsd_px o;
-  o.vg = visib_mode ? visib_bop19(t_, g_, delta) : visib(t_, g_, delta);
-  o.ve = (visib_mode ? visib_bop19(t_, e_, delta) : visib(t_, e_, delta)) || (o.vg && e_ > 0.0);
-  o.gt = g_ > 0.0;
-  o.d = fabs(g_ - e_);
-  return o;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// grid (blocks of VSD_BLOCK pixels, problems).  COST 0 ('step'): integer arithmetic -- taus increase, so a pixel of the
-// intersection adds one to a single LDS bin (the number of taus <= its d) and cost_t is the count of the bins above t.
-// COST 1 ('tlinear'): n_tau float64 sums per thread, all reduced by one halving tree (its order per tau is block_reduce3's).
-// part_cost [problem][block][n_tau] (step: the exact count as a double), part_cnt [problem][block][4] = |inter|, |union|,
-// |visib_gt|, |d_gt > 0|.
-template <int COST>
-__global__ void __launch_bounds__(VSD_THREADS)
-vsd_multi_partial_kernel(int width, int hw, const float* __restrict__ depth_test, long long test_stride,
-                         const float* __restrict__ depth_est, const float* __restrict__ depth_gt, const double* __restrict__ K4,
-                         float delta, int n_tau, vsd_taus taus, int visib_mode, double* __restrict__ part_cost,
-                         int* __restrict__ part_cnt) {
-  __shared__ double red[COST == 1 ? VSD_MAX_TAU * VSD_THREADS : 1];
-  __shared__ int bins[VSD_MAX_TAU + 1];
-  __shared__ int cnt[4];
-  const int tid = threadIdx.x, prob = blockIdx.y;
-  const double* k = K4 + 4 * prob;
-  const double cx = k[2], cy = k[3], rfx = 1.0 / k[0], rfy = 1.0 / k[1];
-  const float* dt = depth_test + (size_t)prob * test_stride;
-  const float* de = depth_est + (size_t)prob * hw;
-  const float* dg = depth_gt + (size_t)prob * hw;
-  if (tid <= VSD_MAX_TAU) bins[tid] = 0;
-  if (tid < 4) cnt[tid] = 0;
-  __syncthreads();
-  const int base = blockIdx.x * VSD_BLOCK, left = hw - base;  // base < hw: base + an offset below `left` cannot overflow
-  float ft[VSD_PER_THREAD], fe[VSD_PER_THREAD], fg[VSD_PER_THREAD];
-#pragma unroll
-  for (int j = 0; j < VSD_PER_THREAD; ++j) {
-    const int off = j * VSD_THREADS + tid;
-    const bool in = off < left;
-    ft[j] = in ? dt[base + off] : 0.0f;
-    fe[j] = in ? de[base + off] : 0.0f;
-    fg[j] = in ? dg[base + off] : 0.0f;
-  }
-  double cost[COST == 1 ? VSD_MAX_TAU : 1];
-  double rtau[COST == 1 ? VSD_MAX_TAU : 1];
-  if constexpr (COST == 1) {
-#pragma unroll
-    for (int t = 0; t < VSD_MAX_TAU; ++t) {
-      cost[t] = 0.0;
-      rtau[t] = t < n_tau ? 1.0 / taus.tau[t] : 0.0;
-    }
-  }
-  int inter = 0, uni = 0, n_vg = 0, n_gt = 0;
-#pragma unroll
-  for (int j = 0; j < VSD_PER_THREAD; ++j) {
-    const vsd_px px = vsd_pixel(ft[j], fe[j], fg[j], base + (j * VSD_THREADS + tid < left ? j * VSD_THREADS + tid : 0), width, cx, cy,
-                                rfx, rfy, delta, visib_mode);
-    if (px.vg && px.ve) {
-      ++inter;
-      if constexpr (COST == 0) {
-        int b = 0;
-#pragma unroll
-        for (int t = 0; t < VSD_MAX_TAU; ++t) b += (t < n_tau && px.d >= taus.tau[t]) ? 1 : 0;
-        if (b > 0) atomicAdd(&bins[b], 1);
-      } else {
-#pragma unroll
-        for (int t = 0; t < VSD_MAX_TAU; ++t) {
-          const double q = px.d * rtau[t];
-          cost[t] += q > 1.0 ? 1.0 : q;
-        }
-      }
-    }
-    uni += (px.vg || px.ve) ? 1 : 0;
-    n_vg += px.vg ? 1 : 0;
-    n_gt += px.gt ? 1 : 0;
-  }
-  inter = wave_sum(inter);
-  uni = wave_sum(uni);
-  n_vg = wave_sum(n_vg);
-  n_gt = wave_sum(n_gt);
-  if ((tid & 63) == 0) {
-    atomicAdd(&cnt[0], inter);
-    atomicAdd(&cnt[1], uni);
-    atomicAdd(&cnt[2], n_vg);
-    atomicAdd(&cnt[3], n_gt);
-  }
-  if constexpr (COST == 1) {
-#pragma unroll
-    for (int t = 0; t < VSD_MAX_TAU; ++t)
-      if (t < n_tau) red[t * VSD_THREADS + tid] = cost[t];
-  }
-  __syncthreads();
-  if constexpr (COST == 1) {
-    for (int s = VSD_THREADS / 2; s > 0; s >>= 1) {
-      if (tid < s)
-        for (int t = 0; t < n_tau; ++t) red[t * VSD_THREADS + tid] += red[t * VSD_THREADS + tid + s];
-      __syncthreads();
-    }
-  }
-  const size_t o = (size_t)prob * gridDim.x + blockIdx.x;
-  if (tid < n_tau) {
-    if constexpr (COST == 0) {
-      int c = 0;
-      for (int b = tid + 1; b <= n_tau; ++b) c += bins[b];
-      part_cost[o * n_tau + tid] = (double)c;
-    } else {
-      part_cost[o * n_tau + tid] = red[tid * VSD_THREADS];
-    }
-  }
-  if (tid < 4) part_cnt[4 * o + tid] = cnt[tid];
-}
-
-// one thread per (problem, tau): the blocks' partials in block order
-__global__ void vsd_multi_final_kernel(int n, int nblk, int n_tau, const double* __restrict__ part_cost, const int* __restrict__ part_cnt,
-                                       double* __restrict__ e, long long* __restrict__ inter_out, long long* __restrict__ union_out,
-                                       long long* __restrict__ visib_gt_out, long long* __restrict__ px_gt_out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n * n_tau) return;
-  const int prob = i / n_tau, t = i - prob * n_tau;
-  double cost = 0.0;
-  long long inter = 0, uni = 0, n_vg = 0, n_gt = 0;
-  for (int b = 0; b < nblk; ++b) {
-    const size_t o = (size_t)prob * nblk + b;
-    cost += part_cost[o * n_tau + t];
-    inter += part_cnt[4 * o];
-    uni += part_cnt[4 * o + 1];
-    n_vg += part_cnt[4 * o + 2];
-    n_gt += part_cnt[4 * o + 3];
-  }
-  e[i] = uni > 0 ? (cost + (double)(uni - inter)) / (double)uni : 1.0;
-  if (t != 0) return;
-  if (inter_out) inter_out[prob] = inter;
-  if (union_out) union_out[prob] = uni;
-  if (visib_gt_out) visib_gt_out[prob] = n_vg;
-  if (px_gt_out) px_gt_out[prob] = n_gt;
-}
-
-extern "C" size_t pp_vsd_multi_workspace_bytes(int n, int width, int height, int n_tau) {
-  if (n <= 0 || width <= 0 || height <= 0 || n_tau <= 0 || n_tau > VSD_MAX_TAU) return 0;
-  const size_t nblk = ((size_t)width * height + VSD_BLOCK - 1) / VSD_BLOCK;
-  return pp_align256((size_t)n * nblk * n_tau * sizeof(double)) + (size_t)n * nblk * 4 * sizeof(int);
-}
-
-extern "C" int pp_vsd_multi_f64(pp_ctx* ctx, int n, int width, int height, const float* depth_test, long long test_stride,
-                                const float* depth_est, const float* depth_gt, const double* K4, double delta, int n_tau,
-                                const double* taus, int cost_type, int visib_mode, void* workspace, double* e, long long* inter,
-                                long long* uni, long long* visib_gt, long long* px_gt) {
-  PP_REQUIRE_CTX(ctx);
-  PP_CHECK_ARG(ctx, n > 0 && n <= 65535 && width > 0 && height > 0 && (long long)width * height <= 0x7FFFFFFFLL, PP_ERR_SHAPE,
-               "pp_vsd_multi_f64: need 1..65535 problems and a non-empty image");
-  PP_CHECK_ARG(ctx, n_tau >= 1 && n_tau <= VSD_MAX_TAU, PP_ERR_SHAPE, "pp_vsd_multi_f64: need 1..%d taus, got %d", VSD_MAX_TAU, n_tau);
-  PP_CHECK_ARG(ctx, depth_test && depth_est && depth_gt && K4 && taus && workspace && e, PP_ERR_ARG, "pp_vsd_multi_f64: null argument");
-  PP_CHECK_ARG(ctx, test_stride == 0 || test_stride == (long long)width * height, PP_ERR_ARG,
-               "pp_vsd_multi_f64: test_stride must be 0 (one shared scene depth) or width * height");
-  PP_CHECK_ARG(ctx, cost_type == 0 || cost_type == 1, PP_ERR_ARG, "pp_vsd_multi_f64: cost_type must be 0 (step) or 1 (tlinear)");
-  PP_CHECK_ARG(ctx, visib_mode == 0 || visib_mode == 1, PP_ERR_ARG, "pp_vsd_multi_f64: visib_mode must be 0 (bop18) or 1 (bop19)");
-  vsd_taus tv;
-  for (int t = 0; t < VSD_MAX_TAU; ++t) {
-    tv.tau[t] = t < n_tau ? taus[t] : 0.0;
-    // (written so that a NaN is refused too)
-    PP_CHECK_ARG(ctx, t >= n_tau || (taus[t] > 0.0 && (t == 0 || taus[t] > taus[t - 1])), PP_ERR_ARG,
-                 "pp_vsd_multi_f64: taus must be positive and strictly increasing (tau[%d] = %g)", t, t < n_tau ? taus[t] : 0.0);
-  }
-  const int hw = width * height, nblk = (hw + VSD_BLOCK - 1) / VSD_BLOCK;
-  double* part_cost = (double*)workspace;
-  int* part_cnt = (int*)((char*)workspace + pp_align256((size_t)n * nblk * n_tau * sizeof(double)));
-  auto partial = cost_type == 0 ? vsd_multi_partial_kernel<0> : vsd_multi_partial_kernel<1>;
-  hipLaunchKernelGGL(partial, dim3(nblk, n), dim3(VSD_THREADS), 0, ctx->stream, width, hw, depth_test, test_stride, depth_est,
-                     depth_gt, K4, (float)delta, n_tau, tv, visib_mode, part_cost, part_cnt);
-  const int total = n * n_tau;
-  hipLaunchKernelGGL(vsd_multi_final_kernel, dim3((total + 63) / 64), dim3(64), 0, ctx->stream, n, nblk, n_tau,
-                     (const double*)part_cost, (const int*)part_cnt, e, inter, uni, visib_gt, px_gt);
-  PP_CHECK_LAUNCH(ctx, "pp_vsd_multi_f64");
-  return PP_OK;
-}
-
-// ---- scene ground truth from rendered instances (masks, boxes, visibility) -------------------------------------------------
-// What bop_toolkit's calc_gt_masks / calc_gt_info write beforehand and annotation_scripts/annotate_BOP.py:363-378, 420, 461-471
-// reads back (mask_visib/*.png, scene_gt_info.json), computed from the depth renders of a scene's instances.  Two passes:
-//   1. scene:    per (scene, image pixel) the scene depth -- the given sensor depth or, without one, the nearest positive
-//                instance depth -- then the id image: the scene's instances from the last to the first, the first one whose
-//                'bop19' visibility mask holds the pixel wins, which is the later instance overwriting the earlier one
-//                (annotate_BOP.py:373)
-//   2. instance: per (instance, canvas pixel) the three pixel counts, both boxes and the optional masks; per-workgroup partials
-//                (LDS integer atomics), then one wave per instance folds them
-// A thread owns four pixels of a row whose image column is a multiple of 4: depths come in as one 16-byte load and bytes go out
-// as one packed 4-byte store where the address allows, element by element otherwise.  Integer counts, minima and maxima only:
-// the same bits whatever order the atomics run in.
-#define SGT_THREADS 256
-#define SGT_PART 11  // n_all, n_valid, n_visib, then (x_min, x_max, y_min, y_max) of the object and of its visible mask
-
-// row[c0 .. c0 + 3] of a row of w floats, 0 where the column is outside [0, w)
-__device__ __forceinline__ void load4_f32(const float* __restrict__ row, int c0, int w, float (&v)[4]) {
-  if (c0 >= 0 && c0 + 3 < w && (reinterpret_cast<uintptr_t>(row + c0) & 15u) == 0) {
-    const float4 q = *reinterpret_cast<const float4*>(row + c0);
-    v[0] = q.x;
-    v[1] = q.y;
-    v[2] = q.z;
-    v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = (c0 + k >= 0 && c0 + k < w) ? row[c0 + k] : 0.0f;
-  }
-}
-
-// the columns of v inside [0, w) to row[c0 .. c0 + 3]; c0 >= 0
-__device__ __forceinline__ void store4_f32(float* __restrict__ row, int c0, int w, const float (&v)[4]) {
-  if (c0 + 3 < w && (reinterpret_cast<uintptr_t>(row + c0) & 15u) == 0) {
-    *reinterpret_cast<float4*>(row + c0) = make_float4(v[0], v[1], v[2], v[3]);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (c0 + k < w) row[c0 + k] = v[k];
-  }
-}
-
-__device__ __forceinline__ void store4_u8(unsigned char* __restrict__ row, int c0, int w, const unsigned char (&v)[4]) {
-  if (c0 + 3 < w && (reinterpret_cast<uintptr_t>(row + c0) & 3u) == 0) {
-    *reinterpret_cast<unsigned*>(row + c0) = (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24);
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (c0 + k < w) row[c0 + k] = v[k];
-  }
-}
-
-__device__ __forceinline__ int wave_min(int v) {
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-__device__ __forceinline__ int wave_max(int v) {
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-// the instances [i0, i1) of a scene; whatever the device copy of the offsets holds, the range stays inside the stack
-__device__ __forceinline__ void scene_range(const int* __restrict__ scene_offsets, int scene, int n_inst, int* i0, int* i1) {
-  *i0 = min(max(scene_offsets[scene], 0), n_inst);
-  *i1 = min(max(scene_offsets[scene + 1], *i0), n_inst);
-}
-
-// grid (blocks of SGT_THREADS groups of 4 image pixels, scenes)
-__global__ void __launch_bounds__(SGT_THREADS)
-scene_gt_scene_kernel(int n_inst, int canvas_w, int canvas_h, int width, int height, int off_x, int off_y,
-                      const float* __restrict__ stack, const int* __restrict__ scene_offsets, const float* __restrict__ depth_test,
-                      long long test_stride, const double* __restrict__ K4, float delta, float* __restrict__ scene_depth,
-                      unsigned char* __restrict__ id_image) {
-  const int groups = (width + 3) / 4, gi = blockIdx.x * SGT_THREADS + threadIdx.x, scene = blockIdx.y;
-  if (gi >= height * groups) return;
-  const int r = gi / groups, c0 = (gi - r * groups) * 4;
-  int i0, i1;
-  scene_range(scene_offsets, scene, n_inst, &i0, &i1);
-  const size_t cpx = (size_t)canvas_w * canvas_h, hw = (size_t)width * height;
-  const float* win = stack + (size_t)(r + off_y) * canvas_w + off_x;  // row r of the window in instance 0's canvas
-  float dt[4], dg[4];
-  if (depth_test) {
-    load4_f32(depth_test + (size_t)scene * test_stride + (size_t)r * width, c0, width, dt);
-  } else {
-    dt[0] = dt[1] = dt[2] = dt[3] = 0.0f;
-    for (int i = i0; i < i1; ++i) {
-      load4_f32(win + i * cpx, c0, width, dg);
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (dg[k] > 0.0f && (dt[k] == 0.0f || dg[k] < dt[k])) dt[k] = dg[k];
-    }
-    store4_f32(scene_depth + scene * hw + (size_t)r * width, c0, width, dt);
-  }
-  unsigned char id[4] = {0, 0, 0, 0};
-  int open = 0;  // bit k: pixel c0 + k is in the image and no instance has claimed it yet
-#pragma unroll
-  for (int k = 0; k < 4; ++k) open |= (c0 + k < width) ? 1 << k : 0;
-  for (int i = i1 - 1; i >= i0 && open; --i) {
-    load4_f32(win + i * cpx, c0, width, dg);
-    const double* kk = K4 + 4 * (size_t)i;
-    const double cx = kk[2], cy = kk[3], rfx = 1.0 / kk[0], rfy = 1.0 / kk[1];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if (!((open >> k) & 1) || !(dg[k] > 0.0f)) continue;
-      const double t_ = dist_px(dt[k], r, c0 + k, cx, cy, rfx, rfy);
-      const double g_ = dist_px(dg[k], r, c0 + k, cx, cy, rfx, rfy);
-      if (visib_bop19(t_, g_, delta)) {
-        id[k] = (unsigned char)(i - i0 + 1);
-        open &= ~(1 << k);
-      }
-    }
-  }
-  store4_u8(id_image + scene * hw + (size_t)r * width, c0, width, id);
-}
-
-// grid (blocks of SGT_THREADS groups of 4 canvas pixels, instances).  A canvas row is cut into `groups` groups that start at
-// canvas column 4 g - shift, shift = (4 - off_x % 4) % 4, so that a group's first image column is a multiple of 4.
-// part [instance][block][SGT_PART]; box coordinates are image coordinates (canvas minus the window's offset).
-__global__ void __launch_bounds__(SGT_THREADS)
-scene_gt_inst_kernel(int n_scene, int canvas_w, int canvas_h, int width, int height, int off_x, int off_y, int shift, int groups,
-                     const float* __restrict__ stack, const int* __restrict__ scene_offsets, const float* __restrict__ test,
-                     long long test_stride, const double* __restrict__ K4, float delta, int* __restrict__ part,
-                     unsigned char* __restrict__ mask_full, unsigned char* __restrict__ mask_visib) {
-  __shared__ int acc[SGT_PART];
-  const int tid = threadIdx.x, inst = blockIdx.y, gi = blockIdx.x * SGT_THREADS + tid;
-  if (tid < SGT_PART) acc[tid] = tid < 3 ? 0 : (((tid - 3) & 1) ? INT_MIN : INT_MAX);
-  __syncthreads();
-  int n_all = 0, n_valid = 0, n_vis = 0;
-  int ox0 = INT_MAX, ox1 = INT_MIN, oy0 = INT_MAX, oy1 = INT_MIN, vx0 = INT_MAX, vx1 = INT_MIN, vy0 = INT_MAX, vy1 = INT_MIN;
-  if (gi < canvas_h * groups) {
-    const int R = gi / groups, C0 = (gi - R * groups) * 4 - shift, r = R - off_y, c0 = C0 - off_x;  // c0 is a multiple of 4
-    const bool row_in = r >= 0 && r < height;
-    const size_t hw = (size_t)width * height;
-    float dg[4], dt[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    load4_f32(stack + (size_t)inst * canvas_w * canvas_h + (size_t)R * canvas_w, C0, canvas_w, dg);
-    if (row_in) {
-      int lo = 0, hi = n_scene;  // scene_offsets[lo] <= inst < scene_offsets[hi]; lo stays in [0, n_scene)
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (scene_offsets[mid] <= inst) lo = mid; else hi = mid;
-      }
-      load4_f32(test + (size_t)lo * test_stride + (size_t)r * width, c0, width, dt);
-    }
-    const double* kk = K4 + 4 * (size_t)inst;
-    const double cx = kk[2], cy = kk[3], rfx = 1.0 / kk[0], rfy = 1.0 / kk[1];
-    unsigned char mf[4], mv[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int c = c0 + k;
-      const bool gt = dg[k] > 0.0f;
-      bool vis = false;
-      if (gt) {
-        ++n_all;
-        ox0 = min(ox0, c);
-        ox1 = max(ox1, c);
-        oy0 = min(oy0, r);
-        oy1 = max(oy1, r);
-        if (row_in && c >= 0 && c < width) {
-          n_valid += dt[k] > 0.0f ? 1 : 0;
-          vis = visib_bop19(dist_px(dt[k], r, c, cx, cy, rfx, rfy), dist_px(dg[k], r, c, cx, cy, rfx, rfy), delta);
-        }
-      }
-      if (vis) {
-        ++n_vis;
-        vx0 = min(vx0, c);
-        vx1 = max(vx1, c);
-        vy0 = min(vy0, r);
-        vy1 = max(vy1, r);
-      }
-      mf[k] = gt ? 255 : 0;
-      mv[k] = vis ? 255 : 0;
-    }
-    if (row_in && c0 >= 0 && c0 < width) {
-      if (mask_full) store4_u8(mask_full + inst * hw + (size_t)r * width, c0, width, mf);
-      if (mask_visib) store4_u8(mask_visib + inst * hw + (size_t)r * width, c0, width, mv);
-    }
-  }
-  const int sums[3] = {wave_sum(n_all), wave_sum(n_valid), wave_sum(n_vis)};
-  const int mins[4] = {wave_min(ox0), wave_min(oy0), wave_min(vx0), wave_min(vy0)};
-  const int maxs[4] = {wave_max(ox1), wave_max(oy1), wave_max(vx1), wave_max(vy1)};
-  if ((tid & 63) == 0) {
-    for (int k = 0; k < 3; ++k) atomicAdd(&acc[k], sums[k]);
-    // acc: obj x_min, x_max, y_min, y_max, visible x_min, x_max, y_min, y_max
-    for (int k = 0; k < 4; ++k) {
-      atomicMin(&acc[3 + 2 * k], mins[k]);
-      atomicMax(&acc[4 + 2 * k], maxs[k]);
-    }
-  }
-  __syncthreads();
-  if (tid < SGT_PART) part[((size_t)inst * gridDim.x + blockIdx.x) * SGT_PART + tid] = acc[tid];
-}
-
-// one wave per instance: the blocks' partials -> px_count [3], bbox_obj (x, y, w, h), bbox_visib (x, y, w, h)
-__global__ void __launch_bounds__(64)
-scene_gt_final_kernel(int nblk, const int* __restrict__ part, long long* __restrict__ px_count, int* __restrict__ bbox_obj,
-                      int* __restrict__ bbox_visib) {
-  const int inst = blockIdx.x, lane = threadIdx.x;
-  int v[SGT_PART];
-#pragma unroll
-  for (int k = 0; k < SGT_PART; ++k) v[k] = k < 3 ? 0 : (((k - 3) & 1) ? INT_MIN : INT_MAX);
-  for (int b = lane; b < nblk; b += 64) {
-    const int* p = part + ((size_t)inst * nblk + b) * SGT_PART;
-#pragma unroll
-    for (int k = 0; k < SGT_PART; ++k) v[k] = k < 3 ? v[k] + p[k] : (((k - 3) & 1) ? max(v[k], p[k]) : min(v[k], p[k]));
-  }
-#pragma unroll
-  for (int k = 0; k < SGT_PART; ++k) v[k] = k < 3 ? wave_sum(v[k]) : (((k - 3) & 1) ? wave_max(v[k]) : wave_min(v[k]));
-  if (lane != 0) return;
-  for (int k = 0; k < 3; ++k) px_count[3 * (size_t)inst + k] = v[k];
-  const bool seen = v[2] > 0;  // calc_gt_info: both boxes are (-1, -1, -1, -1) when nothing is visible
-  for (int b = 0; b < 2; ++b) {
-    int* box = (b ? bbox_visib : bbox_obj) + 4 * (size_t)inst;
-    const int* m = v + 3 + 4 * b;  // x_min, x_max, y_min, y_max
-    box[0] = seen ? m[0] : -1;
-    box[1] = seen ? m[2] : -1;
-    box[2] = seen ? m[1] - m[0] : -1;
-    box[3] = seen ? m[3] - m[2] : -1;
-  }
-}
-
-#define SGT_MAX_PER_SCENE 255  // the id image is uint8 and 0 is the background
-
-static bool scene_gt_shape_ok(int n_inst, int canvas_w, int canvas_h) {
-  return n_inst > 0 && n_inst <= 65535 && canvas_w > 0 && canvas_h > 0 && canvas_w <= 16384 && canvas_h <= 16384;
-}
-
-// workgroups of scene_gt_inst_kernel per instance, at the window offset that needs the most groups per row
-static size_t scene_gt_blocks(int canvas_w, int canvas_h, int shift) {
-  const size_t groups = ((size_t)canvas_w + shift + 3) / 4;
-  return (groups * canvas_h + SGT_THREADS - 1) / SGT_THREADS;
-}
-
-extern "C" size_t pp_scene_gt_workspace_bytes(int n_inst, int canvas_w, int canvas_h) {
-  if (!scene_gt_shape_ok(n_inst, canvas_w, canvas_h)) return 0;
-  return (size_t)n_inst * scene_gt_blocks(canvas_w, canvas_h, 3) * SGT_PART * sizeof(int);
-}
-
-extern "C" int pp_scene_gt_info(pp_ctx* ctx, int n_inst, int n_scene, const int* scene_offsets_host, const int* scene_offsets_dev,
-                                int canvas_w, int canvas_h, int width, int height, int off_x, int off_y, const float* depth_stack,
-                                const double* K4, const float* depth_test, long long test_stride, double delta, void* workspace,
-                                size_t workspace_bytes, float* scene_depth, unsigned char* id_image, long long* px_count,
-                                int* bbox_obj, int* bbox_visib, unsigned char* mask_full, unsigned char* mask_visib) {
-  PP_REQUIRE_CTX(ctx);
-  PP_CHECK_ARG(ctx, scene_gt_shape_ok(n_inst, canvas_w, canvas_h) && n_scene > 0 && n_scene <= 65535, PP_ERR_SHAPE,
-               "pp_scene_gt_info: need 1..65535 instances, 1..65535 scenes and a 1..16384 canvas");
-  PP_CHECK_ARG(ctx, width > 0 && height > 0 && off_x >= 0 && off_y >= 0 && off_x <= canvas_w - width && off_y <= canvas_h - height,
-               PP_ERR_SHAPE, "pp_scene_gt_info: the %d x %d window at (%d, %d) must lie inside the %d x %d canvas", width, height,
-               off_x, off_y, canvas_w, canvas_h);
-  PP_CHECK_ARG(ctx, scene_offsets_host && scene_offsets_dev && depth_stack && K4 && workspace && id_image && px_count && bbox_obj &&
-                        bbox_visib, PP_ERR_ARG, "pp_scene_gt_info: null argument");
-  PP_CHECK_ARG(ctx, (depth_test != nullptr) != (scene_depth != nullptr), PP_ERR_ARG,
-               "pp_scene_gt_info: give depth_test, or scene_depth for the depth composed from the instances, not both");
-  PP_CHECK_ARG(ctx, !depth_test || test_stride == 0 || test_stride == (long long)width * height, PP_ERR_ARG,
-               "pp_scene_gt_info: test_stride must be 0 (one depth image shared by the scenes) or width * height");
-  PP_CHECK_ARG(ctx, delta >= 0.0, PP_ERR_ARG, "pp_scene_gt_info: delta must not be negative");  // (a NaN is refused too)
-  PP_CHECK_ARG(ctx, scene_offsets_host[0] == 0 && scene_offsets_host[n_scene] == n_inst, PP_ERR_ARG,
-               "pp_scene_gt_info: scene_offsets must run from 0 to n_inst");
-  for (int s = 0; s < n_scene; ++s) {
-    const int m = scene_offsets_host[s + 1] - scene_offsets_host[s];
-    PP_CHECK_ARG(ctx, m >= 0, PP_ERR_ARG, "pp_scene_gt_info: scene_offsets must not decrease (scene %d)", s);
-    PP_CHECK_ARG(ctx, m <= SGT_MAX_PER_SCENE, PP_ERR_SHAPE, "pp_scene_gt_info: scene %d has %d instances, the uint8 id image holds %d",
-                 s, m, SGT_MAX_PER_SCENE);
-  }
-  const int shift = (4 - off_x % 4) % 4, groups = (canvas_w + shift + 3) / 4;
-  const size_t nblk = scene_gt_blocks(canvas_w, canvas_h, shift), need = (size_t)n_inst * nblk * SGT_PART * sizeof(int);
-  PP_CHECK_ARG(ctx, workspace_bytes >= need, PP_ERR_ARG, "pp_scene_gt_info: workspace of %zu bytes, need %zu", workspace_bytes, need);
-  const size_t hw = (size_t)width * height;
-  const int scene_blocks = (int)((((size_t)width + 3) / 4 * height + SGT_THREADS - 1) / SGT_THREADS);
-  hipLaunchKernelGGL(scene_gt_scene_kernel, dim3(scene_blocks, n_scene), dim3(SGT_THREADS), 0, ctx->stream, n_inst, canvas_w, canvas_h,
-                     width, height, off_x, off_y, depth_stack, scene_offsets_dev, depth_test, test_stride, K4, (float)delta, scene_depth,
-                     id_image);
-  const float* test = depth_test ? depth_test : scene_depth;
-  hipLaunchKernelGGL(scene_gt_inst_kernel, dim3((unsigned)nblk, n_inst), dim3(SGT_THREADS), 0, ctx->stream, n_scene, canvas_w, canvas_h,
-                     width, height, off_x, off_y, shift, groups, depth_stack, scene_offsets_dev, test,
-                     depth_test ? test_stride : (long long)hw, K4, (float)delta, (int*)workspace, mask_full, mask_visib);
-  hipLaunchKernelGGL(scene_gt_final_kernel, dim3(n_inst), dim3(64), 0, ctx->stream, (int)nblk, (const int*)workspace, px_count, bbox_obj,
-                     bbox_visib);
-  PP_CHECK_LAUNCH(ctx, "pp_scene_gt_info");
-  return PP_OK;
-}
-
-// ---- a scene's image from its instances' colour renders ---------------------------------------------------------------------
-// Per (scene, pixel): id k > 0 of pp_scene_gt_info's id image selects the colour of instance scene_offsets[scene] + k - 1 of
-// the uint8 stack (pp_render_rgbd outputs in scene order), anything else the background -- the scene's image or a constant.
-// Inputs are RGB; the output is RGB or, reversed per pixel, BGR.  A thread owns four pixels of a row (one packed load of the
-// ids, three packed stores where the addresses allow).  Bytes are selected, never computed.
-__global__ void __launch_bounds__(SGT_THREADS)
-scene_compose_kernel(int n_inst, int width, int height, const int* __restrict__ scene_offsets, const unsigned char* __restrict__ id_image,
-                     const unsigned char* __restrict__ colors, const unsigned char* __restrict__ background, unsigned bg_const, int bgr,
-                     unsigned char* __restrict__ out) {
-  const int groups = (width + 3) / 4, gi = blockIdx.x * SGT_THREADS + threadIdx.x, scene = blockIdx.y;
-  if (gi >= height * groups) return;
-  const int r = gi / groups, c0 = (gi - r * groups) * 4;
-  int i0, i1;
-  scene_range(scene_offsets, scene, n_inst, &i0, &i1);
-  const size_t hw = (size_t)width * height, p0 = (size_t)r * width + c0;
-  const unsigned char* ids = id_image + scene * hw + p0;
-  const bool whole = c0 + 3 < width;
-  unsigned packed = 0;
-  if (whole && (reinterpret_cast<uintptr_t>(ids) & 3u) == 0) {
-    packed = *reinterpret_cast<const unsigned*>(ids);
-  } else {
-    for (int k = 0; k < 4; ++k)
-      if (c0 + k < width) packed |= (unsigned)ids[k] << (8 * k);
-  }
-  unsigned char v[12];
-  for (int k = 0; k < 4; ++k) {
-    const int id = (int)((packed >> (8 * k)) & 255u);
-    const unsigned char* src = nullptr;
-    if (c0 + k < width) {
-      if (id > 0 && id <= i1 - i0)
-        src = colors + ((size_t)(i0 + id - 1) * hw + p0 + k) * 3;
-      else if (background)
-        src = background + (scene * hw + p0 + k) * 3;
-    }
-    for (int j = 0; j < 3; ++j) {
-      const int jj = bgr ? 2 - j : j;
-      v[3 * k + j] = src ? src[jj] : (unsigned char)((bg_const >> (8 * jj)) & 255u);
-    }
-  }
-  unsigned char* o = out + (scene * hw + p0) * 3;
-  if (whole && (reinterpret_cast<uintptr_t>(o) & 3u) == 0) {
-    for (int j = 0; j < 3; ++j)
-      reinterpret_cast<unsigned*>(o)[j] = (unsigned)v[4 * j] | ((unsigned)v[4 * j + 1] << 8) | ((unsigned)v[4 * j + 2] << 16) | ((unsigned)v[4 * j + 3] << 24);
-  } else {
-    for (int k = 0; k < 12; ++k)
-      if (c0 + k / 3 < width) o[k] = v[k];
-  }
-}
-
-extern "C" int pp_scene_compose_u8(pp_ctx* ctx, int n_inst, int n_scene, const int* scene_offsets_host, const int* scene_offsets_dev,
-                                   int width, int height, const unsigned char* id_image, const unsigned char* colors,
-                                   const unsigned char* background, const unsigned char* bg_const, int channel_order,
-                                   unsigned char* out) {
-  PP_REQUIRE_CTX(ctx);
-  PP_CHECK_ARG(ctx, scene_gt_shape_ok(n_inst, width, height) && n_scene > 0 && n_scene <= 65535, PP_ERR_SHAPE,
-               "pp_scene_compose_u8: need 1..65535 instances, 1..65535 scenes and a 1..16384 image");
-  PP_CHECK_ARG(ctx, scene_offsets_host && scene_offsets_dev && id_image && colors && out && (background || bg_const), PP_ERR_ARG,
-               "pp_scene_compose_u8: null argument (give a background image or a constant)");
-  PP_CHECK_ARG(ctx, channel_order == 0 || channel_order == 1, PP_ERR_ARG, "pp_scene_compose_u8: channel_order must be 0 (RGB) or 1 (BGR)");
-  PP_CHECK_ARG(ctx, scene_offsets_host[0] == 0 && scene_offsets_host[n_scene] == n_inst, PP_ERR_ARG,
-               "pp_scene_compose_u8: scene_offsets must run from 0 to n_inst");
-  for (int s = 0; s < n_scene; ++s) {
-    const int m = scene_offsets_host[s + 1] - scene_offsets_host[s];
-    PP_CHECK_ARG(ctx, m >= 0, PP_ERR_ARG, "pp_scene_compose_u8: scene_offsets must not decrease (scene %d)", s);
-    PP_CHECK_ARG(ctx, m <= SGT_MAX_PER_SCENE, PP_ERR_SHAPE, "pp_scene_compose_u8: scene %d has %d instances, the uint8 id image holds %d",
-                 s, m, SGT_MAX_PER_SCENE);
-  }
-  const unsigned bg = background ? 0u : (unsigned)bg_const[0] | ((unsigned)bg_const[1] << 8) | ((unsigned)bg_const[2] << 16);
-  const int blocks = (int)((((size_t)width + 3) / 4 * height + SGT_THREADS - 1) / SGT_THREADS);
-  hipLaunchKernelGGL(scene_compose_kernel, dim3(blocks, n_scene), dim3(SGT_THREADS), 0, ctx->stream, n_inst, width, height,
-                     scene_offsets_dev, id_image, colors, background, bg, channel_order, out);
-  PP_CHECK_LAUNCH(ctx, "pp_scene_compose_u8");
-  return PP_OK;
-}
-
-// ---- the textured raster kernel of the colour renderer (declared there) ---------------------------------------------------------
-#define RASTER_KERNEL render_rgbd_tex_raster_kernel
-#define RASTER_TEX true
-#define RASTER_TP_PARAM , tex_params tp
-#define RASTER_TP tp
-#include "render_rgbd_raster.inc"

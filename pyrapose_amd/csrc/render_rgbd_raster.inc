@@ -1,5 +1,6 @@
-// The raster kernel of the colour renderer, included by render.hip once per kernel: the raster workgroup is one text and only the
-// colour of the shading tail differs.  The includer defines RASTER_KERNEL (the kernel's name), RASTER_TEX (false: vertex colours
+// The raster kernel of the colour renderer, included by render.hip once per kernel: the raster phase is
+// render_raster_tile.inc (the depth pass's too); resolve, stores and shading are one text here and only the colour of the
+// shading tail differs.  The includer defines RASTER_KERNEL (the kernel's name), RASTER_TEX (false: vertex colours
 // [n_vert,3] in colors; true: texture coordinates [n_vert,2] there), RASTER_TP_PARAM (nothing, or the trailing tex_params
 // parameter) and RASTER_TP (the tex_params the shading tail is given).  Two plain kernels rather than one template: the untextured
 // one keeps the signature, the code and the place in the code object it had before the textured one existed.
@@ -15,48 +16,8 @@ RASTER_KERNEL(int n_vert, const int* __restrict__ faces, const rvtx* __restrict_
   const int pose = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
   const int r0 = (tile / tiles_x) * RT, c0 = (tile % tiles_x) * RT;
   const rvtx* vtx = vtx_all + (size_t)pose * n_vert;
-  for (int k = tid; k < RT * RT; k += RASTER_THREADS) zb[k] = ZKEY_EMPTY;
-  if (tid == 0) qn = 0;
-  __syncthreads();
-  const size_t b = (size_t)pose * n_tiles + tile;
-  const int l0 = offsets[b], l1 = offsets[b + 1];
-  for (int base = l0; base < l1; base += RASTER_THREADS) {
-    if (base + tid < l1) {
-      const int tri = list[base + tid];
-      tri_setup T;
-      if (setup_triangle(vtx, n_vert, faces, tri, width, height, &T)) {
-        const int a0 = max(T.c0, c0), a1 = min(T.c1, c0 + RT - 1), b0 = max(T.r0, r0), b1 = min(T.r1, r0 + RT - 1);
-        const int area = (a1 - a0 + 1) * (b1 - b0 + 1);
-        if (a0 <= a1 && b0 <= b1) {
-          if (area <= RASTER_SMALL_PX) {
-            for (int r = b0; r <= b1; ++r)
-              for (int c = a0; c <= a1; ++c) raster_px(zb, T, tri, r, c, r0, c0, zn, zf);
-          } else {
-            queue[atomicAdd(&qn, 1)] = tri;
-          }
-        }
-      }
-    }
-    __syncthreads();
-    raster_queue(zb, queue, qn, vtx, n_vert, faces, width, height, r0, c0, zn, zf);
-    __syncthreads();
-    if (tid == 0) qn = 0;
-    __syncthreads();
-  }
-  const int nb = big_n[pose];
-  for (int base = 0; base < nb; base += RASTER_THREADS) {
-    if (base + tid < nb) {
-      const int tri = big[(size_t)pose * n_tri + base + tid];
-      tri_setup T;
-      if (setup_triangle(vtx, n_vert, faces, tri, width, height, &T) && T.c0 < c0 + RT && T.c1 >= c0 && T.r0 < r0 + RT && T.r1 >= r0)
-        queue[atomicAdd(&qn, 1)] = tri;
-    }
-    __syncthreads();
-    raster_queue(zb, queue, qn, vtx, n_vert, faces, width, height, r0, c0, zn, zf);
-    __syncthreads();
-    if (tid == 0) qn = 0;
-    __syncthreads();
-  }
+#define RASTER_EMPTY ZKEY_EMPTY
+#include "render_raster_tile.inc"
   // the tile, 4 pixels of one row per thread
   const int r = r0 + tid / (RT / 4), c = c0 + (tid % (RT / 4)) * 4;
   if (r >= height || c >= width) return;

@@ -790,6 +790,38 @@ RENDER_SHADING = {"flat": 0, "phong": 1}
 RENDER_OUTPUTS = {"depth": _F32, "tri_id": _I32, "rgb_f32": _F32, "rgb": _U8}  # in the ABI's order
 
 
+RENDER_FILTER = {"nearest": 0, "bilinear": 1}
+RENDER_WRAP = {"clamp": 0, "repeat": 1}
+
+
+def _render_mesh(what, choices, outputs, verts, faces, R, t, K4):
+    """what render_rgbd / render_rgbd_tex check first; choices: {kind: (value, its table)} -> (outputs as a tuple, verts, faces,
+    R, t, K4, n, n_vert, n_tri)"""
+    for kind, (value, table) in choices.items():
+        if value not in table:
+            raise ValueError("%s: unknown %s %r (%s)" % (what, kind, value, " | ".join(table)))
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+    unknown = [o for o in outputs if o not in RENDER_OUTPUTS]
+    if unknown or not outputs:
+        raise ValueError("%s: outputs must name at least one of %s, got %r" % (what, " | ".join(RENDER_OUTPUTS), outputs))
+    verts = _arg(what, "verts", verts, _F64, (None, 3))
+    faces = _arg(what, "faces", faces, _I32, (None, 3))
+    R = _arg(what, "R", R, _F64, (None, 3, 3))
+    n, nv, nt = int(R.shape[0]), int(verts.shape[0]), int(faces.shape[0])
+    return outputs, verts, faces, R, _arg(what, "t", t, _F64, (n, 3)), _arg(what, "K4", K4, _F64, (n, 4)), n, nv, nt
+
+
+def _render_frame(what, outputs, verts, n, nv, nt, width, height, normals, light_cam_pos, bg_color, nbytes, texture=""):
+    """and last: -> (normals, light, bg as the ABI takes them, workspace of nbytes, dict of the output tensors)"""
+    normals = _arg(what, "normals", normals, _F64, (nv, 3), optional=True)
+    light = (C.c_double * 3)(*(float(v) for v in np.asarray(light_cam_pos, np.float64).reshape(3)))
+    bg = (C.c_double * 3)(*(float(v) for v in np.asarray(bg_color, np.float64).reshape(3)))
+    ws = _workspace(nbytes, "%s: unsupported shape (n=%d, vertices=%d, triangles=%d, %dx%d%s)" % (what, n, nv, nt, width, height, texture))
+    out = {k: _out(verts, (n, int(height), int(width)) + ((3,) if k.startswith("rgb") else ()), dt)
+           for k, dt in RENDER_OUTPUTS.items() if k in outputs}
+    return normals, light, bg, ws, out
+
+
 def render_rgbd(ctx, verts, faces, R, t, K4, width, height, colors=None, normals=None, clip_near=100.0, clip_far=10000.0,
                 shading="phong", ambient_weight=0.5, light_cam_pos=(0.0, 0.0, 0.0), bg_color=(0.0, 0.0, 0.0), outputs=("rgb", "depth")):
     """Shaded colour, depth and triangle ids of one mesh at n poses (pp_render_rgbd): cuda tensors as in render_depth plus
@@ -797,34 +829,14 @@ def render_rgbd(ctx, verts, faces, R, t, K4, width, height, colors=None, normals
     shading); shading 'flat' | 'phong'; light_cam_pos in the OpenCV camera frame; outputs: any of 'rgb' (uint8 [n,h,w,3], RGB),
     'rgb_f32' (float32 [n,h,w,3]), 'depth' (float32 [n,h,w], the bits of render_depth), 'tri_id' (int32 [n,h,w], -1 = none)
     -> dict of the requested outputs."""
-    if shading not in RENDER_SHADING:
-        raise ValueError("render_rgbd: unknown shading %r (flat | phong)" % (shading,))
-    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
-    unknown = [o for o in outputs if o not in RENDER_OUTPUTS]
-    if unknown or not outputs:
-        raise ValueError("render_rgbd: outputs must name at least one of %s, got %r" % (" | ".join(RENDER_OUTPUTS), outputs))
-    verts = _arg("render_rgbd", "verts", verts, _F64, (None, 3))
-    faces = _arg("render_rgbd", "faces", faces, _I32, (None, 3))
-    R = _arg("render_rgbd", "R", R, _F64, (None, 3, 3))
-    n, nv, nt = int(R.shape[0]), int(verts.shape[0]), int(faces.shape[0])
-    t = _arg("render_rgbd", "t", t, _F64, (n, 3))
-    K4 = _arg("render_rgbd", "K4", K4, _F64, (n, 4))
+    outputs, verts, faces, R, t, K4, n, nv, nt = _render_mesh("render_rgbd", {"shading": (shading, RENDER_SHADING)}, outputs, verts, faces, R, t, K4)
     colors = _arg("render_rgbd", "colors", colors, _F64, (nv, 3), optional=True)
-    normals = _arg("render_rgbd", "normals", normals, _F64, (nv, 3), optional=True)
-    light = (C.c_double * 3)(*(float(v) for v in np.asarray(light_cam_pos, np.float64).reshape(3)))
-    bg = (C.c_double * 3)(*(float(v) for v in np.asarray(bg_color, np.float64).reshape(3)))
     nbytes = lib.pp_render_rgbd_workspace_bytes(n, nv, nt, int(width), int(height))
-    ws = _workspace(nbytes, "render_rgbd: unsupported shape (n=%d, vertices=%d, triangles=%d, %dx%d)" % (n, nv, nt, width, height))
-    out = {k: _out(verts, (n, int(height), int(width)) + ((3,) if k.startswith("rgb") else ()), dt)
-           for k, dt in RENDER_OUTPUTS.items() if k in outputs}
+    normals, light, bg, ws, out = _render_frame("render_rgbd", outputs, verts, n, nv, nt, width, height, normals, light_cam_pos, bg_color, nbytes)
     check(lib.pp_render_rgbd(ctx.handle, n, nv, _ptr(verts), _ptr(colors), _ptr(normals), nt, _ptr(faces), _ptr(R), _ptr(t), _ptr(K4),
                              int(width), int(height), float(clip_near), float(clip_far), RENDER_SHADING[shading], float(ambient_weight),
                              light, bg, _ptr(ws), nbytes, *[_ptr(out.get(k)) for k in RENDER_OUTPUTS]), ctx.handle, "pp_render_rgbd")
     return out
-
-
-RENDER_FILTER = {"nearest": 0, "bilinear": 1}
-RENDER_WRAP = {"clamp": 0, "repeat": 1}
 
 
 def render_rgbd_tex(ctx, verts, faces, R, t, K4, width, height, uv=None, tex=None, filter="nearest", wrap="clamp", normals=None,
@@ -833,33 +845,14 @@ def render_rgbd_tex(ctx, verts, faces, R, t, K4, width, height, uv=None, tex=Non
     """render_rgbd of a textured mesh (pp_render_rgbd_tex): in place of colors, uv float64 [n_vert,2] and tex, a cuda uint8
     tensor [th,tw,4] (RGBX, the rows in the image file's order: v = 0 is its bottom row; the fourth byte is ignored), both
     needed for 'rgb' / 'rgb_f32'; filter 'nearest' | 'bilinear'; wrap 'clamp' | 'repeat'.  Everything else as in render_rgbd."""
-    if shading not in RENDER_SHADING:
-        raise ValueError("render_rgbd_tex: unknown shading %r (flat | phong)" % (shading,))
-    if filter not in RENDER_FILTER:
-        raise ValueError("render_rgbd_tex: unknown filter %r (nearest | bilinear)" % (filter,))
-    if wrap not in RENDER_WRAP:
-        raise ValueError("render_rgbd_tex: unknown wrap %r (clamp | repeat)" % (wrap,))
-    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs)
-    unknown = [o for o in outputs if o not in RENDER_OUTPUTS]
-    if unknown or not outputs:
-        raise ValueError("render_rgbd_tex: outputs must name at least one of %s, got %r" % (" | ".join(RENDER_OUTPUTS), outputs))
-    verts = _arg("render_rgbd_tex", "verts", verts, _F64, (None, 3))
-    faces = _arg("render_rgbd_tex", "faces", faces, _I32, (None, 3))
-    R = _arg("render_rgbd_tex", "R", R, _F64, (None, 3, 3))
-    n, nv, nt = int(R.shape[0]), int(verts.shape[0]), int(faces.shape[0])
-    t = _arg("render_rgbd_tex", "t", t, _F64, (n, 3))
-    K4 = _arg("render_rgbd_tex", "K4", K4, _F64, (n, 4))
+    choices = {"shading": (shading, RENDER_SHADING), "filter": (filter, RENDER_FILTER), "wrap": (wrap, RENDER_WRAP)}
+    outputs, verts, faces, R, t, K4, n, nv, nt = _render_mesh("render_rgbd_tex", choices, outputs, verts, faces, R, t, K4)
     uv = _arg("render_rgbd_tex", "uv", uv, _F64, (nv, 2), optional=True)
     tex = _arg("render_rgbd_tex", "tex", tex, _U8, (None, None, 4), optional=True)
-    normals = _arg("render_rgbd_tex", "normals", normals, _F64, (nv, 3), optional=True)
     th, tw = (int(tex.shape[0]), int(tex.shape[1])) if tex is not None else (1, 1)
-    light = (C.c_double * 3)(*(float(v) for v in np.asarray(light_cam_pos, np.float64).reshape(3)))
-    bg = (C.c_double * 3)(*(float(v) for v in np.asarray(bg_color, np.float64).reshape(3)))
     nbytes = lib.pp_render_rgbd_tex_workspace_bytes(n, nv, nt, int(width), int(height), tw, th)
-    ws = _workspace(nbytes, "render_rgbd_tex: unsupported shape (n=%d, vertices=%d, triangles=%d, %dx%d, texture %dx%d)" %
-                    (n, nv, nt, width, height, tw, th))
-    out = {k: _out(verts, (n, int(height), int(width)) + ((3,) if k.startswith("rgb") else ()), dt)
-           for k, dt in RENDER_OUTPUTS.items() if k in outputs}
+    normals, light, bg, ws, out = _render_frame("render_rgbd_tex", outputs, verts, n, nv, nt, width, height, normals, light_cam_pos, bg_color,
+                                                nbytes, ", texture %dx%d" % (tw, th))
     check(lib.pp_render_rgbd_tex(ctx.handle, n, nv, _ptr(verts), _ptr(uv), _ptr(tex), tw, th, RENDER_FILTER[filter], RENDER_WRAP[wrap],
                                  _ptr(normals), nt, _ptr(faces), _ptr(R), _ptr(t), _ptr(K4), int(width), int(height), float(clip_near),
                                  float(clip_far), RENDER_SHADING[shading], float(ambient_weight), light, bg, _ptr(ws), nbytes,
@@ -870,20 +863,27 @@ def render_rgbd_tex(ctx, verts, faces, R, t, K4, width, height, uv=None, tex=Non
 VSD_COSTS = {"step": 0, "tlinear": 1}
 
 
+def _vsd_args(what, depth_test, depth_est, depth_gt, K4):
+    """the tensors of vsd() / vsd_multi(), checked -> (n, h, w, then in ABI order: depth_test, its stride between problems,
+    depth_est, depth_gt, K4)"""
+    de = _arg(what, "depth_est", depth_est, _F32, (None, None, None))
+    n, h, w = (int(s) for s in de.shape)
+    dg = _arg(what, "depth_gt", depth_gt, _F32, (n, h, w))
+    shared = torch.is_tensor(depth_test) and depth_test.dim() == 2  # one scene [h,w] for all problems, else [n,h,w]
+    dt = _arg(what, "depth_test", depth_test, _F32, (h, w) if shared else (n, h, w))
+    K4 = _arg(what, "K4", K4, _F64, (n, 4))
+    return n, h, w, dt, 0 if shared else h * w, de, dg, K4
+
+
 def vsd(ctx, depth_test, depth_est, depth_gt, K4, delta, tau, cost_type="step"):
     """Visible Surface Discrepancy of n problems (pp_vsd_f64): cuda float32 depth_est / depth_gt [n,h,w], depth_test [h,w]
     (shared by all problems) or [n,h,w], K4 float64 [n,4] -> (e float64 [n], intersection int64 [n], union int64 [n])."""
     if cost_type not in VSD_COSTS:
         raise ValueError("vsd: unknown pixel matching cost %r (step | tlinear)" % (cost_type,))
-    de = _arg("vsd", "depth_est", depth_est, _F32, (None, None, None))
-    n, h, w = (int(s) for s in de.shape)
-    dg = _arg("vsd", "depth_gt", depth_gt, _F32, (n, h, w))
-    shared = torch.is_tensor(depth_test) and depth_test.dim() == 2  # one scene [h,w] for all problems, else [n,h,w]
-    dt = _arg("vsd", "depth_test", depth_test, _F32, (h, w) if shared else (n, h, w))
-    K4 = _arg("vsd", "K4", K4, _F64, (n, 4))
+    n, h, w, dt, stride, de, dg, K4 = _vsd_args("vsd", depth_test, depth_est, depth_gt, K4)
     ws = _workspace(lib.pp_vsd_workspace_bytes(n, w, h))
     e, inter, uni = _out(de, (n,)), _out(de, (n,), torch.int64), _out(de, (n,), torch.int64)
-    check(lib.pp_vsd_f64(ctx.handle, n, w, h, _ptr(dt), 0 if shared else h * w, _ptr(de), _ptr(dg), _ptr(K4), float(delta), float(tau),
+    check(lib.pp_vsd_f64(ctx.handle, n, w, h, _ptr(dt), stride, _ptr(de), _ptr(dg), _ptr(K4), float(delta), float(tau),
                          VSD_COSTS[cost_type], _ptr(ws), _ptr(e), _ptr(inter), _ptr(uni)), ctx.handle, "pp_vsd_f64")
     return e, inter, uni
 
@@ -902,16 +902,11 @@ def vsd_multi(ctx, depth_test, depth_est, depth_gt, K4, delta, taus, cost_type="
         raise ValueError("vsd_multi: unknown visibility rule %r (bop18 | bop19)" % (visib_mode,))
     taus = np.ascontiguousarray(np.asarray(taus, np.float64).reshape(-1))
     T = int(taus.size)
-    de = _arg("vsd_multi", "depth_est", depth_est, _F32, (None, None, None))
-    n, h, w = (int(s) for s in de.shape)
-    dg = _arg("vsd_multi", "depth_gt", depth_gt, _F32, (n, h, w))
-    shared = torch.is_tensor(depth_test) and depth_test.dim() == 2  # one scene [h,w] for all problems, else [n,h,w]
-    dt = _arg("vsd_multi", "depth_test", depth_test, _F32, (h, w) if shared else (n, h, w))
-    K4 = _arg("vsd_multi", "K4", K4, _F64, (n, 4))
+    n, h, w, dt, stride, de, dg, K4 = _vsd_args("vsd_multi", depth_test, depth_est, depth_gt, K4)
     ws = _workspace(lib.pp_vsd_multi_workspace_bytes(n, w, h, T))
     e = _out(de, (n, T))
     inter, uni, vis, px = (_out(de, (n,), torch.int64) for _ in range(4))
-    check(lib.pp_vsd_multi_f64(ctx.handle, n, w, h, _ptr(dt), 0 if shared else h * w, _ptr(de), _ptr(dg), _ptr(K4), float(delta), T,
+    check(lib.pp_vsd_multi_f64(ctx.handle, n, w, h, _ptr(dt), stride, _ptr(de), _ptr(dg), _ptr(K4), float(delta), T,
                                taus.ctypes.data_as(C.POINTER(C.c_double)), VSD_COSTS[cost_type], VSD_VISIB[visib_mode], _ptr(ws),
                                _ptr(e), _ptr(inter), _ptr(uni), _ptr(vis), _ptr(px)), ctx.handle, "pp_vsd_multi_f64")
     return e, inter, uni, vis, px
@@ -919,6 +914,14 @@ def vsd_multi(ctx, depth_test, depth_est, depth_gt, K4, delta, taus, cost_type="
 
 SCENE_GT_MAX_INSTANCES = 255  # per scene: the id image is uint8 and 0 is the background
 SceneGT = collections.namedtuple("SceneGT", "px_count bbox_obj bbox_visib id_image scene_depth mask_full mask_visib")
+
+
+def _scene_offsets(what, scene_offsets, S=None):
+    """scene_offsets as S+1 host int32 values; S: the number of scenes they must fit, None = any (at least one)"""
+    off = np.ascontiguousarray(np.asarray(scene_offsets).reshape(-1), np.int32)
+    if (off.size < 2 if S is None else off.size != S + 1) or not np.array_equal(off, np.asarray(scene_offsets).reshape(-1)):
+        raise ValueError("%s: scene_offsets must hold S+1 %s integers" % (what, ">= 2" if S is None else "= %d" % (S + 1)))
+    return off
 
 
 def scene_gt_info(ctx, depth_stack, scene_offsets, K4, depth_test=None, delta=15.0, window=None, masks=False):
@@ -931,9 +934,7 @@ def scene_gt_info(ctx, depth_stack, scene_offsets, K4, depth_test=None, delta=15
     float32 [S,h,w] (None with depth_test), mask_full, mask_visib uint8 [n,h,w] 0 / 255 (None without masks))."""
     stack = _arg("scene_gt_info", "depth_stack", depth_stack, _F32, (None, None, None))
     n, ch, cw = (int(s) for s in stack.shape)
-    off = np.ascontiguousarray(np.asarray(scene_offsets).reshape(-1), np.int32)
-    if off.size < 2 or not np.array_equal(off, np.asarray(scene_offsets).reshape(-1)):
-        raise ValueError("scene_gt_info: scene_offsets must hold S+1 >= 2 integers")
+    off = _scene_offsets("scene_gt_info", scene_offsets)
     S = int(off.size) - 1
     ox, oy, w, h = (int(v) for v in (window if window is not None else (0, 0, cw, ch)))
     K4 = _arg("scene_gt_info", "K4", K4, _F64, (n, 4))
@@ -967,9 +968,7 @@ def scene_compose(ctx, id_image, colors, scene_offsets, background=(0, 0, 0), ch
     S, h, w = (int(s) for s in ids.shape)
     colors = _arg("scene_compose", "colors", colors, _U8, (None, h, w, 3))
     n = int(colors.shape[0])
-    off = np.ascontiguousarray(np.asarray(scene_offsets).reshape(-1), np.int32)
-    if off.size != S + 1 or not np.array_equal(off, np.asarray(scene_offsets).reshape(-1)):
-        raise ValueError("scene_compose: scene_offsets must hold S+1 = %d integers" % (S + 1))
+    off = _scene_offsets("scene_compose", scene_offsets, S)
     bg_image, bg_const = None, None
     if torch.is_tensor(background):
         bg_image = _arg("scene_compose", "background", background, _U8, (S, h, w, 3))

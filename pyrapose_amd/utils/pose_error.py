@@ -1,6 +1,6 @@
 """Mirror of the pose-error functions the evaluation loops call (utils/pose_error.py:43-75, 105-275;
 utils/linemod_eval.py:525-531, tless_eval.py:470-471, 651-662): same names, arguments and float return values, computed by the
-HIP kernels (ADD / ADI / reproj in csrc/pose.hip, VSD in csrc/render.hip on depth images from utils.renderer); re / te and
+HIP kernels (ADD / ADI / reproj in csrc/pose.hip, VSD in csrc/vsd.hip on depth images from utils.renderer); re / te and
 depth_im_to_dist_im stay on the host in numpy.  mssd / mspd are BOP's symmetry-aware errors (bop_toolkit_lib.pose_error), also
 in csrc/pose.hip, over the symmetry sets of utils/symmetry.py; vsd_multi_* score VSD at up to 16 misalignment tolerances in one
 pass with BOP 2019's visibility rule (AR_VSD), and visib_fract_batch gives the visible fraction of an annotation."""

@@ -2,7 +2,7 @@
 reference takes from disk -- annotation_scripts/annotate_BOP.py:363-378, 420, 461-471 reads mask_visib/*.png and
 scene_gt_info.json, which bop_toolkit's calc_gt_masks / calc_gt_info wrote beforehand with an OpenGL renderer.  Here every
 mesh is rendered once at all its poses (utils.renderer.render_depth_batch) and one pass over the renders (pp_scene_gt_info,
-csrc/render.hip) gives the instance-id image, both masks, both boxes, the three pixel counts and the visible fraction of every
+csrc/scene_gt.hip) gives the instance-id image, both masks, both boxes, the three pixel counts and the visible fraction of every
 instance, against the sensor depth or, for a synthetic scene, against the depth composed from the instances themselves.
 Parity with bop_toolkit is unpinned: its definitions are restated (tests/scene_gt_np.py)."""
 import collections

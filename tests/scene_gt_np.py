@@ -1,4 +1,4 @@
-"""numpy restatement of the scene ground-truth pass (pp_scene_gt_info, csrc/render.hip), pixel by pixel in the same expression
+"""numpy restatement of the scene ground-truth pass (pp_scene_gt_info, csrc/scene_gt.hip), pixel by pixel in the same expression
 order: from a stack of instance depth images grouped into scenes, the composed scene depth, the three pixel counts, both boxes
 and both masks of every instance (bop_toolkit's calc_gt_info / calc_gt_masks, definitions restated) and the id image
 (annotate_BOP.py:363-374: instances in order, later ones overwrite earlier ones).  The distance images and the 'bop19'

@@ -1,4 +1,4 @@
-"""GPU: the colour renderer pp_render_rgbd and the scene image pp_scene_compose_u8 (csrc/render.hip) through ops.render_rgbd,
+"""GPU: the colour renderer pp_render_rgbd (csrc/render.hip) and the scene image pp_scene_compose_u8 (csrc/scene_gt.hip) through ops.render_rgbd,
 utils.renderer.render_rgbd_batch / render_object and utils.scene_gt.render_scenes, against the numpy restatement
 tests/render_rgb_np.py (pinned to closed forms by tests/test_render_rgb_cpu.py).  Depth is compared with the depth pass bit for
 bit, colour with the restatement fed the device's own triangle ids, so that coverage differences cannot enter."""

@@ -1,4 +1,4 @@
-"""numpy restatement of VSD over a vector of misalignment tolerances (pp_vsd_multi_f64, csrc/render.hip), one problem at a
+"""numpy restatement of VSD over a vector of misalignment tolerances (pp_vsd_multi_f64, csrc/vsd.hip), one problem at a
 time: the distance images of depth_im_to_dist_im, both visibility rules ('bop18': the reference's estimate_visib_mask, a
 pixel without sensor depth is never visible; 'bop19': BOP 2019's, a rendered pixel without sensor depth is visible), both
 pixel costs and the pixel counts.  Written from the definitions; tests/test_vsd_bop_cpu.py pins it in mode 'bop18' to the
