@@ -19,13 +19,33 @@ def tf_iou(a, b):
     return np.float32(inter / np.float32(np.float32(area_a + area_b) - inter))
 
 
+def tf_iou_many(a, B):
+    """tf_iou(a, b) for every row b of B [k,4] at once: the same float32 operations in the same order, element by element
+    (tests/test_oracle_detect.py holds the two bit-equal), so that the greedy loop below costs one numpy call per candidate"""
+    a = np.asarray(a, np.float32); B = np.asarray(B, np.float32).reshape(-1, 4)
+    ay0, ax0 = min(a[0], a[2]), min(a[1], a[3]); ay1, ax1 = max(a[0], a[2]), max(a[1], a[3])
+    by0, bx0 = np.minimum(B[:, 0], B[:, 2]), np.minimum(B[:, 1], B[:, 3])
+    by1, bx1 = np.maximum(B[:, 0], B[:, 2]), np.maximum(B[:, 1], B[:, 3])
+    area_a = np.float32(ay1 - ay0) * np.float32(ax1 - ax0)
+    area_b = (by1 - by0) * (bx1 - bx0)
+    iy0, ix0 = np.maximum(ay0, by0), np.maximum(ax0, bx0); iy1, ix1 = np.minimum(ay1, by1), np.minimum(ax1, bx1)
+    inter = np.maximum(iy1 - iy0, np.float32(0)) * np.maximum(ix1 - ix0, np.float32(0))
+    ok = ~(area_b <= 0) & (not area_a <= 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        iou = inter / ((area_a + area_b) - inter)
+    return np.where(ok, iou, np.float32(0)).astype(np.float32)
+
+
 def non_max_suppression(boxes, scores, max_output_size, iou_threshold):
+    boxes = np.asarray(boxes, np.float32).reshape(-1, 4)
     order = sorted(range(len(scores)), key=lambda i: (-float(scores[i]), i))
     keep = []
+    kept = np.empty((min(len(order), max_output_size), 4), np.float32)
     for i in order:
         if len(keep) >= max_output_size:
             break
-        if all(not (tf_iou(boxes[i], boxes[j]) > np.float32(iou_threshold)) for j in keep):
+        if not np.any(tf_iou_many(boxes[i], kept[:len(keep)]) > np.float32(iou_threshold)):
+            kept[len(keep)] = boxes[i]
             keep.append(i)
     return np.asarray(keep, np.int64)
 

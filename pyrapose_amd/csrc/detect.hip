@@ -2,7 +2,7 @@
 // (tf.image.non_max_suppression, TF 2.1, third-party) -> concat classes -> top_k -> gather -> pad -1.
 // The layer is registered but never instantiated by the reference graph; it is built
 // because the north star names NMS.  Tie-breaks: higher score first, equal score -> lower index first
-// ("parity unpinned").  Compiled with -ffp-contract=off (IoU compares are op-by-op f32).
+// ("parity unpinned"; "equal" is float equality, so -0 and +0 tie).  Compiled with -ffp-contract=off (IoU compares are op-by-op f32).
 #include "pp_internal.h"
 
 struct FilterWs {
@@ -24,8 +24,10 @@ extern "C" size_t pp_filter_workspace_bytes(int n, int n_class, int max_det) {
   return (size_t)n_class * np2 * 8 + (size_t)n_class * 4 * 2 + (size_t)n_class * max_det * 4 + 256;
 }
 
+// Equal floats must give equal score bits, or the index could not break their tie: -0.0f == +0.0f, so the zero is
+// canonicalised first (-0.0f + 0.0f is +0.0f).  key_score therefore returns +0.0f for a score of -0.0f: equal, not identical.
 __device__ __forceinline__ unsigned long long make_key(float score, int idx) {
-  unsigned int b = __float_as_uint(score);
+  unsigned int b = __float_as_uint(score + 0.0f);
   b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);  // monotone map of float order onto unsigned order
   return ((unsigned long long)(~b) << 32) | (unsigned int)idx;
 }
@@ -219,6 +221,10 @@ extern "C" int pp_filter_detections_batch(pp_ctx* ctx, int n_img, int n, int n_c
   ws.sel_count = (int*)w;
   w += (size_t)n_img * n_class * 4;
   ws.sel_idx = (int*)w;
+  // The top-k stage sorts next_pow2(classes * max_det) 8-byte keys in dynamic LDS, at most 65 536 bytes, beside 264 bytes of
+  // static LDS (s_off[65], padded; .group_segment_fixed_size of filter_topk_kernel in the gfx950 code object).  A gfx950
+  // workgroup may take 163 840 bytes (hipDeviceProp_t.sharedMemPerBlock on the MI355X), so 65 800 fits and the limit below is
+  // the whole condition; tests/test_gpu_detect.py runs 8 classes x 1024 with more than 4096 survivors against the oracle.
   const int tot_max = next_pow2(n_class * max_det);
   PP_CHECK_ARG(ctx, (size_t)tot_max * 8 <= 64 * 1024, PP_ERR_SHAPE, "pp_filter_detections: classes*max_det too large for the top-k stage");
   hipLaunchKernelGGL(filter_sort_kernel, dim3(n_class, n_img), dim3(1024), 0, ctx->stream, n, n_class, np2, scores, score_thr, ws.keys,

@@ -190,3 +190,137 @@ def test_filter_detections_batch_matches_per_image(ctx):
         want = ops.filter_detections(ctx, boxes[b].contiguous(), boxes3d[b].contiguous(), scores[b].contiguous(), 0.05, 0.5, 300)
         for g, w in zip(got, want):
             assert torch.equal(g[b], w)
+
+
+# ---- threshold_compact_kernel and box3d_decode_kernel at their edges ----
+def _compact_scores(rng, B, n, Cc, thr):
+    s = rng.uniform(0, 1, size=(B, n, Cc)).astype(np.float32)    # about 30 % above 0.7
+    flat = s.reshape(-1)
+    pick = rng.permutation(flat.size)
+    flat[pick[: flat.size // 5]] = thr                           # equal to the threshold: excluded (the test is >)
+    flat[pick[flat.size // 5: flat.size // 4]] = np.nan          # NaN > thr is false: excluded
+    return s
+
+
+def _check_compaction(scores, thr, idx, cnt, cap):
+    from oracle import anchors_np as O
+    B, n, Cc = scores.shape
+    assert idx.shape == (B, Cc, cap) and cnt.shape == (B, Cc)
+    for b in range(B):
+        want = O.score_threshold_indices(scores[b], np.float32(thr))
+        for c in range(Cc):
+            k = len(want[c])
+            assert cnt[b, c] == k, (b, c)                        # the true total, whatever the capacity
+            assert np.array_equal(idx[b, c, : min(k, cap)], want[c][:cap]), (b, c)
+            assert np.all(idx[b, c, k:] == -1), (b, c)
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 1023, 1024, 1025, 2049])
+def test_compaction_sizes_around_wave_and_pass(ctx, n):
+    """one lane, one wave -/+ 1, one 1024-thread pass -/+ 1, two passes + 1; C = 1 and 3 (the class stride), B = 1 and 2"""
+    from pyrapose_amd import ops
+    thr = np.float32(0.7)
+    for B, Cc in ((1, 1), (1, 3), (2, 1), (2, 3)):
+        rng = np.random.default_rng(100 * n + 10 * B + Cc)
+        scores = _compact_scores(rng, B, n, Cc, thr)
+        if n > 1:
+            scores[B - 1, n - 1, Cc - 1] = 0.9                   # the very last score is a hit
+        idx, cnt = ops.score_threshold_compact(ctx, torch.from_numpy(scores).cuda(), float(thr))
+        _check_compaction(scores, thr, idx.cpu().numpy(), cnt.cpu().numpy(), n)
+        cap = n + 37                                             # more room than anchors: the tail is -1
+        idx, cnt = ops.score_threshold_compact(ctx, torch.from_numpy(scores).cuda(), float(thr), cap)
+        _check_compaction(scores, thr, idx.cpu().numpy(), cnt.cpu().numpy(), cap)
+
+
+def test_compaction_hits_in_last_lane_and_last_wave(ctx):
+    from pyrapose_amd import ops
+    n, thr = 2049, 0.5
+    i = np.arange(n)
+    scores = np.zeros((1, n, 4), np.float32)
+    scores[0, i % 64 == 63, 0] = 0.9             # only the last lane of every wave
+    scores[0, i % 1024 >= 960, 1] = 0.9          # only the last wave of every pass
+    scores[0, i % 1024 == 1023, 2] = 0.9         # only the last lane of the last wave
+    scores[0, 2048, 3] = 0.9                     # only the one anchor of the third pass
+    idx, cnt = ops.score_threshold_compact(ctx, torch.from_numpy(scores).cuda(), thr)
+    idx, cnt = idx.cpu().numpy(), cnt.cpu().numpy()
+    _check_compaction(scores, thr, idx, cnt, n)
+    assert list(cnt[0]) == [32, 128, 2, 1] and list(idx[0, 2, :2]) == [1023, 2047] and idx[0, 3, 0] == 2048
+
+
+@pytest.mark.parametrize("cap", [1, 63, 64, 65, 200])
+def test_compaction_cap_below_the_hit_count(ctx, cap):
+    """cap < hits: the count is still the true total, idx holds the first cap hits in order, nothing is written past a row's
+    cap -- the 64 ints after the last row keep their bytes (the kernel's rows are cap apart, so a store at out[cap] of the last
+    row lands there; the hits are dense in the last row so that it is the one that overflows)"""
+    from pyrapose_amd._lib import check, lib
+    import ctypes
+    rng = np.random.default_rng(cap)
+    B, n, Cc, thr = 2, 1500, 3, np.float32(0.7)
+    scores = _compact_scores(rng, B, n, Cc, thr)
+    scores[1, :, 2] = 0.9                                        # the last row: every anchor hits
+    scores[0, :, 1] = 0.0                                        # a row with no hit
+    scores[0, :cap, 0] = 0.9; scores[0, cap:, 0] = 0.0           # a row with exactly cap hits
+    sentinel = -77
+    buf = torch.full((B * Cc * cap + 64,), sentinel, dtype=torch.int32, device="cuda")
+    cnt = torch.full((B * Cc + 64,), sentinel, dtype=torch.int32, device="cuda")
+    d = torch.from_numpy(scores).cuda()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    check(lib.pp_score_threshold_compact(ctx.handle, B, n, Cc, p(d), float(thr), cap, p(buf), p(cnt)), ctx.handle, "compact")
+    torch.cuda.synchronize()
+    buf, cnt = buf.cpu().numpy(), cnt.cpu().numpy()
+    assert np.all(buf[B * Cc * cap:] == sentinel) and np.all(cnt[B * Cc:] == sentinel)
+    idx, cnt = buf[: B * Cc * cap].reshape(B, Cc, cap), cnt[: B * Cc].reshape(B, Cc)
+    _check_compaction(scores, thr, idx, cnt, cap)
+    assert cnt[1, 2] == n and np.array_equal(idx[1, 2], np.arange(cap)) and cnt[0, 1] == 0 and cnt[0, 0] == cap
+    assert np.all(idx[0, 1] == -1) and np.array_equal(idx[0, 0], np.arange(cap))
+    assert np.all(idx != sentinel)                               # every slot is either a hit or -1
+
+
+def _synthetic_anchors(rng, n):
+    c = rng.uniform(0, 640, size=(n, 2)); wh = rng.uniform(4, 300, size=(n, 2))
+    return np.concatenate([c - wh / 2, c + wh / 2], axis=1).astype(np.float32)
+
+
+def _decode_bits(ctx, anchors, reg):
+    from oracle import anchors_np as O
+    from pyrapose_amd import ops
+    got = ops.box3d_decode(ctx, torch.from_numpy(anchors).cuda(), torch.from_numpy(reg).cuda()).cpu().numpy()
+    with np.errstate(over="ignore", invalid="ignore"):           # (the special values overflow on purpose)
+        want = O.box3d_transform_inv_f32(anchors[None], reg)
+    assert got.shape == want.shape and got.dtype == want.dtype
+    bad = got.view(np.int32) != want.view(np.int32)
+    assert not bad.any(), (int(bad.sum()), np.argwhere(bad)[:4].tolist())
+
+
+def test_decode_stride_loop_second_trip(ctx):
+    """B * N just above 4096 blocks x 256 threads: the last rows are decoded on the second trip of the grid-stride loop"""
+    rng = np.random.default_rng(31)
+    B, N = 2, 4096 * 128 + 100                                   # 1 048 776 rows > 1 048 576
+    anchors = _synthetic_anchors(rng, N)
+    reg = rng.standard_normal((B, N, 16), dtype=np.float32)
+    _decode_bits(ctx, anchors, reg)
+
+
+def test_decode_row_to_anchor_mapping_and_special_values(ctx):
+    """B = 3 with N = 7: row i of the flat [B * N] batch reads anchor i % N.  Zero-width / zero-height anchors; +-inf, NaN and
+    denormal regressions, compared as bits.  (An infinite regression is not paired with a zero-size anchor: inf * 0 is an
+    invalid operation whose NaN carries an implementation-defined sign; every NaN here is a propagated input NaN.)"""
+    rng = np.random.default_rng(32)
+    B, N = 3, 7
+    anchors = _synthetic_anchors(rng, N)
+    reg = rng.standard_normal((B, N, 16), dtype=np.float32)
+    _decode_bits(ctx, anchors, reg)
+    flat = anchors.copy()
+    flat[1, 2] = flat[1, 0]                                      # zero width
+    flat[3, 3] = flat[3, 1]                                      # zero height
+    flat[5, 2:] = flat[5, :2]                                    # a point
+    flat[6] = flat[6][[2, 3, 0, 1]]                              # negative width and height
+    _decode_bits(ctx, flat, reg)
+    sp = reg.copy()
+    sp[0, 0, 0:4] = [np.inf, -np.inf, np.inf, -np.inf]
+    sp[1, 2, 4:8] = np.nan
+    sp[2, 4, :] = np.float32(1e-40)                              # denormal: * 0.2 stays denormal
+    sp[2, 2, 0:4] = [1e-45, -1e-45, 3e-39, -3e-39]
+    sp[1, 0, 8:12] = [3.0e38, -3.0e38, 1e38, -0.0]               # overflows to +-inf in the multiply by the size
+    assert np.isnan(sp).sum() == 4 and np.isinf(sp).sum() == 4
+    _decode_bits(ctx, anchors, sp)
