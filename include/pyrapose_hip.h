@@ -795,6 +795,42 @@ int pp_vote_cluster(pp_ctx* ctx, int batch, int n, int n_class, int cap, const f
                     const int* idx, const int* counts, double iou_thr, int min_votes, int max_instances, int max_rounds,
                     void* workspace, int* inst, int* order, int* inst_offsets, int* n_inst, int* leader, float* inst_box);
 
+/* ---- model geometry: diameter and farthest-point control points (csrc/model_info.hip) ------------------------------------
+ * What the evaluation tail takes as given from a dataset's models_info.json (the 'diameter' the ADD decision and VSD's taus
+ * scale with) and from the reference's offline FPS.py (features.json), computed from the model's points.  float64; with
+ *   d2(a, b) = (dx dx + dy dy) + dz dz        in exactly that association, every product and sum rounded on its own
+ * (numpy's (diff * diff).sum(axis=1) on rows of three).  Parity with bop_toolkit's misc.calc_pts_diameter and with a run of
+ * FPS.py is unpinned: both definitions restated, tests/model_info_np.py.
+ *
+ * pp_pts_diameter_f64: pts [n,3], 1 <= n <= 2^24 (PP_ERR_SHAPE otherwise).
+ *   d2 [1]   = max over i <= j of d2(p_i, p_j); the diameter is its square root, taken on the host (math.sqrt, as
+ *              calc_pts_diameter does after its .max()), so the device result is a maximum of exactly rounded sums
+ *   pair [2] = int32 (i, j), i <= j, a pair that attains it: the lowest i, then the lowest j.  n = 1: d2 = 0, pair (0, 0).
+ *   Points past n take no part (a partial tile's tail is not a set of zero points).  Maxima only: bit-identical run to run.
+ *   workspace_bytes >= pp_pts_diameter_workspace_bytes(n) (0: bad n), workspace not NULL: PP_ERR_ARG otherwise.
+ *
+ * pp_farthest_points_f64: greedy farthest-point sampling of k points from each of n_model point sets in ONE launch (one
+ *   workgroup per model).  pts [n_total,3]: the sets concatenated; offsets [n_model+1] int32 from 0 to n_total, given twice
+ *   as pp_scene_gt_info's scene_offsets are: the HOST copy is checked before anything is launched, the kernel reads the
+ *   device copy.  start [n_model] int32 (device): each model's first pick (clamped into the model), or NULL: the first
+ *   maximum of (x x + y y) + z z (FPS.py:40-42, argmax of the norm restated on squares).  Then k - 1 times: update every
+ *   point's running score against the point chosen last, pick the first maximum (np.argmax: the lowest index on ties).
+ *     rule 0 ("min"): score_i = min over the chosen c of d2(p_i, p_c); no square root is taken.  k <= every model's size.
+ *     rule 1 ("sum"): FPS.py:62-94.  score_i = sum over the chosen c, added in the order chosen, of sqrt(d2(p_i, q_c)), q_c
+ *       being p_c ROUNDED TO FLOAT32 (control_points is a float32 array, :37, :83-84); the score counts as 0.0 if any
+ *       sqrt(d2(p_i, q_c)) < min_dist[model] (float64 [n_model], device; FPS.py:55-59 passes (x_dim + y_dim + z_dim) / 7).
+ *       When every score is 0 the pick is index 0.  k may exceed a model's size.
+ *   index [n_model,k] int32: the picks as indices WITHIN their model.  Fixed order: bit-identical run to run.
+ *   Errors before anything is launched: n_model, n_total or k < 1, an empty model, k > a model's size under rule 0:
+ *   PP_ERR_SHAPE; null pointers (min_dist may be NULL under rule 0), rule outside {0, 1}, offsets that decrease or do not run
+ *   from 0 to n_total, workspace_bytes < pp_farthest_points_workspace_bytes(n_total): PP_ERR_ARG. */
+size_t pp_pts_diameter_workspace_bytes(int n);
+int pp_pts_diameter_f64(pp_ctx* ctx, int n, const double* pts, void* workspace, size_t workspace_bytes, double* d2, int* pair);
+size_t pp_farthest_points_workspace_bytes(int n_total);
+int pp_farthest_points_f64(pp_ctx* ctx, int n_model, int n_total, const double* pts, const int* offsets_host, const int* offsets_dev,
+                           int k, int rule, const double* min_dist, const int* start, void* workspace, size_t workspace_bytes,
+                           int* index);
+
 #ifdef __cplusplus
 }
 #endif

@@ -204,6 +204,10 @@ _SIGS = {
     "pp_pnp_refine_weighted_f64": (_i, [_p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _i, _d, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pp_vote_cluster_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "pp_vote_cluster": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _d, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "pp_pts_diameter_workspace_bytes": (_sz, [_i]),
+    "pp_pts_diameter_f64": (_i, [_p, _i, _p, _p, _sz, _p, _p]),
+    "pp_farthest_points_workspace_bytes": (_sz, [_i]),
+    "pp_farthest_points_f64": (_i, [_p, _i, _i, _p, C.POINTER(_i), _p, _i, _i, _p, _p, _p, _sz, _p]),
 }
 
 EXPORTS = sorted(_SIGS)

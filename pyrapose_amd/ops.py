@@ -1165,3 +1165,49 @@ def vote_cluster(ctx, boxes3D, scores, idx, cnt, iou=0.5, min_votes=10, max_inst
                               _ptr(ws), _ptr(inst), _ptr(order), _ptr(offs), _ptr(n_inst), _ptr(leader), _ptr(box)), ctx.handle,
           "pp_vote_cluster")
     return inst, order, offs, n_inst, leader, box
+
+
+DIAMETER_TILE = 256    # points per tile of pp_pts_diameter_f64 (square tiles: one constant); a workgroup sweeps one tile pair
+DIAMETER_MAX_CHUNKS = 64  # up to this many tiles a workgroup sweeps ONE j tile; beyond, ceil(tiles / 64) j tiles in a loop (a chunk)
+FPS_THREADS = 1024    # threads of the one workgroup per model of pp_farthest_points_f64; a model's further points go through the workspace
+FPS_RULES = {"min": 0, "sum": 1}
+
+
+def pts_diameter(ctx, pts):
+    """The farthest pair of one point set (pp_pts_diameter_f64): cuda float64 pts [n,3], 1 <= n <= 2^24 -> (d2 float64 [1] =
+    max over i <= j of (dx dx + dy dy) + dz dz, pair int32 [2] = the (i, j) that attains it, lowest i then lowest j).  The
+    diameter is math.sqrt(d2) on the host.  All n (n + 1) / 2 pairs are visited in ONE launch: 2^24 is what the pair key
+    can address, not a size to use -- at the measured 3e12 pairs/s, 1 M points take about 0.2 s and 2^24 about 45 s."""
+    pts = _arg("pts_diameter", "pts", pts, _F64, (None, 3))
+    n = int(pts.shape[0])
+    nbytes = lib.pp_pts_diameter_workspace_bytes(n)
+    ws = _workspace(nbytes)
+    d2, pair = _out(pts, (1,)), _out(pts, (2,), _I32)
+    check(lib.pp_pts_diameter_f64(ctx.handle, n, _ptr(pts), _ptr(ws), nbytes, _ptr(d2), _ptr(pair)), ctx.handle, "pp_pts_diameter_f64")
+    return d2, pair
+
+
+def farthest_points(ctx, pts, offsets, k, rule="min", min_dist=None, start=None):
+    """Greedy farthest-point sampling of k points from each of M point sets in one launch (pp_farthest_points_f64): cuda
+    float64 pts [N,3] (the sets concatenated), offsets: M+1 HOST integers rising from 0 to N, rule 'min' (score = smallest
+    squared distance to the chosen points; k <= every set's size) or 'sum' (the reference's FPS.py: score = sum of distances to
+    the chosen points rounded to float32, 0 for a point nearer than min_dist to any of them; cuda float64 min_dist [M]),
+    start: cuda int32 [M] first picks, None = the point of largest norm -> int32 [M,k] indices within each set, the lowest
+    index on ties."""
+    if rule not in FPS_RULES:
+        raise ValueError("farthest_points: unknown rule %r (min | sum)" % (rule,))
+    pts = _arg("farthest_points", "pts", pts, _F64, (None, 3))
+    off = np.ascontiguousarray(np.asarray(offsets).reshape(-1), np.int32)
+    if off.size < 2 or not np.array_equal(off, np.asarray(offsets).reshape(-1)):
+        raise ValueError("farthest_points: offsets must hold M+1 >= 2 integers")
+    M, N = int(off.size) - 1, int(pts.shape[0])
+    min_dist = _arg("farthest_points", "min_dist", min_dist, _F64, (M,), optional=rule == "min")
+    start = _arg("farthest_points", "start", start, _I32, (M,), optional=True)
+    nbytes = lib.pp_farthest_points_workspace_bytes(N)
+    ws = _workspace(nbytes)
+    index = _out(pts, (M, max(int(k), 0)), _I32)
+    off_dev = torch.from_numpy(off).to(pts.device)
+    check(lib.pp_farthest_points_f64(ctx.handle, M, N, _ptr(pts), off.ctypes.data_as(C.POINTER(C.c_int)), _ptr(off_dev), int(k),
+                                     FPS_RULES[rule], _ptr(min_dist), _ptr(start), _ptr(ws), nbytes, _ptr(index)), ctx.handle,
+          "pp_farthest_points_f64")
+    return index
