@@ -237,6 +237,27 @@ int pp_conv2d_nhwc_bwd_weight_bf16x3(pp_ctx* ctx, const pp_conv_desc* d, const f
                                      const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo,
                                      float* dw, float* dbias, const pp_conv_opts* opts);
 
+/* Host only, no context: which kernels the three entry points above WOULD launch for descriptor d, as text -- one line per launch
+ * in the wording of the PP_CONV_DEBUG trace, then the kernel family and, behind " | ", the plan's numbers as key=value.  Built
+ * from the same facts and by the same planner as the launches themselves (csrc/conv_plan.h), under the PP_* switches of the
+ * calling process.  pass: PP_PLAN_FWD / PP_PLAN_BWD_DATA / PP_PLAN_BWD_WEIGHT.  forms: PP_PLAN_* bits -- how the call would give
+ * its operands (gathered operand and, for the weight gradient, both operands as planes; output as planes and / or f32, f32 when
+ * neither bit is set; split capture; skip_flags + skip_list, or out_flags + out_list in the forward pass; lazy_in; lazy_out).
+ * planes_fmt as pp_ctx_set_planes_format, n_cu and ws_bytes as the context would hold them (ws_bytes 0: no scratch).
+ * Returns the bytes written to buf (text is cut at buf_bytes - 1) or a PP_ERR_* code. */
+#define PP_PLAN_FWD 0
+#define PP_PLAN_BWD_DATA 1
+#define PP_PLAN_BWD_WEIGHT 2
+#define PP_PLAN_PLANES_IN 1u
+#define PP_PLAN_PLANES_OUT 2u
+#define PP_PLAN_F32_OUT 4u
+#define PP_PLAN_CAPTURE 8u
+#define PP_PLAN_LIST 16u
+#define PP_PLAN_LAZY_IN 32u
+#define PP_PLAN_LAZY_OUT 64u
+int pp_conv_plan_text(const pp_conv_desc* d, int pass, unsigned forms, int planes_fmt, int n_cu, size_t ws_bytes, char* buf,
+                      int buf_bytes);
+
 /* ---- data-parallel gradient exchange on RCCL -----------------------------------------------------------
  * The reference trains on one device (bin/train.py:82-89: the multi_gpu_model branch is disabled); what its single-device
  * semantics fix is that the loss normalisers count positives over the WHOLE batch (losses.py:62-66, :402-405) and that Adam clips

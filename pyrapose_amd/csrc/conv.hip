@@ -489,7 +489,7 @@ static void pick_tile(const pp_ctx* ctx, int M, int Nout, int* tm, int* tn) {
   static const int cand[4][2] = {{2, 2}, {1, 2}, {2, 1}, {1, 1}};
   static const double eff[4] = {1.0, 0.955, 0.92, 0.915};
   static const int slots[4] = {4, 5, 5, 8};
-  const int cus = ctx->n_cu > 0 ? ctx->n_cu : 256;
+  const int cus = pp_cus(ctx->n_cu);
   double best = 1e300;
   for (int i = 0; i < 4; ++i) {
     const int bm = 64 * cand[i][0], bn = 64 * cand[i][1];
@@ -501,10 +501,10 @@ static void pick_tile(const pp_ctx* ctx, int M, int Nout, int* tm, int* tn) {
       *tn = cand[i][1];
     }
   }
-  const char* e = getenv("PP_CONV_TILE");  // tuning hook: "tm,tn"
-  if (e && e[0] && e[1] == ',' && e[2]) {
-    *tm = e[0] - '0';
-    *tn = e[2] - '0';
+  char a, b;
+  if (pp_sw_tile("PP_CONV_TILE", &a, &b)) {  // tuning hook: "tm,tn"
+    *tm = a - '0';
+    *tn = b - '0';
   }
 }
 

@@ -1138,8 +1138,8 @@ extern "C" int PP_API(pp_grad_scale_from_counts_adj)(pp_ctx* ctx, const int* cou
   PP_REQUIRE_CTX(ctx);
   PP_CHECK_ARG(ctx, counts_dev && scale2_dev && n_counts >= 1 && n_counts <= 16 && log2_adjust >= -16 && log2_adjust <= 16, PP_ERR_ARG,
                "pp_grad_scale_from_counts: bad arguments");
-  static const int base_log2 = []() { const char* e = getenv("PP_GSCALE_LOG2"); const int v = e ? atoi(e) : 8; return v < -20 ? -20 : (v > 30 ? 30 : v); }();
-  hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(64), 0, ctx->stream, counts_dev, n_counts, scale2_dev, base_log2 + log2_adjust);
+  hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(64), 0, ctx->stream, counts_dev, n_counts, scale2_dev,
+                     pp_conv_switches().gscale_log2 + log2_adjust);
   PP_CHECK_LAUNCH(ctx, "pp_grad_scale_from_counts");
   return PP_OK;
 }
@@ -1247,29 +1247,6 @@ extern "C" int PP_API(pp_conv_split_weights_bf16x3)(pp_ctx* ctx, const pp_conv_d
 }
 namespace {
 
-static bool igemm3_fast_ok(const IgemmParams& p, bool planes, int w_rows, int w_ld8) {
-  // the branch-free loop needs a tap-linear gather and 31-bit byte offsets (see igemm3f_kernel)
-  static const bool fast_on = []() { const char* e = getenv("PP_CONV3_FAST"); return !(e && e[0] == '0'); }();
-  const long long a_bytes = p.src_rows * (long long)p.ld_src * 4;  // (packed planes take the same 4 bytes per element)
-  (void)planes;
-  const long long w_bytes = (long long)p.w_taps * w_rows * w_ld8 * 16;
-  int max_sw = 0;
-  for (int i = 0; i < p.n_seg; ++i) max_sw = p.seg[i].SW > max_sw ? p.seg[i].SW : max_sw;
-  return fast_on && p.div == 1 && p.kh * p.kw <= 31 && a_bytes < (1ll << 31) && w_bytes < (1ll << 31) &&
-         (long long)max_sw * p.ld_src * 4 < (1ll << 23) && p.src_rows > 0;
-}
-
-// the tap-row-reuse kernel applies: 3-wide stride-1 "same" geometry on an f32 operand (conditions of igemm3x_kernel)
-static bool igemm3x_ok(const IgemmParams& p, bool planes_in, bool planes_out, int w_rows, int w_ld8) {
-  static const bool x_on = []() { const char* e = getenv("PP_CONV3_XREUSE"); return !(e && e[0] == '0'); }();
-  bool same = x_on && igemm3_fast_ok(p, planes_in, w_rows, w_ld8) && !p.sc_on && p.kw == 3 && p.mul == 1 && p.div == 1 &&
-              (p.src != nullptr || planes_in) && (!planes_in || p.ld_src % 8 == 0) && p.w_tstep == 1 && p.w_tx0 == 0;
-  (void)planes_out;
-  for (int i = 0; i < p.n_seg && same; ++i)
-    same = p.seg[i].OH == p.seg[i].SH && p.seg[i].OW == p.seg[i].SW && p.seg[i].row_begin == p.seg[i].src_row_begin;
-  return same;
-}
-
 // ---- sparse data gradient of a 3x3 stride-1 conv: which 32-row OUTPUT blocks can a non-zero of dy reach? ----
 // Output row m reads dy rows m + dy * W + dx, dy, dx in {-1, 0, 1} (W = width of m's level): block b is live when a flagged
 // dy block intersects one of the three 34-row windows [32 b - 1 + j W, 32 b + 32 + j W], j = -1, 0, 1 -- exact in 2-D up to
@@ -1351,59 +1328,62 @@ __global__ void rl_fill_kernel(const IgemmParams p, const unsigned char* __restr
   }
 }
 
-__global__ void row_block_compact_kernel(const unsigned char* __restrict__ flags, int n_blocks, int* __restrict__ list);
+// the operands of one forward / data-gradient launch, beside IgemmParams
+struct Igemm3Args {
+  const void *ahi, *alo, *whi, *wlo;  // gathered operand as planes (NULL: p.src), weight planes
+  int w_rows, w_ld8;
+  void *ohi, *olo;                    // output planes (may be NULL)
+  void *chi, *clo;                    // may be NULL: also write the split of the gathered f32 operand (pp_conv_opts.capture_hi / capture_lo) --
+                                      // inside the tap-row-reuse kernel where that one runs, by a separate pass over the operand otherwise
+  const unsigned char* flags;         // may be NULL: the row-block flags of the gathered operand
+  float* ws;                          // the context's scratch (may be NULL)
+};
+
+static PpIgemmFacts igemm3_facts(const pp_ctx* ctx, const IgemmParams& p, const Igemm3Args& a) {
+  return igemm_facts(p, a.w_rows, a.w_ld8, a.ahi != nullptr, p.src != nullptr, a.ohi != nullptr, p.out != nullptr, a.chi != nullptr,
+                     a.flags != nullptr, ctx->n_cu, ctx->ws != nullptr, (long long)ctx->ws_bytes);
+}
+
+// adds the split-K slices of rows p.m_off .. M - 1 and writes the output (planes included)
+static void launch_splitk_finish(hipStream_t st, const IgemmParams& p, int splits, const float* ws, unsigned blocks, void* ohi, void* olo) {
+  hipLaunchKernelGGL(splitk_finish_kernel, dim3(blocks), dim3(256), 0, st, p, splits, ws, p.bias, p.addend, p.mask_src, p.out, ohi, olo);
+}
 
 // the whole sparse bwd-data: dilate -> compact -> igemm3f over the listed blocks -> fill the others.  scratch: n_blocks bytes
 // + (n_blocks + 1) ints behind the caller's flags / list (pp_row_block_list documents the sizes).
-// ws / ws_bytes: the split-K scratch (may be NULL).  The listed tiles are few (a fifth of the rows on the bench targets: ~320
-// workgroups of 144 k-steps each on 256 CUs, every one of them alone with its load latencies): with a scratch buffer the
-// reduction is split two ways (PP_SPARSE_DGRAD_SPLITS) and rl_splitk_finish_kernel adds the slices of the listed blocks.
 // dy_flags == NULL (forward, pp_conv_opts.out_flags): out_flags are given -- no dilation, and the rows of the other blocks
 // are left as they are (fill = false).
 template <int TM, int TN>
-static void launch_igemm3_rowlist(hipStream_t st, IgemmParams& p, const void* ahi, const void* alo, const void* whi, const void* wlo, int w_rows,
-                                  int w_ld8, void* ohi, void* olo, const unsigned char* dy_flags, unsigned char* out_flags, int* out_list,
-                                  float* ws, size_t ws_bytes, bool fill = true) {
+static void launch_igemm3_rowlist(hipStream_t st, IgemmParams& p, const Igemm3Args& a, const PpIgemmPlan& pl, const unsigned char* dy_flags,
+                                  unsigned char* out_flags, int* out_list, bool fill) {
   // (dy_flags also masks the gather: rows of the gathered tensor outside its flagged blocks are never fetched)
-  constexpr int BM = 64 * TM, BN = 64 * TN;
-  const int nb = (p.M + 31) / 32;
-  static const int want_splits = []() { const char* e = getenv("PP_SPARSE_DGRAD_SPLITS"); return e ? atoi(e) : 2; }();
-  const int n_steps = p.kh * p.kw * (p.Cred / 32);
-  int splits = 1;
-  if (ws && want_splits > 1 && (ohi || p.out)) {
-    const long long slice_bytes = (long long)nb * 32 * p.ld_out * 4;
-    splits = want_splits;
-    while (splits > 1 && (n_steps / splits < 24 || slice_bytes * splits > (long long)ws_bytes)) --splits;
-  }
-  if (dy_flags) hipLaunchKernelGGL(rl_dilate_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, p, dy_flags, out_flags, nb);
-  hipLaunchKernelGGL(row_block_compact_kernel, dim3(1), dim3(256), 0, st, (const unsigned char*)out_flags, nb, out_list);
-  p.n_tiles_n = (p.Nout + BN - 1) / BN;
-  const int n_tiles_m = (nb + BM / 32 - 1) / (BM / 32);
-  const long long a_bytes = p.src_rows * (long long)p.ld_src * 4, w_bytes = (long long)p.w_taps * w_rows * w_ld8 * 16;
-  const dim3 grid((unsigned)(n_tiles_m * p.n_tiles_n * splits));
-  if (ahi && !ohi)  // planes in, float32 out (a head's last conv in the forward pass)
-    hipLaunchKernelGGL((igemm3f_kernel<TM, TN, true, false, false, true>), grid, dim3(256), 0, st, p, ahi, alo, (unsigned)a_bytes, whi, wlo,
-                       (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)nullptr, (uint2*)nullptr, w_rows, w_ld8, splits,
-                       splits > 1 ? ws : (float*)nullptr, (const int*)out_list, dy_flags);
-  else if (ahi)  // planes in, planes out
-    hipLaunchKernelGGL((igemm3f_kernel<TM, TN, true, true, false, true>), grid, dim3(256), 0, st, p, ahi, alo, (unsigned)a_bytes, whi, wlo,
-                       (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)ohi, (uint2*)olo, w_rows, w_ld8, splits,
-                       splits > 1 ? ws : (float*)nullptr, (const int*)out_list, dy_flags);
+  const int nb = (p.M + 31) / 32, splits = pl.splits;
+  float* const ws = splits > 1 ? a.ws : nullptr;
+  const unsigned a_bytes = (unsigned)(p.src_rows * (long long)p.ld_src * 4), w_bytes = (unsigned)((long long)p.w_taps * a.w_rows * a.w_ld8 * 16);
+  const dim3 grid(pl.grid), wg(256);
+  p.n_tiles_n = pl.n_tiles_n;
+  if (dy_flags) hipLaunchKernelGGL(rl_dilate_kernel, dim3((unsigned)((nb + 255) / 256)), wg, 0, st, p, dy_flags, out_flags, nb);
+  hipLaunchKernelGGL(row_block_compact_kernel, dim3(1), wg, 0, st, (const unsigned char*)out_flags, nb, out_list);
+  if (a.ahi && !a.ohi)  // planes in, float32 out (a head's last conv in the forward pass)
+    hipLaunchKernelGGL((igemm3f_kernel<TM, TN, true, false, false, true>), grid, wg, 0, st, p, a.ahi, a.alo, a_bytes, a.whi, a.wlo, w_bytes, p.bias,
+                       p.addend, p.mask_src, p.out, (uint2*)nullptr, (uint2*)nullptr, a.w_rows, a.w_ld8, splits, ws, (const int*)out_list, dy_flags);
+  else if (a.ahi)  // planes in, planes out
+    hipLaunchKernelGGL((igemm3f_kernel<TM, TN, true, true, false, true>), grid, wg, 0, st, p, a.ahi, a.alo, a_bytes, a.whi, a.wlo, w_bytes, p.bias,
+                       p.addend, p.mask_src, p.out, (uint2*)a.ohi, (uint2*)a.olo, a.w_rows, a.w_ld8, splits, ws, (const int*)out_list, dy_flags);
   else
-    hipLaunchKernelGGL((igemm3f_kernel<TM, TN, false, false, false, true>), grid, dim3(256), 0, st, p, (const void*)p.src, nullptr,
-                       (unsigned)a_bytes, whi, wlo, (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)nullptr, (uint2*)nullptr,
-                       w_rows, w_ld8, splits, splits > 1 ? ws : (float*)nullptr, (const int*)out_list, dy_flags);
-  if (splits > 1)
-    hipLaunchKernelGGL(rl_splitk_finish_kernel, dim3((unsigned)nb), dim3(256), 0, st, p, splits, (const float*)ws, (const int*)out_list, p.bias,
-                       p.addend, p.mask_src, p.out, ohi, olo);
+    hipLaunchKernelGGL((igemm3f_kernel<TM, TN, false, false, false, true>), grid, wg, 0, st, p, (const void*)p.src, nullptr, a_bytes, a.whi, a.wlo,
+                       w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)nullptr, (uint2*)nullptr, a.w_rows, a.w_ld8, splits, ws,
+                       (const int*)out_list, dy_flags);
+  if (pl.finish_blocks)
+    hipLaunchKernelGGL(rl_splitk_finish_kernel, dim3(pl.finish_blocks), wg, 0, st, p, splits, (const float*)a.ws, (const int*)out_list, p.bias,
+                       p.addend, p.mask_src, p.out, a.ohi, a.olo);
   // In place on the addend (dx == the running sum of the other data gradients of this tensor, no ReLU mask): the rows that no
   // non-zero reaches already hold their value -- nothing to fill (the shared pyramid features' gradient: 103 MB not moved).
-  const bool in_place = (ohi != nullptr && p.add_hi == (const void*)ohi && p.ld_add == p.ld_out && !p.out && !p.addend && !p.mask_hi &&
+  const bool in_place = (a.ohi != nullptr && p.add_hi == (const void*)a.ohi && p.ld_add == p.ld_out && !p.out && !p.addend && !p.mask_hi &&
                          !p.mask_src && !p.relu) ||
-                        (p.out != nullptr && p.addend == p.out && p.ld_add == p.ld_out && !ohi && !p.add_hi && !p.mask_hi && !p.mask_src && !p.relu);
+                        (p.out != nullptr && p.addend == p.out && p.ld_add == p.ld_out && !a.ohi && !p.add_hi && !p.mask_hi && !p.mask_src && !p.relu);
   if (fill && !in_place)
-    hipLaunchKernelGGL(rl_fill_kernel, dim3((unsigned)nb), dim3(256), 0, st, p, (const unsigned char*)out_flags, p.addend, p.mask_src, p.out, ohi,
-                       olo);
+    hipLaunchKernelGGL(rl_fill_kernel, dim3((unsigned)nb), wg, 0, st, p, (const unsigned char*)out_flags, p.addend, p.mask_src, p.out, a.ohi, a.olo);
 }
 
 static void split_capture_pass(hipStream_t st, const IgemmParams& p, void* chi, void* clo) {
@@ -1413,294 +1393,125 @@ static void split_capture_pass(hipStream_t st, const IgemmParams& p, void* chi, 
   hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)blocks), dim3(256), 0, st, n8, (const float4*)p.src, (uint4*)chi, (uint4*)clo, (const float*)nullptr);
 }
 
-// chi / clo (may be NULL): also write the bf16 split of the gathered f32 operand (pp_conv_opts.capture_hi / capture_lo) -- inside the
-// tap-row-reuse kernel where that one runs, by a separate pass over the operand otherwise
+// the launches of one plan (conv_plan.h: pp_plan_igemm decided everything) on its tile
 template <int TM, int TN>
-static void launch_igemm3(hipStream_t st, IgemmParams& p, const void* ahi, const void* alo, const void* whi, const void* wlo, int w_rows,
-                          int w_ld8, void* ohi, void* olo, int splits, float* ws, void* chi = nullptr, void* clo = nullptr,
-                          const unsigned char* flags = nullptr, float* ws_any = nullptr, size_t ws_any_bytes = 0, int n_cu = 256) {
-  constexpr int BM = 64 * TM, BN = 64 * TN;
-  p.n_tiles_n = (p.Nout + BN - 1) / BN;
-  const int n_tiles_m = (p.M + BM - 1) / BM;
-  const dim3 grid((unsigned)(n_tiles_m * p.n_tiles_n * splits));
-  const bool fast = igemm3_fast_ok(p, ahi != nullptr, w_rows, w_ld8);
-  const long long a_bytes = p.src_rows * (long long)p.ld_src * 4;
-  const long long w_bytes = (long long)p.w_taps * w_rows * w_ld8 * 16;
-  if (p.sc_on) {  // parity-class launch of a stride-2 bwd-data (host guarantees: fast, no split, planes on both sides or on neither)
-    if (ahi)
-      hipLaunchKernelGGL((igemm3f_kernel<TM, TN, true, true, true>), grid, dim3(256), 0, st, p, ahi, alo, (unsigned)a_bytes, whi, wlo,
-                         (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)ohi, (uint2*)olo, w_rows, w_ld8, 1, nullptr);
-    else
-      hipLaunchKernelGGL((igemm3f_kernel<TM, TN, false, false, true>), grid, dim3(256), 0, st, p, (const void*)p.src, nullptr, (unsigned)a_bytes,
-                         whi, wlo, (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)nullptr, (uint2*)nullptr, w_rows, w_ld8, 1,
-                         nullptr);
-    return;
-  }
-  {
-    // (the 256-row tile has the tap-row-reuse kernel for plane-stored operands only: its f32 form would need 32 more staging registers)
-    if (igemm3x_ok(p, ahi != nullptr, ohi != nullptr, w_rows, w_ld8) && (TM <= 2 || (ahi != nullptr && !chi))) {
-      const int n_tiles_mx = (p.M + BM - 3) / (BM - 2);  // tiles overlap by two rows
-      int skip_halo = 0;
-      for (int i = 0; i < p.n_seg; ++i) skip_halo = p.seg[i].SW + 1 > skip_halo ? p.seg[i].SW + 1 : skip_halo;
-      const dim3 gridx((unsigned)(n_tiles_mx * p.n_tiles_n * splits));
-      static const int x_order = []() { const char* e = getenv("PP_CONV3_X_ORDER"); return e ? atoi(e) : 1; }();
-      p.x_ty_inner = x_order;
-      // with split-K the partial sums go to the f32 scratch and splitk_finish_kernel writes the output (planes included)
-      const bool op = ohi != nullptr && splits == 1;
-      if constexpr (TM <= 2) {
-        if (chi) {
-          hipLaunchKernelGGL((igemm3x_kernel<TM, TN, true>), gridx, dim3(256), 0, st, p, (const void*)p.src, nullptr, (unsigned)a_bytes, whi, wlo,
-                             (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)nullptr, (uint2*)nullptr, w_rows, w_ld8, splits,
-                             ws, chi, clo, flags, skip_halo);
-          return;
-        }
-      }
+static void launch_igemm3(hipStream_t st, IgemmParams& p, const Igemm3Args& a, const PpIgemmPlan& pl) {
+  const dim3 grid(pl.grid), wg(256);
+  const unsigned a_bytes = (unsigned)(p.src_rows * (long long)p.ld_src * 4), w_bytes = (unsigned)((long long)p.w_taps * a.w_rows * a.w_ld8 * 16);
+  const int splits = pl.splits;
+  float* const ws = splits > 1 ? a.ws : nullptr;  // partial sums -> scratch; splitk_finish_kernel writes the output
+  uint2 *const no_hi = nullptr, *const no_lo = nullptr;
+  p.n_tiles_n = pl.n_tiles_n;
+  p.x_ty_inner = pl.x_ty_inner;
+  if (pl.capture_first) split_capture_pass(st, p, a.chi, a.clo);
+  switch (pl.family) {
+    case PP_IGEMM3F_CLASS:
+      if (a.ahi)
+        hipLaunchKernelGGL((igemm3f_kernel<TM, TN, true, true, true>), grid, wg, 0, st, p, a.ahi, a.alo, a_bytes, a.whi, a.wlo, w_bytes, p.bias, p.addend,
+                           p.mask_src, p.out, (uint2*)a.ohi, (uint2*)a.olo, a.w_rows, a.w_ld8, 1, nullptr);
+      else
+        hipLaunchKernelGGL((igemm3f_kernel<TM, TN, false, false, true>), grid, wg, 0, st, p, (const void*)p.src, nullptr, a_bytes, a.whi, a.wlo, w_bytes,
+                           p.bias, p.addend, p.mask_src, p.out, no_hi, no_lo, a.w_rows, a.w_ld8, 1, nullptr);
+      return;
+    case PP_IGEMM3X_CAPTURE:
+      if constexpr (TM <= 2)
+        hipLaunchKernelGGL((igemm3x_kernel<TM, TN, true>), grid, wg, 0, st, p, (const void*)p.src, nullptr, a_bytes, a.whi, a.wlo, w_bytes, p.bias,
+                           p.addend, p.mask_src, p.out, no_hi, no_lo, a.w_rows, a.w_ld8, splits, ws, a.chi, a.clo, a.flags, pl.skip_halo);
+      break;
+    case PP_IGEMM4X:
       if constexpr (TM == 2 && TN == 2) {
-        // the multi-stage LDS-DMA form of this launch (igemm4x_kernel: planes in and out, at least two rounds of 256 x 128 tiles);
-        // PP_CONV3_DMA=0 keeps everything on igemm3x
-        // (read at every launch, unlike the other knobs: tests compare the two kernels inside one process)
-        const char* const dma_env = getenv("PP_CONV3_DMA");
-        const bool dma_on = !(dma_env && dma_env[0] == '0');
-        if (dma_on && ahi && op && !flags && splits == 1 && p.kh == 3 && x_order == 1 && w_rows % 128 == 0 && p.Cred % 32 == 0) {
-          constexpr int BM4 = 256;
-          const int n_tiles_m4 = (p.M + BM4 - 3) / (BM4 - 2);
-          const int ntn = (p.Nout + 127) / 128;
-          // (one workgroup per CU: a launch of less than two rounds is better off with three 128 x 128 workgroups per CU)
-          // between one and two rounds (the 256-channel heads: 398 tiles) one launch CAN pay in isolation when the second round is
-          // at least half full (PP_CONV3_DMA_FRAC=50: class head 149 us against 162; 1.19 rounds do not: mask head 137 / 115) -- but in
-          // the training step those launches run beside the regression head's on the other lane, and two 115 KB workgroups cannot
-          // share a CU where a 33 KB one fits next to this kernel's: the step LOSES 2.4 % (594 vs 608 images/s).  Off by default.
-          static const int dma_min = []() { const char* e = getenv("PP_CONV3_DMA_MIN"); return e ? atoi(e) : 512; }();
-          static const int dma_frac = []() { const char* e = getenv("PP_CONV3_DMA_FRAC"); return e ? atoi(e) : 1000; }();  // percent
-          const int n_blk = n_tiles_m4 * ntn;
-          const bool one_and_a_bit = n_blk > n_cu && n_blk < 2 * n_cu && (n_blk - n_cu) * 100 >= dma_frac * n_cu;
-          if (n_blk >= dma_min || one_and_a_bit) {
-            // Whole rounds of 256 x 128 tiles go to igemm4x; with one workgroup per CU a last, partly filled round would cost a
-            // full round's time, so the rows of that round are a second launch: 128 x 128 tiles of igemm3x with the reduction
-            // split over enough workgroups to fill the chip once (partial sums -> scratch, splitk_finish_kernel writes the rows)
-            static const bool tail_on = []() { const char* e = getenv("PP_CONV3_DMA_TAIL"); return !(e && e[0] == '0'); }();
-            int full_rt = n_tiles_m4;
-            const int rounds = (n_tiles_m4 * ntn) / n_cu;
-            // (a last round that is mostly full stays in the one launch: 720 x 540 gives 1 016 tiles = 3.97 rounds)
-            static const int tail_frac = []() { const char* e = getenv("PP_CONV3_DMA_TAIL_FRAC"); return e ? atoi(e) : 60; }();  // percent
-            const int last = (n_tiles_m4 * ntn) % n_cu;
-            if (tail_on && last != 0 && last * 100 < tail_frac * n_cu && rounds >= 2 && ws_any != nullptr) full_rt = rounds * n_cu / ntn;
-            const int m_split = full_rt * (BM4 - 2);
-            int tail_splits = 0;
-            if (full_rt < n_tiles_m4) {
-              const int rem = p.M - m_split;
-              const int n_rt = (rem + BM - 3) / (BM - 2);
-              const int groups = p.kh * (p.Cred / 32);
-              int sp = (3 * n_cu + n_rt * ntn - 1) / (n_rt * ntn);  // ~ one full round of three workgroups per CU
-              while (sp > 1 && (groups / sp < 4 || (size_t)sp * rem * p.ld_out * 4 > ws_any_bytes)) --sp;
-              if (sp > 1) tail_splits = sp;
-              else full_rt = n_tiles_m4;  // (no room to split: everything in the one launch)
-            }
-            p.n_tiles_n = ntn;
-            // scheduling variants (measured on the regression-head launch, P16): 1 = no iglp_opt hint in the k-step (default: 442 us
-            // against 465 with igemm3x's hint, 0), 2 / 3 = s_setprio around the MFMAs of 0 / 1 (466 / 461), 4 = igemm3f's sched_barrier
-            const char* const e_var = getenv("PP_CONV3_DMA_VAR");  // (per launch: A/B in one process)
-            const int var = e_var ? atoi(e_var) : 1;
-            auto go4 = [&](auto v) {
-              hipLaunchKernelGGL((igemm4x_kernel<true, decltype(v)::value>), dim3((unsigned)(full_rt * ntn)), dim3(512), 0, st, p, ahi, alo,
-                                 (unsigned)a_bytes, whi, wlo, (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)ohi, (uint2*)olo, w_rows,
-                                 w_ld8);
-            };
-            if (var == 0) go4(std::integral_constant<int, 0>{});
-            else if (var == 2) go4(std::integral_constant<int, 2>{});
-            else if (var == 3) go4(std::integral_constant<int, 3>{});
-            else if (var == 4) go4(std::integral_constant<int, 4>{});
-            else if (var == 9) go4(std::integral_constant<int, 9>{});
-            else go4(std::integral_constant<int, 1>{});
-            if (tail_splits > 1) {
-              IgemmParams q = p;
-              q.m_off = full_rt * (BM4 - 2);
-              const int rem = q.M - q.m_off;
-              const int n_rt = (rem + BM - 3) / (BM - 2);
-              hipLaunchKernelGGL((igemm3x_kernel<TM, TN, false, true, false>), dim3((unsigned)(n_rt * ntn * tail_splits)), dim3(256), 0, st, q, ahi,
-                                 alo, (unsigned)a_bytes, whi, wlo, (unsigned)w_bytes, q.bias, q.addend, q.mask_src, q.out, (uint2*)nullptr,
-                                 (uint2*)nullptr, w_rows, w_ld8, tail_splits, ws_any, nullptr, nullptr, (const unsigned char*)nullptr, skip_halo);
-              const long long total = (long long)rem * ((q.Nout + 3) >> 2);
-              long long blocks = (total + 255) / 256;
-              if (blocks > (long long)n_cu * 8) blocks = (long long)n_cu * 8;
-              hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, st, q, tail_splits, (const float*)ws_any, q.bias, q.addend,
-                                 q.mask_src, q.out, ohi, olo);
-            }
-            return;
-          }
-          // Round 4: launches too small for two rounds of 256-row tiles (the 256-channel heads, the FPN 3x3: 1.2-1.6 rounds of 128-row
-          // tiles on 2 x 256 slots) CAN take the 128 x 128 form of the same pipeline, two workgroups per CU (PP_CONV3_DMA2=1: opt-in;
-          // PP_CONV3_DMA2_MIN: fewest 128-row tiles, default one round)
-          const char* const e_dma2 = getenv("PP_CONV3_DMA2");  // (per launch, like PP_CONV3_DMA)
-          // (off by default: +8 % on the class-head launch, -8 % on the mask head / FPN launches -- 610 tiles on 512 slots --, -2 % on
-          // the training step, profiles/r04_lds_dma_128_row_tiles.txt)
-          const bool dma2_on = e_dma2 && e_dma2[0] == '1';
-          static const int dma2_min = []() { const char* e = getenv("PP_CONV3_DMA2_MIN"); return e ? atoi(e) : 512; }();
-          if (dma2_on && n_tiles_mx * ntn >= dma2_min) {
-            p.n_tiles_n = ntn;
-            hipLaunchKernelGGL((igemm4x_kernel<true, 1, 2>), dim3((unsigned)(n_tiles_mx * ntn)), dim3(256), 0, st, p, ahi, alo, (unsigned)a_bytes, whi,
-                               wlo, (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)ohi, (uint2*)olo, w_rows, w_ld8);
-            return;
-          }
+        auto go4 = [&](auto v) {
+          hipLaunchKernelGGL((igemm4x_kernel<true, decltype(v)::value>), grid, dim3(512), 0, st, p, a.ahi, a.alo, a_bytes, a.whi, a.wlo, w_bytes, p.bias,
+                             p.addend, p.mask_src, p.out, (uint2*)a.ohi, (uint2*)a.olo, a.w_rows, a.w_ld8);
+        };
+        if (pl.variant == 0) go4(std::integral_constant<int, 0>{});
+        else if (pl.variant == 2) go4(std::integral_constant<int, 2>{});
+        else if (pl.variant == 3) go4(std::integral_constant<int, 3>{});
+        else if (pl.variant == 4) go4(std::integral_constant<int, 4>{});
+        else if (pl.variant == 9) go4(std::integral_constant<int, 9>{});
+        else go4(std::integral_constant<int, 1>{});
+        if (pl.tail_splits > 1) {  // the rows of the last, partly filled round
+          IgemmParams q = p;
+          q.m_off = pl.tail_m_off;
+          hipLaunchKernelGGL((igemm3x_kernel<TM, TN, false, true, false>), dim3(pl.tail_grid), wg, 0, st, q, a.ahi, a.alo, a_bytes, a.whi, a.wlo, w_bytes,
+                             q.bias, q.addend, q.mask_src, q.out, no_hi, no_lo, a.w_rows, a.w_ld8, pl.tail_splits, a.ws, nullptr, nullptr,
+                             (const unsigned char*)nullptr, pl.skip_halo);
+          launch_splitk_finish(st, q, pl.tail_splits, a.ws, pl.finish_blocks, a.ohi, a.olo);
         }
       }
-      if (ahi && op)
-        hipLaunchKernelGGL((igemm3x_kernel<TM, TN, false, true, true>), gridx, dim3(256), 0, st, p, ahi, alo, (unsigned)a_bytes, whi, wlo,
-                           (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)ohi, (uint2*)olo, w_rows, w_ld8, splits, ws, nullptr,
-                           nullptr, flags, skip_halo);
-      else if (ahi)
-        hipLaunchKernelGGL((igemm3x_kernel<TM, TN, false, true, false>), gridx, dim3(256), 0, st, p, ahi, alo, (unsigned)a_bytes, whi, wlo,
-                           (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)nullptr, (uint2*)nullptr, w_rows, w_ld8, splits, ws,
-                           nullptr, nullptr, flags, skip_halo);
-      else if constexpr (TM <= 2) {
-        if (op)
-          hipLaunchKernelGGL((igemm3x_kernel<TM, TN, false, false, true>), gridx, dim3(256), 0, st, p, (const void*)p.src, nullptr,
-                             (unsigned)a_bytes, whi, wlo, (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)ohi, (uint2*)olo,
-                             w_rows, w_ld8, splits, ws, nullptr, nullptr, flags, skip_halo);
+      return;
+    case PP_IGEMM4X2:
+      if constexpr (TM == 2 && TN == 2)
+        hipLaunchKernelGGL((igemm4x_kernel<true, 1, 2>), grid, wg, 0, st, p, a.ahi, a.alo, a_bytes, a.whi, a.wlo, w_bytes, p.bias, p.addend, p.mask_src,
+                           p.out, (uint2*)a.ohi, (uint2*)a.olo, a.w_rows, a.w_ld8);
+      return;
+    case PP_IGEMM4P:
+      if constexpr (TM == 2 && TN == 2)
+        PP_API(pp4_launch_igemm4p)(st, p, a.ahi, a.whi, a.wlo, a.w_rows, a.w_ld8, a.ohi, a.olo, splits, ws, pl.grid, pl.stages);
+      break;
+    case PP_IGEMM3X_PP:
+      hipLaunchKernelGGL((igemm3x_kernel<TM, TN, false, true, true>), grid, wg, 0, st, p, a.ahi, a.alo, a_bytes, a.whi, a.wlo, w_bytes, p.bias, p.addend,
+                         p.mask_src, p.out, (uint2*)a.ohi, (uint2*)a.olo, a.w_rows, a.w_ld8, splits, ws, nullptr, nullptr, a.flags, pl.skip_halo);
+      break;
+    case PP_IGEMM3X_PF:
+      hipLaunchKernelGGL((igemm3x_kernel<TM, TN, false, true, false>), grid, wg, 0, st, p, a.ahi, a.alo, a_bytes, a.whi, a.wlo, w_bytes, p.bias, p.addend,
+                         p.mask_src, p.out, no_hi, no_lo, a.w_rows, a.w_ld8, splits, ws, nullptr, nullptr, a.flags, pl.skip_halo);
+      break;
+    case PP_IGEMM3X_FP:
+      if constexpr (TM <= 2)
+        hipLaunchKernelGGL((igemm3x_kernel<TM, TN, false, false, true>), grid, wg, 0, st, p, (const void*)p.src, nullptr, a_bytes, a.whi, a.wlo, w_bytes,
+                           p.bias, p.addend, p.mask_src, p.out, (uint2*)a.ohi, (uint2*)a.olo, a.w_rows, a.w_ld8, splits, ws, nullptr, nullptr, a.flags,
+                           pl.skip_halo);
+      break;
+    case PP_IGEMM3X_FF:
+      if constexpr (TM <= 2)
+        hipLaunchKernelGGL((igemm3x_kernel<TM, TN, false>), grid, wg, 0, st, p, (const void*)p.src, nullptr, a_bytes, a.whi, a.wlo, w_bytes, p.bias,
+                           p.addend, p.mask_src, p.out, no_hi, no_lo, a.w_rows, a.w_ld8, splits, ws, nullptr, nullptr, a.flags, pl.skip_halo);
+      break;
+    default: {  // PP_IGEMM3F / PP_IGEMM3, four operand forms each
+      void *const ohi = splits > 1 ? nullptr : a.ohi, *const olo = splits > 1 ? nullptr : a.olo;
+      auto go = [&](auto ap, auto op) {
+        constexpr bool AP = decltype(ap)::value, OP = decltype(op)::value;
+        if (pl.family == PP_IGEMM3F)
+          hipLaunchKernelGGL((igemm3f_kernel<TM, TN, AP, OP>), grid, wg, 0, st, p, AP ? a.ahi : (const void*)p.src, AP ? a.alo : nullptr, a_bytes, a.whi,
+                             a.wlo, w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)ohi, (uint2*)olo, a.w_rows, a.w_ld8, splits, ws);
         else
-          hipLaunchKernelGGL((igemm3x_kernel<TM, TN, false>), gridx, dim3(256), 0, st, p, (const void*)p.src, nullptr, (unsigned)a_bytes, whi,
-                             wlo, (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)nullptr, (uint2*)nullptr, w_rows, w_ld8, splits,
-                             ws, nullptr, nullptr, flags, skip_halo);
-      }
-      return;
+          hipLaunchKernelGGL((igemm3_kernel<TM, TN, AP, OP>), grid, wg, 0, st, p, p.src, (const uint4*)(AP ? a.ahi : nullptr),
+                             (const uint4*)(AP ? a.alo : nullptr), (const uint4*)a.whi, (const uint4*)a.wlo, p.bias, p.addend, p.mask_src, p.out,
+                             (uint2*)ohi, (uint2*)olo, a.w_rows, a.w_ld8);
+      };
+      if (a.ahi && ohi) go(std::true_type{}, std::true_type{});
+      else if (a.ahi) go(std::true_type{}, std::false_type{});
+      else if (ohi) go(std::false_type{}, std::true_type{});
+      else go(std::false_type{}, std::false_type{});
     }
   }
-  if (chi) split_capture_pass(st, p, chi, clo);
-  if (splits > 1) ohi = olo = nullptr;  // partial sums -> scratch; splitk_finish_kernel writes the planes
-  auto go = [&](auto ap, auto op) {
-    constexpr bool AP = decltype(ap)::value, OP = decltype(op)::value;
-    if (fast)
-      hipLaunchKernelGGL((igemm3f_kernel<TM, TN, AP, OP>), grid, dim3(256), 0, st, p, AP ? ahi : (const void*)p.src, AP ? alo : nullptr,
-                         (unsigned)a_bytes, whi, wlo, (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)ohi, (uint2*)olo,
-                         w_rows, w_ld8, splits, ws);
-    else
-      hipLaunchKernelGGL((igemm3_kernel<TM, TN, AP, OP>), grid, dim3(256), 0, st, p, p.src, (const uint4*)(AP ? ahi : nullptr),
-                         (const uint4*)(AP ? alo : nullptr), (const uint4*)whi, (const uint4*)wlo, p.bias, p.addend, p.mask_src, p.out,
-                         (uint2*)ohi, (uint2*)olo, w_rows, w_ld8);
-  };
-  if (ahi && ohi) go(std::true_type{}, std::true_type{});
-  else if (ahi) go(std::true_type{}, std::false_type{});
-  else if (ohi) go(std::false_type{}, std::true_type{});
-  else go(std::false_type{}, std::false_type{});
+  if (pl.finish_blocks) launch_splitk_finish(st, p, splits, a.ws, pl.finish_blocks, a.ohi, a.olo);
 }
 
-static void pick_tile3(const pp_ctx* ctx, int M, int Nout, int ld_out, int n_steps, bool may_split, bool x_ok, int* tm, int* tn, int* splits) {
-  // measured in-flight rates relative to 128x128 (tools/conv_bench.py): the LDS store path (ds_write_b128 of the
-  // staged tiles) costs ~30 % of the loop, so the tile with the fewest staged bytes per MFMA wins when it fills the chip.
-  // A workgroup costs (its k-steps + ~8 steps' worth of prologue, epilogue and launch ramp) x tile area; splitting the
-  // reduction S ways multiplies the workgroups and pays S x the output in f32 atomics plus the finishing pass.
-  static const int cand[5][2] = {{4, 2}, {2, 2}, {1, 2}, {2, 1}, {1, 1}};
-  static const double eff[5] = {1.1, 1.0, 0.9, 0.9, 0.8};
-  static const int slots[5] = {2, 3, 4, 4, 4};
-  static const int split_cand[8] = {1, 2, 3, 4, 6, 8, 12, 16};
-  const int cus = ctx->n_cu > 0 ? ctx->n_cu : 256;
-  const long long ws_bytes = (long long)ctx->ws_bytes;
-  double best = 1e300;
-  *splits = 1;
-  for (int i = 0; i < 5; ++i) {
-    const int bm = 64 * cand[i][0], bn = 64 * cand[i][1];
-    const long long blocks = (long long)((M + bm - 1) / bm) * ((Nout + bn - 1) / bn);
-    for (int si = 0; si < (may_split ? 8 : 1); ++si) {
-      const int sp = split_cand[si];
-      if (sp > 1 && (n_steps / sp < 8 || (long long)sp * M * ld_out * 4 > ws_bytes)) break;
-      const double steps = (double)((n_steps + sp - 1) / sp) + 8.0;
-      double t = est_rounds(blocks * sp, slots[i], cus) * steps * cand[i][0] * cand[i][1] / eff[i];
-      if (sp > 1) {
-        // slices: sp x M x N x 4 B written and read back (~4 TB/s), the epilogue operands, one more launch; one k-step
-        // of a 128x128 tile ~ 2.1 us when the chip is full  ->  convert microseconds to the same step units
-        const double us = (double)M * Nout * (8.0 * sp + 12.0) / 4.0e6 + 4.0;
-        t += us / 2.1 * 4.0;
-      }
-      if (t < best * 0.97) {
-        best = t;
-        *tm = cand[i][0];
-        *tn = cand[i][1];
-        *splits = sp;
-      }
-    }
-  }
-  // the 256x128 tile has no tap-row-reuse variant: where that kernel applies, 128x128 with reuse wins (measured on the
-  // 256-channel class head, 50400 rows: 194-207 us against 205-227 us; a reuse bonus inside the model above instead sent
-  // that shape to 64x128 and the step lost 2 %)
-  static const bool x4 = []() { const char* e = getenv("PP_CONV3_X4"); return e && e[0] == '1'; }();
-  if (x_ok && *tm == 4 && *splits == 1 && !x4) {
-    *tm = 2;
-    *tn = 2;
-  }
-  const char* e = getenv("PP_CONV3_TILE");
-  if (e && e[0] && e[1] == ',' && e[2]) {
-    *tm = e[0] - '0';
-    *tn = e[2] - '0';
-  }
-  if (const char* es = getenv("PP_CONV3_SPLITS")) {
-    const int v = atoi(es);
-    if (v >= 1 && (v == 1 || (may_split && n_steps / v >= 1 && (long long)v * M * ld_out * 4 <= ws_bytes))) *splits = v;
-  }
+// facts -> plan -> launch of one forward / data-gradient GEMM
+static void dispatch3(pp_ctx* ctx, IgemmParams& p, const Igemm3Args& a) {
+  const PpIgemmFacts f = igemm3_facts(ctx, p, a);
+  const PpIgemmPlan pl = pp_plan_igemm(f);
+  pp_plan_debug(f, pl);
+  if (pl.tm == 4) launch_igemm3<4, 2>(ctx->stream, p, a, pl);
+  else if (pl.tm == 2 && pl.tn == 2) launch_igemm3<2, 2>(ctx->stream, p, a, pl);
+  else if (pl.tm == 1 && pl.tn == 2) launch_igemm3<1, 2>(ctx->stream, p, a, pl);
+  else if (pl.tm == 2 && pl.tn == 1) launch_igemm3<2, 1>(ctx->stream, p, a, pl);
+  else launch_igemm3<1, 1>(ctx->stream, p, a, pl);
 }
 
-static void dispatch3(pp_ctx* ctx, IgemmParams& p, const void* ahi, const void* alo, const void* whi, const void* wlo, int w_rows,
-                      int w_ld8, void* ohi, void* olo, void* chi = nullptr, void* clo = nullptr, const unsigned char* flags = nullptr) {
-  int tm, tn, splits;
-  const int n_steps = p.kh * p.kw * (p.Cred / 32);
-  {
-    // Round 4: 1x1 convolutions on plane-stored operands (the bottleneck branches of the backbone, the FPN laterals; forward and
-    // stride-1 data gradient) -> the persistent LDS-DMA GEMM of conv4.hip.  OPT-IN (PP_CONV4P=1): bit-identical, but 1.05-1.9x
-    // SLOWER than igemm3f per launch and -7 % on the training step (profiles/r04_1x1_persistent_dma_gemm.txt);
-    // PP_CONV4P_NST: stages of its ring (4 = all of the CU's LDS, default; 3); PP_CONV4P_SPLITS forces the reduction split.
-    // (read at every launch: tests compare the two kernels inside one process)
-    const char* const e_on = getenv("PP_CONV4P");
-    const char* const e_nst = getenv("PP_CONV4P_NST");
-    const char* const e_sp = getenv("PP_CONV4P_SPLITS");
-    const bool p_on = e_on && e_on[0] == '1';  // (off by default: measured slower than igemm3f on every backbone shape, see conv4.hip)
-    const int p_nst = e_nst && atoi(e_nst) == 3 ? 3 : 4;
-    const int p_splits = e_sp ? atoi(e_sp) : 0;
-    const long long a_bytes = p.src_rows * (long long)p.ld_src * 4, w_bytes = (long long)p.w_taps * w_rows * w_ld8 * 16;
-    if (p_on && p.kh == 1 && p.kw == 1 && ahi && !chi && !flags && !p.sc_on && p.div == 1 && p.Cred % 32 == 0 && p.ld_src % 8 == 0 &&
-        a_bytes < (1ll << 31) && w_bytes < (1ll << 31) && p.src_rows > 0 && (ohi || p.out)) {
-      const int n_cu = ctx->n_cu > 0 ? ctx->n_cu : 256;
-      const long long tiles = (long long)((p.M + 127) / 128) * ((p.Nout + 127) / 128);
-      int sp = 1;
-      if (tiles * 4 < (long long)n_cu * 3 && ctx->ws != nullptr) {  // under three quarters of a round: split the reduction to fill the chip
-        sp = (int)(n_cu / tiles);
-        while (sp > 1 && (n_steps / sp < 4 || (long long)sp * p.M * p.ld_out * 4 > (long long)ctx->ws_bytes)) --sp;
-      }
-      if (p_splits >= 1 && (p_splits == 1 || (ctx->ws != nullptr && n_steps / p_splits >= 1 && (long long)p_splits * p.M * p.ld_out * 4 <= (long long)ctx->ws_bytes)))
-        sp = p_splits;
-      if (getenv("PP_CONV_DEBUG"))
-        fprintf(stderr, "igemm4p M %d N %d steps %d -> %lld tiles x %d splits on %d CUs, %d stages\n", p.M, p.Nout, n_steps, tiles, sp, n_cu, p_nst);
-      PP_API(pp4_launch_igemm4p)(ctx->stream, p, ahi, whi, wlo, w_rows, w_ld8, ohi, olo, sp, sp > 1 ? ctx->ws : nullptr, n_cu, p_nst);
-      if (sp > 1) {
-        const long long total = (long long)p.M * ((p.Nout + 3) >> 2);
-        long long blocks = (total + 255) / 256;
-        if (blocks > (long long)n_cu * 8) blocks = (long long)n_cu * 8;
-        hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, p, sp, ctx->ws, p.bias, p.addend, p.mask_src, p.out,
-                           ohi, olo);
-      }
-      return;
-    }
-  }
-  const bool may_split = ctx->ws != nullptr && (ohi || p.out != nullptr) && !p.sc_on && igemm3_fast_ok(p, ahi != nullptr, w_rows, w_ld8);
-  pick_tile3(ctx, p.M, p.Nout, p.ld_out, n_steps, may_split, igemm3x_ok(p, ahi != nullptr, ohi != nullptr, w_rows, w_ld8), &tm, &tn, &splits);
-  if (getenv("PP_CONV_DEBUG"))
-    fprintf(stderr, "igemm3 M %d N %d steps %d -> tile %dx%d splits %d (may_split %d: ws %d planes_out %d out %d)\n", p.M, p.Nout, n_steps, 64 * tm,
-            64 * tn, splits, (int)may_split, (int)(ctx->ws != nullptr), (int)(ohi != nullptr), (int)(p.out != nullptr));
-  float* ws = splits > 1 ? ctx->ws : nullptr;
-  if (tm == 4) launch_igemm3<4, 2>(ctx->stream, p, ahi, alo, whi, wlo, w_rows, w_ld8, ohi, olo, splits, ws, chi, clo, flags);
-  else if (tm == 2 && tn == 2)
-    launch_igemm3<2, 2>(ctx->stream, p, ahi, alo, whi, wlo, w_rows, w_ld8, ohi, olo, splits, ws, chi, clo, flags, ctx->ws, (size_t)ctx->ws_bytes,
-                        ctx->n_cu > 0 ? ctx->n_cu : 256);
-  else if (tm == 1 && tn == 2) launch_igemm3<1, 2>(ctx->stream, p, ahi, alo, whi, wlo, w_rows, w_ld8, ohi, olo, splits, ws, chi, clo, flags);
-  else if (tm == 2 && tn == 1) launch_igemm3<2, 1>(ctx->stream, p, ahi, alo, whi, wlo, w_rows, w_ld8, ohi, olo, splits, ws, chi, clo, flags);
-  else launch_igemm3<1, 1>(ctx->stream, p, ahi, alo, whi, wlo, w_rows, w_ld8, ohi, olo, splits, ws, chi, clo, flags);
-  if (splits > 1) {
-    const long long total = (long long)p.M * ((p.Nout + 3) >> 2);
-    long long blocks = (total + 255) / 256;
-    const long long cap = (long long)(ctx->n_cu > 0 ? ctx->n_cu : 256) * 8;
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(splitk_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, p, splits, ctx->ws, p.bias, p.addend, p.mask_src,
-                       p.out, ohi, olo);
-  }
+// the launch over the listed 32-row blocks (tm: 2 = 128 x 128 tiles, 1 = 64 x 128)
+static void dispatch3_rowlist(pp_ctx* ctx, IgemmParams& p, const Igemm3Args& a, int tm, const unsigned char* dy_flags, unsigned char* out_flags,
+                              int* out_list, bool fill) {
+  PpIgemmFacts f = igemm3_facts(ctx, p, a);
+  f.listed = true;
+  f.listed_tm = tm;
+  const PpIgemmPlan pl = pp_plan_igemm(f);
+  if (tm == 2) launch_igemm3_rowlist<2, 2>(ctx->stream, p, a, pl, dy_flags, out_flags, out_list, fill);
+  else launch_igemm3_rowlist<1, 2>(ctx->stream, p, a, pl, dy_flags, out_flags, out_list, fill);
 }
+
 
 }  // namespace
 extern "C" int PP_API(pp_conv2d_nhwc_fwd_bf16x3)(pp_ctx* ctx, const pp_conv_desc* d, const float* x, const void* x_hi, const void* x_lo,
@@ -1732,31 +1543,23 @@ extern "C" int PP_API(pp_conv2d_nhwc_fwd_bf16x3)(pp_ctx* ctx, const pp_conv_desc
   memset(&p, 0, sizeof(p));
   p.src = x; p.out = y; p.bias = bias; p.addend = residual; p.mask_src = nullptr;
   p.add_hi = ep_ah; p.add_lo = ep_al;
-  p.ld_src = d->ld_x; p.ld_w = d->ld_w; p.ld_out = d->ld_y; p.ld_add = ld_res; p.ld_mask = 0;
+  igemm_geometry_fwd(ctx, d, p);
+  p.ld_add = ld_res; p.ld_mask = 0;
   p.relu = relu;
-  p.n_seg = d->in.n_seg;
-  fill_segs(ctx, d, true, p.seg, &p.M, &p.src_rows);
-  p.Cred = d->cin; p.Nout = d->cout; p.w_tap_rows = d->cin;
-  p.kh = d->kh; p.kw = d->kw;
-  p.mul = d->stride; p.tsign = 1; p.off_y = -d->pad_t; p.off_x = -d->pad_l; p.div = 1;
-  p.w_ty0 = 0; p.w_tx0 = 0; p.w_tstep = 1; p.w_kw = d->kw; p.w_taps = d->kh * d->kw;
   PP_CHECK_ARG(ctx, (y_hi == nullptr) == (y_lo == nullptr) && (!y_hi || (d->ld_y % 4 == 0 && pp_is_aligned16(y_hi) && pp_is_aligned16(y_lo))),
                PP_ERR_ARG, "pp_conv2d_nhwc_fwd_bf16x3: output planes");
+  const Igemm3Args a = {x_hi, x_lo, w_hi, w_lo, d->cout, d->cin / 8, y_hi, y_lo, chi, clo, nullptr, ctx->ws};
   if (opts->out_flags) {
     // only the flagged 32-row output blocks (the listed-block launch of the sparse data gradient, without dilation and fill):
     // plane-stored input, 3x3 stride 1 pad 1 on an unchanged grid, no residual
-    bool ok = x_hi != nullptr && ((y != nullptr) != (y_hi != nullptr)) && !chi && !residual && !ep_ah && d->stride == 1 && d->kh == 3 && d->kw == 3 && d->pad_t == 1 &&
-              d->pad_l == 1 && igemm3_fast_ok(p, true, d->cout, d->cin / 8);
-    for (int i = 0; i < p.n_seg && ok; ++i)
-      ok = p.seg[i].OH == p.seg[i].SH && p.seg[i].OW == p.seg[i].SW && p.seg[i].row_begin == p.seg[i].src_row_begin;
+    const bool ok = fwd_listed_ok(d, igemm3_facts(ctx, p, a), residual != nullptr || ep_ah != nullptr);
     PP_CHECK_ARG(ctx, ok, PP_ERR_SHAPE, "pp_conv2d_nhwc_fwd_bf16x3: out_flags needs a 3x3 stride-1 'same' conv on plane-stored input");
-    launch_igemm3_rowlist<2, 2>(ctx->stream, p, x_hi, x_lo, w_hi, w_lo, d->cout, d->cin / 8, y_hi, y_lo, nullptr,
-                                const_cast<unsigned char*>(opts->out_flags) /* (only read: no dilation without dy_flags) */, opts->out_list, ctx->ws,
-                                ctx->ws_bytes, false);
+    dispatch3_rowlist(ctx, p, a, 2, nullptr, const_cast<unsigned char*>(opts->out_flags) /* (only read: no dilation without dy_flags) */,
+                      opts->out_list, false);
     PP_CHECK_LAUNCH(ctx, "pp_conv2d_nhwc_fwd_bf16x3");
     return PP_OK;
   }
-  dispatch3(ctx, p, x_hi, x_lo, w_hi, w_lo, d->cout, d->cin / 8, y_hi, y_lo, chi, clo);
+  dispatch3(ctx, p, a);
   PP_CHECK_LAUNCH(ctx, "pp_conv2d_nhwc_fwd_bf16x3");
   return PP_OK;
 }
@@ -1774,8 +1577,7 @@ extern "C" int PP_API(pp_row_block_dilate)(pp_ctx* ctx, const pp_conv_desc* d, c
   memset(&p, 0, sizeof(p));
   p.n_seg = d->in.n_seg;
   fill_segs(ctx, d, true, p.seg, &p.M, &p.src_rows);
-  bool same = d->stride == 1 && d->kh == 3 && d->kw == 3;
-  for (int i = 0; i < p.n_seg && same; ++i) same = p.seg[i].OH == p.seg[i].SH && p.seg[i].OW == p.seg[i].SW && p.seg[i].row_begin == p.seg[i].src_row_begin;
+  const bool same = d->stride == 1 && d->kh == 3 && d->kw == 3 && segs_same_grid(p.seg, p.n_seg);
   PP_CHECK_ARG(ctx, same, PP_ERR_SHAPE, "pp_row_block_dilate: 3x3 stride-1 conv on an unchanged grid");
   const int nb = (p.M + 31) / 32;
   hipLaunchKernelGGL(rl_dilate_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, p, in_flags, out_flags, nb);
@@ -1813,8 +1615,9 @@ extern "C" int PP_API(pp_stem7x7s2_fwd_bf16x3)(pp_ctx* ctx, int n_img, int H, in
   p.kh = 7; p.kw = 1;
   p.mul = 2; p.tsign = 1; p.off_y = 0; p.off_x = 0; p.div = 1;
   p.w_ty0 = 0; p.w_tx0 = 0; p.w_tstep = 1; p.w_kw = 1; p.w_taps = 7;
-  PP_CHECK_ARG(ctx, igemm3_fast_ok(p, false, cout, 4), PP_ERR_SHAPE, "pp_stem7x7s2_fwd_bf16x3: frame too large for 31-bit offsets");
-  dispatch3(ctx, p, nullptr, nullptr, w_hi, w_lo, cout, 4, nullptr, nullptr);
+  const Igemm3Args a = {nullptr, nullptr, w_hi, w_lo, cout, 4, nullptr, nullptr, nullptr, nullptr, nullptr, ctx->ws};
+  PP_CHECK_ARG(ctx, pp_igemm_fast_ok(igemm3_facts(ctx, p, a)), PP_ERR_SHAPE, "pp_stem7x7s2_fwd_bf16x3: frame too large for 31-bit offsets");
+  dispatch3(ctx, p, a);
   PP_CHECK_LAUNCH(ctx, "pp_stem7x7s2_fwd_bf16x3");
   return PP_OK;
 }
@@ -1858,93 +1661,34 @@ extern "C" int PP_API(pp_conv2d_nhwc_bwd_data_bf16x3)(pp_ctx* ctx, const pp_conv
   memset(&p, 0, sizeof(p));
   p.src = dy; p.out = dx; p.bias = nullptr; p.addend = addend; p.mask_src = relu_src;
   p.add_hi = ep_ah; p.add_lo = ep_al; p.mask_hi = ep_mh;
-  p.ld_src = d->ld_y; p.ld_w = d->ld_w; p.ld_out = d->ld_x; p.ld_add = ld_add; p.ld_mask = ld_rs;
+  igemm_geometry_bwd_data(ctx, d, p);
+  p.ld_add = ld_add; p.ld_mask = ld_rs;
   p.relu = 0;
-  p.n_seg = d->in.n_seg;
-  fill_segs(ctx, d, false, p.seg, &p.M, &p.src_rows);
-  p.Cred = cred; p.Nout = d->cin; p.w_tap_rows = d->cin;
-  p.kh = d->kh; p.kw = d->kw;
-  p.mul = 1; p.tsign = -1; p.off_y = d->pad_t; p.off_x = d->pad_l; p.div = d->stride;
-  p.w_ty0 = 0; p.w_tx0 = 0; p.w_tstep = 1; p.w_kw = d->kw; p.w_taps = d->kh * d->kw;
   PP_CHECK_ARG(ctx, (dx_hi == nullptr) == (dx_lo == nullptr) && (!dx_hi || (d->ld_x % 4 == 0 && pp_is_aligned16(dx_hi) && pp_is_aligned16(dx_lo))),
                PP_ERR_ARG, "pp_conv2d_nhwc_bwd_data_bf16x3: output planes");
-  static const bool s2_classes = []() { const char* e = getenv("PP_CONV3_S2CLASSES"); return !(e && e[0] == '0'); }();
-  const bool all_f32 = dy && dx && !dy_hi && !dx_hi, all_planes = dy_hi && dx_hi && !dx;  // (the parity-class / row-list kernels exist for these two)
-  // Row-block skip: does the launch over the LISTED blocks (launch_igemm3_rowlist below) apply?  PP_SPARSE_DGRAD: 22 (default)
-  // / 12 = tile of that launch (equal within noise on the bench step), 0 = keep the dense grid and skip the k-loop of tiles
-  // that see no flagged block (coarser: a 126-row tile spans 1.6 image rows)
-  static const int rl_mode = []() { const char* e = getenv("PP_SPARSE_DGRAD"); return e ? atoi(e) : 22; }();
-  bool rl_ok = skip_flags && skip_scratch_ok && rl_mode && (all_f32 || all_planes) && !chi && d->stride == 1 && d->kh == 3 && d->kw == 3 &&
-               d->pad_t == 1 && d->pad_l == 1 && p.bias == nullptr && igemm3_fast_ok(p, all_planes, d->cin, cred / 8);
-  for (int i = 0; i < p.n_seg && rl_ok; ++i)
-    rl_ok = p.seg[i].OH == p.seg[i].SH && p.seg[i].OW == p.seg[i].SW && p.seg[i].row_begin == p.seg[i].src_row_begin;
+  const Igemm3Args a = {dy_hi, dy_lo, w_hi, w_lo, d->cin, cred / 8, dx_hi, dx_lo, chi, clo, skip_flags, ctx->ws};
+  DgradRoute route;
+  dgrad_route(d, p, igemm3_facts(ctx, p, a), skip_scratch_ok, &route);
   // Contract of the hint's scratch (pp_row_block_list_planes_within relies on it): after this call the second n_blocks bytes
   // of the flags buffer flag every 32-row block of dx that may hold a non-zero -- the dilated list when the listed launch
   // runs, everything otherwise.
-  PP_CHECK_ARG(ctx, !opts->lazy_in || rl_ok, PP_ERR_ARG,
+  PP_CHECK_ARG(ctx, !opts->lazy_in || route.listed, PP_ERR_ARG,
                "pp_conv2d_nhwc_bwd_data_bf16x3: dy was declared lazy (unwritten outside its flagged blocks) but the listed-block launch "
                "does not apply to this call");
-  if (skip_scratch_ok && !rl_ok)
-    PP_HIP(ctx, hipMemsetAsync(skip_flags + (p.M + 31) / 32, 1, (size_t)((p.M + 31) / 32), ctx->stream));
-  if (d->stride == 2 && s2_classes && (all_f32 || all_planes) && d->in.n_seg == 1) {
-    // Stride-2 bwd-data as four stride-1 launches, one per parity class (cy, cx) of the input grid: input cell
-    // (2y'+cy, 2x'+cx) only receives the taps ty = ty0 + 2i with ty0 = (cy + pad_t) & 1 (x alike), from output cell
-    // y' + (cy + pad_t - ty0)/2 - i.  The single-launch form spends 3/4 of its MFMAs on taps that the divisibility
-    // mask zeroes; here every MFMA is useful and classes without taps (1x1 kernels) only run the epilogue.
-    IgemmParams q = p;
-    q.div = 1;
-    const int H = d->in.h[0], W = d->in.w[0];
-    bool ok = true;
-    IgemmParams cls[4];
-    for (int c = 0; c < 4 && ok; ++c) {
-      const int cy = c >> 1, cx = c & 1;
-      IgemmParams& r = cls[c];
-      r = q;
-      const int ty0 = (cy + d->pad_t) & 1, tx0 = (cx + d->pad_l) & 1;
-      r.kh = ty0 < d->kh ? (d->kh - ty0 + 1) / 2 : 0;
-      r.kw = tx0 < d->kw ? (d->kw - tx0 + 1) / 2 : 0;
-      r.off_y = (cy + d->pad_t - ty0) / 2;
-      r.off_x = (cx + d->pad_l - tx0) / 2;
-      r.w_ty0 = ty0; r.w_tx0 = tx0; r.w_tstep = 2; r.w_kw = d->kw;
-      if (r.kh == 0 || r.kw == 0) r.kh = r.kw = 0;  // no taps: class_fill_kernel below
-      r.seg[0].OH = (H - cy + 1) / 2;
-      r.seg[0].OW = (W - cx + 1) / 2;
-      r.M = d->in.n_img * r.seg[0].OH * r.seg[0].OW;
-      r.sc_on = 1; r.sc_H = H; r.sc_W = W; r.sc_cy = cy; r.sc_cx = cx;
-      if (r.M > 0 && r.kh > 0 && !(igemm3_fast_ok(r, all_planes, d->cin, cred / 8) && r.M < (1 << 24))) ok = false;
-    }
-    if (ok) {
-      if (chi) split_capture_pass(ctx->stream, p, chi, clo);
-      for (int c = 0; c < 4; ++c) {
-        if (cls[c].M <= 0) continue;
-        if (cls[c].kh > 0) {
-          dispatch3(ctx, cls[c], dy_hi, dy_lo, w_hi, w_lo, d->cin, cred / 8, dx_hi, dx_lo);
-        } else {
-          const long long total = (long long)cls[c].M * ((cls[c].Nout + 3) >> 2);
-          long long blocks = (total + 255) / 256;
-          const long long cap = (long long)(ctx->n_cu > 0 ? ctx->n_cu : 256) * 8;
-          if (blocks > cap) blocks = cap;
-          hipLaunchKernelGGL(class_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, cls[c], addend, relu_src, dx, dx_hi, dx_lo);
-        }
-      }
-      PP_CHECK_LAUNCH(ctx, "pp_conv2d_nhwc_bwd_data_bf16x3");
-      return PP_OK;
-    }
-  }
-  if (rl_ok) {
-    const int nb = (p.M + 31) / 32;
-    unsigned char* out_flags = skip_flags + nb;
-    int* out_list = opts->skip_list + nb + 1;
-    if (rl_mode == 22)
-      launch_igemm3_rowlist<2, 2>(ctx->stream, p, dy_hi, dy_lo, w_hi, w_lo, d->cin, cred / 8, dx_hi, dx_lo, skip_flags, out_flags, out_list, ctx->ws,
-                                  ctx->ws_bytes, !opts->lazy_out);
-    else
-      launch_igemm3_rowlist<1, 2>(ctx->stream, p, dy_hi, dy_lo, w_hi, w_lo, d->cin, cred / 8, dx_hi, dx_lo, skip_flags, out_flags, out_list, ctx->ws,
-                                  ctx->ws_bytes, !opts->lazy_out);
-    PP_CHECK_LAUNCH(ctx, "pp_conv2d_nhwc_bwd_data_bf16x3");
-    return PP_OK;
-  }
-  dispatch3(ctx, p, dy_hi, dy_lo, w_hi, w_lo, d->cin, cred / 8, dx_hi, dx_lo, chi, clo, skip_flags);
+  const int nb = (p.M + 31) / 32;
+  if (skip_scratch_ok && !route.listed) PP_HIP(ctx, hipMemsetAsync(skip_flags + nb, 1, (size_t)nb, ctx->stream));
+  const Igemm3Args ac = {dy_hi, dy_lo, w_hi, w_lo, d->cin, cred / 8, dx_hi, dx_lo, nullptr, nullptr, nullptr, ctx->ws};
+  if (route.classes && chi) split_capture_pass(ctx->stream, p, chi, clo);
+  dgrad_launches(
+      route, p,
+      [&](IgemmParams& q, bool is_class, bool listed) {
+        if (listed) dispatch3_rowlist(ctx, q, a, route.listed_tm, skip_flags, skip_flags + nb, opts->skip_list + nb + 1, !opts->lazy_out);
+        else dispatch3(ctx, q, is_class ? ac : a);
+      },
+      [&](IgemmParams& q) {
+        hipLaunchKernelGGL(class_fill_kernel, dim3(pp_finish_blocks(q.M, q.Nout, pp_cus(ctx->n_cu))), dim3(256), 0, ctx->stream, q, addend, relu_src,
+                           dx, dx_hi, dx_lo);
+      });
   PP_CHECK_LAUNCH(ctx, "pp_conv2d_nhwc_bwd_data_bf16x3");
   return PP_OK;
 }
@@ -2488,96 +2232,40 @@ __global__ void wgrad_finish_kernel(long long n4_dw, int ld4, int splits, long l
   }
 }
 
+// the launches of one weight-gradient plan (conv_plan.h: pp_plan_wgrad) on its tile
 template <int TM, int TN>
-static bool launch_wgrad3(pp_ctx* ctx, Wgrad3Params& p, const float* x, const float* dy, const void* xhi, const void* xlo, const void* dhi,
-                          const void* dlo, float* dw, float* dbias, const int* list = nullptr, bool lazy_in = false) {
-  constexpr int BM = 64 * TM, BN = 64 * TN;
-  p.k_tiles_per_tap = p.Cin / BM;
-  p.n_tiles_k = p.kh * p.kw * p.k_tiles_per_tap;
-  p.n_tiles_n = (p.Cout + BN - 1) / BN;
-  const int tiles = p.n_tiles_k * p.n_tiles_n;
-  const int cus = ctx->n_cu > 0 ? ctx->n_cu : 256;
-  int max_splits = (p.M + 511) / 512;  // at least 16 reduction steps of 32 rows per workgroup
-  if (max_splits < 1) max_splits = 1;
-  if (max_splits > 64) max_splits = 64;
-  static const bool fast_on = []() { const char* e = getenv("PP_CONV3_FAST"); return !(e && e[0] == '0'); }();
-  const long long x_bytes = p.src_rows * (long long)p.ld_src * 4, d_bytes = (long long)p.M * p.ld_dy * 4;  // f32 or packed planes
-  int min_ow = 1 << 30, min_hw = 1 << 30;
-  for (int i = 0; i < p.n_seg; ++i) {
-    min_ow = p.seg[i].OW < min_ow ? p.seg[i].OW : min_ow;
-    min_hw = p.seg[i].OH * p.seg[i].OW < min_hw ? p.seg[i].OH * p.seg[i].OW : min_hw;
+static void launch_wgrad3(hipStream_t st, const Wgrad3Params& p, const PpWgradPlan& pl, const float* x, const float* dy, const void* xhi,
+                          const void* xlo, const void* dhi, const void* dlo, float* dw, float* dbias, const int* list, float* ctx_ws) {
+  const dim3 grid(pl.grid), wg(256);
+  const unsigned x_bytes = (unsigned)(p.src_rows * (long long)p.ld_src * 4), d_bytes = (unsigned)((long long)p.M * p.ld_dy * 4);  // f32 or packed planes
+  float* const ws = pl.finish_blocks ? ctx_ws : nullptr;  // (a single split adds its tile straight into dW)
+  switch (pl.family) {
+    case PP_WGRAD3F_PLANES_LIST:
+      hipLaunchKernelGGL((wgrad3f_kernel<TM, TN, true, true>), grid, wg, 0, st, p, xhi, xlo, x_bytes, dhi, dlo, d_bytes, dw, dbias, list, ws, pl.ws_slice);
+      break;
+    case PP_WGRAD3F_PLANES:
+      hipLaunchKernelGGL((wgrad3f_kernel<TM, TN, true, false>), grid, wg, 0, st, p, xhi, xlo, x_bytes, dhi, dlo, d_bytes, dw, dbias, (const int*)nullptr,
+                         ws, pl.ws_slice);
+      break;
+    case PP_WGRAD3F_F32_LIST:
+      hipLaunchKernelGGL((wgrad3f_kernel<TM, TN, false, true>), grid, wg, 0, st, p, (const void*)x, nullptr, x_bytes, (const void*)dy, nullptr, d_bytes,
+                         dw, dbias, list, ws, pl.ws_slice);
+      break;
+    case PP_WGRAD3F_F32:
+      hipLaunchKernelGGL((wgrad3f_kernel<TM, TN, false, false>), grid, wg, 0, st, p, (const void*)x, nullptr, x_bytes, (const void*)dy, nullptr, d_bytes,
+                         dw, dbias, (const int*)nullptr, ws, pl.ws_slice);
+      break;
+    default:  // PP_WGRAD3
+      if (xhi)
+        hipLaunchKernelGGL((wgrad3_kernel<TM, TN, true>), grid, wg, 0, st, p, x, dy, (const uint4*)xhi, (const uint4*)xlo, (const uint4*)dhi,
+                           (const uint4*)dlo, dw, dbias);
+      else
+        hipLaunchKernelGGL((wgrad3_kernel<TM, TN, false>), grid, wg, 0, st, p, x, dy, (const uint4*)nullptr, (const uint4*)nullptr,
+                           (const uint4*)nullptr, (const uint4*)nullptr, dw, dbias);
   }
-  p.max_wraps = (32 + min_ow - 1) / min_ow;
-  const bool fast = fast_on && x_bytes < (1ll << 31) && d_bytes < (1ll << 31) && p.M < (1 << 24) && p.src_rows > 0 && min_hw >= 32;
-  if (lazy_in && !(fast && list)) return false;  // (only the listed-block reduction never looks at the other rows of dy)
-  const int slots = fast ? ((TM * TN == 4) ? 3 : 4) : ((TM * TN == 4) ? 2 : 3);
-  const double tile_work = (double)(TM * TN) / 4.0;
-  // one slice = a full-size copy of dW plus a bias row (f32).  PP_WGRAD3_DETERMINISTIC=1 (and a scratch buffer): the splits write
-  // slices and a finishing pass adds them in a fixed order -- bit-reproducible gradients; default: float atomics into dW, which
-  // are fire-and-forget and overlap the k-loops of other workgroups (measured in the training step, same box, slices vs
-  // atomics: 531.5 vs 537.1 images/s, dense backward 424 vs 433: the extra pass and its launch cost more than the atomics)
-  const long long ws_slice = (long long)p.kh * p.kw * p.Cin * p.ld_w + p.ld_w;
-  const bool use_ws = fast && ctx->ws != nullptr && (long long)ctx->ws_bytes >= ws_slice * 4 && ((uintptr_t)dw & 15u) == 0 &&
-                      (!dbias || ((uintptr_t)dbias & 15u) == 0) && []() { const char* e = getenv("PP_WGRAD3_DETERMINISTIC"); return e && e[0] == '1'; }();
-  if (use_ws) {
-    const long long fit = (long long)ctx->ws_bytes / (ws_slice * 4);
-    if (max_splits > fit) max_splits = (int)fit;
-  }
-  // per split: atomics = |dW| at ~1.3 TB/s, half of it hidden under the k-loops of other workgroups (measured: 256-channel
-  // head convs 252 -> 234 us going from 14 to 21 splits); slices = |dW| written and read back once at ~4 TB/s
-  const double atomic_us_per_split = use_ws ? (double)tiles * BM * BN * 4.0 * 2.0 / 4.0e6 : 0.5 * (double)tiles * BM * BN * 4.0 / 1.3e6;
-  int splits = 1;
-  double best = 1e300;
-  for (int sp = 1; sp <= max_splits; ++sp) {
-    const double steps = (double)((p.M + sp - 1) / sp + 31) / 32.0;
-    const double cost = est_rounds((long long)tiles * sp, slots, cus) * steps * tile_work * 0.8 + atomic_us_per_split * sp;
-    if (cost < best * 0.995) {
-      best = cost;
-      splits = sp;
-    }
-  }
-  if (const char* e = getenv("PP_WGRAD3_SPLITS")) {  // tuning hook
-    const int v = atoi(e);
-    if (v >= 1 && v <= max_splits) splits = v;
-  }
-  if (getenv("PP_CONV_DEBUG")) fprintf(stderr, "wgrad3 tile %dx%d tiles %d splits %d (M %d) fast %d\n", BM, BN, tiles, splits, p.M, (int)fast);
-  int rps = (p.M + splits - 1) / splits;
-  rps = (rps + 31) / 32 * 32;
-  splits = (p.M + rps - 1) / rps;
-  p.splits = splits;
-  p.rows_per_split = rps;
-  {
-    static const int sp_steps = []() { const char* e = getenv("PP_WGRAD3_SP_STEPS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 1; }();
-    p.sp_min_steps = sp_steps;
-  }
-  float* const ws = (use_ws && splits > 1) ? ctx->ws : nullptr;  // (a single split adds its tile straight into dW)
-  if (fast) {
-    if (xhi && list)
-      hipLaunchKernelGGL((wgrad3f_kernel<TM, TN, true, true>), dim3((unsigned)(tiles * splits)), dim3(256), 0, ctx->stream, p, xhi, xlo,
-                         (unsigned)x_bytes, dhi, dlo, (unsigned)d_bytes, dw, dbias, list, ws, ws_slice);
-    else if (xhi)
-      hipLaunchKernelGGL((wgrad3f_kernel<TM, TN, true, false>), dim3((unsigned)(tiles * splits)), dim3(256), 0, ctx->stream, p, xhi, xlo,
-                         (unsigned)x_bytes, dhi, dlo, (unsigned)d_bytes, dw, dbias, (const int*)nullptr, ws, ws_slice);
-    else if (list)
-      hipLaunchKernelGGL((wgrad3f_kernel<TM, TN, false, true>), dim3((unsigned)(tiles * splits)), dim3(256), 0, ctx->stream, p, (const void*)x,
-                         nullptr, (unsigned)x_bytes, (const void*)dy, nullptr, (unsigned)d_bytes, dw, dbias, list, ws, ws_slice);
-    else
-      hipLaunchKernelGGL((wgrad3f_kernel<TM, TN, false, false>), dim3((unsigned)(tiles * splits)), dim3(256), 0, ctx->stream, p, (const void*)x,
-                         nullptr, (unsigned)x_bytes, (const void*)dy, nullptr, (unsigned)d_bytes, dw, dbias, (const int*)nullptr, ws, ws_slice);
-    if (ws) {
-      const long long n4 = (ws_slice - p.ld_w) / 4;
-      long long blocks = (n4 + p.ld_w / 4 + 255) / 256;
-      if (blocks > (long long)cus * 8) blocks = (long long)cus * 8;
-      hipLaunchKernelGGL(wgrad_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, n4, p.ld_w / 4, splits, ws_slice / 4,
-                         (const float4*)ws, (float4*)dw, (float4*)dbias);
-    }
-  } else if (xhi)
-    hipLaunchKernelGGL((wgrad3_kernel<TM, TN, true>), dim3((unsigned)(tiles * splits)), dim3(256), 0, ctx->stream, p, x, dy, (const uint4*)xhi,
-                       (const uint4*)xlo, (const uint4*)dhi, (const uint4*)dlo, dw, dbias);
-  else
-    hipLaunchKernelGGL((wgrad3_kernel<TM, TN, false>), dim3((unsigned)(tiles * splits)), dim3(256), 0, ctx->stream, p, x, dy,
-                       (const uint4*)nullptr, (const uint4*)nullptr, (const uint4*)nullptr, (const uint4*)nullptr, dw, dbias);
-  return true;
+  if (ws)
+    hipLaunchKernelGGL(wgrad_finish_kernel, dim3(pl.finish_blocks), wg, 0, st, (pl.ws_slice - p.ld_w) / 4, p.ld_w / 4, pl.splits, pl.ws_slice / 4,
+                       (const float4*)ws, (float4*)dw, (float4*)dbias);
 }
 
 }  // namespace
@@ -2603,61 +2291,24 @@ extern "C" int PP_API(pp_conv2d_nhwc_bwd_weight_bf16x3)(pp_ctx* ctx, const pp_co
                "pp_conv2d_nhwc_bwd_weight_bf16x3: tensors must be 16-byte aligned");
   Wgrad3Params p;
   memset(&p, 0, sizeof(p));
-  p.ld_src = d->ld_x; p.ld_dy = d->ld_y; p.ld_w = d->ld_w;
-  p.n_seg = d->in.n_seg;
-  fill_segs(ctx, d, true, p.seg, &p.M, &p.src_rows);
+  wgrad_geometry(ctx, d, p);
   p.inv_scale = (planes && ctx->grad_scale) ? ctx->grad_scale + 1 : nullptr;  // (f32 operands are never scaled)
-  p.Cin = d->cin; p.Cout = d->cout;
-  p.kh = d->kh; p.kw = d->kw; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l;
-  // (tools/sweep_wgrad.sh: the small 1x1 layers of res4 / res5 take ~35 us for ANY tile / split choice: ~19 latency-bound
-  // steps of a lone workgroup per CU plus the f32 atomics of splits x |dW|.  Register double-buffering of the staged tiles
-  // (loads two steps ahead) shortens such lone-workgroup launches by 10-20 % in isolation, but no measurable step time.)
-  {
-    // Round 4: 3x3 stride-1 "same" layers on plane-stored operands -> the tap-row-reuse kernels of conv4.hip (one staged tile pair per
-    // kernel ROW, 192 accumulators).  PP_WGRAD3R (read per launch: tests compare the kernels in one process):
-    //   unset  wgrad3w (producer + consumer waves) for the DENSE reductions of the P16 launches with 512 input or output channels --
-    //          the 3D-box head: 5-19 % faster per launch, +2.8 % on the dense-backward step; the 256-wide launches gain 5-13 % in
-    //          isolation and LOSE 1 % in the step (a workgroup of 8 waves x 256 registers owns its CU: nothing of the data-gradient
-    //          lane runs beside it), the bf16-pair launches of the backbone lose outright (profiles/r04_wgrad_producer_consumer_waves.txt);
-    //          PP_WGRAD3W_MIN moves the channel threshold
-    //   0      wgrad3f everywhere
-    //   1      wgrad3r (one wave per SIMD; dense launches 1.15-1.45x SLOWER than wgrad3f: profiles/r04_wgrad_tap_row_reuse.txt)
-    //   2      wgrad3w wherever its conditions hold
-    // The deterministic slices mode keeps wgrad3f.
-    const char* const e_r = getenv("PP_WGRAD3R");
-    const char* const e_det = getenv("PP_WGRAD3_DETERMINISTIC");  // (read per launch, like the slices path itself)
-    const bool det = e_det && e_det[0] == '1';
-    static const int w_min = []() { const char* e = getenv("PP_WGRAD3W_MIN"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 512; }();
-    int variant = 0;
-    if (e_r && (e_r[0] == '1' || e_r[0] == '2')) variant = e_r[0] - '0';
-    else if (!e_r && PP_FMT == 1 && !skip_list && (d->cin >= w_min || d->cout >= w_min)) variant = 2;
-    if (variant && planes && !(det && ctx->ws != nullptr) && (!lazy_in || skip_list)) {
-      static const int sp_steps = []() { const char* e = getenv("PP_WGRAD3_SP_STEPS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 1; }();
-      p.sp_min_steps = sp_steps;
-      if (PP_API(pp4_launch_wgrad3r)(ctx->stream, p, x_hi, x_lo, dy_hi, dy_lo, dw, dbias, skip_list, ctx->n_cu > 0 ? ctx->n_cu : 256, variant)) {
-        PP_CHECK_LAUNCH(ctx, "pp_conv2d_nhwc_bwd_weight_bf16x3");
-        return PP_OK;
-      }
-    }
-  }
-  bool big_k = (d->cin % 128 == 0);
-  bool big_n = ((d->cout + 127) / 128 * 128) <= ((d->cout + 63) / 64 * 64);
-  if (const char* e = getenv("PP_WGRAD3_TILE")) {  // tuning hook: "1,1" / "1,2" / "2,1" / "2,2"
-    if (e[0] && e[1] == ',' && e[2]) {
-      big_k = big_k && e[0] == '2';
-      big_n = e[2] == '2';
-    }
-  }
-  bool launched;
-  if (big_k && big_n) launched = launch_wgrad3<2, 2>(ctx, p, x, dy, planes ? x_hi : nullptr, x_lo, dy_hi, dy_lo, dw, dbias, skip_list, lazy_in);
-  else if (big_k) launched = launch_wgrad3<2, 1>(ctx, p, x, dy, planes ? x_hi : nullptr, x_lo, dy_hi, dy_lo, dw, dbias, skip_list, lazy_in);
-  else if (big_n) launched = launch_wgrad3<1, 2>(ctx, p, x, dy, planes ? x_hi : nullptr, x_lo, dy_hi, dy_lo, dw, dbias, skip_list, lazy_in);
-  else launched = launch_wgrad3<1, 1>(ctx, p, x, dy, planes ? x_hi : nullptr, x_lo, dy_hi, dy_lo, dw, dbias, skip_list, lazy_in);
-  PP_CHECK_ARG(ctx, launched, PP_ERR_ARG,
+  const PpWgradFacts f = wgrad_facts(p, planes, skip_list != nullptr, lazy_in, PP_FMT, ctx->n_cu, ctx->ws != nullptr, (long long)ctx->ws_bytes,
+                                     pp_is_aligned16(dw), pp_is_aligned16(dbias));
+  const PpWgradPlan pl = pp_plan_wgrad(f);
+  PP_CHECK_ARG(ctx, !pl.refused, PP_ERR_ARG,
                "pp_conv2d_nhwc_bwd_weight_bf16x3: dy was declared lazy (unwritten outside its listed blocks) but the listed-block reduction "
                "does not apply to this call");
+  pp_plan_debug(f, pl);
+  p.k_tiles_per_tap = pl.k_tiles_per_tap; p.n_tiles_k = pl.n_tiles_k; p.n_tiles_n = pl.n_tiles_n;
+  p.splits = pl.splits; p.rows_per_split = pl.rows_per_split; p.max_wraps = pl.max_wraps; p.sp_min_steps = pl.sp_min_steps;
+  const void* const xhi = planes ? x_hi : nullptr;
+  if (pl.family == PP_WGRAD3R || pl.family == PP_WGRAD3W)
+    PP_API(pp4_launch_wgrad3r)(ctx->stream, p, pl.grid, pl.family == PP_WGRAD3W, x_hi, x_lo, dy_hi, dy_lo, dw, dbias, skip_list);
+  else if (pl.tm == 2 && pl.tn == 2) launch_wgrad3<2, 2>(ctx->stream, p, pl, x, dy, xhi, x_lo, dy_hi, dy_lo, dw, dbias, skip_list, ctx->ws);
+  else if (pl.tm == 2) launch_wgrad3<2, 1>(ctx->stream, p, pl, x, dy, xhi, x_lo, dy_hi, dy_lo, dw, dbias, skip_list, ctx->ws);
+  else if (pl.tn == 2) launch_wgrad3<1, 2>(ctx->stream, p, pl, x, dy, xhi, x_lo, dy_hi, dy_lo, dw, dbias, skip_list, ctx->ws);
+  else launch_wgrad3<1, 1>(ctx->stream, p, pl, x, dy, xhi, x_lo, dy_hi, dy_lo, dw, dbias, skip_list, ctx->ws);
   PP_CHECK_LAUNCH(ctx, "pp_conv2d_nhwc_bwd_weight_bf16x3");
   return PP_OK;
 }
-namespace {
-}  // namespace

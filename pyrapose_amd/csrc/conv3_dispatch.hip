@@ -1,6 +1,6 @@
 // Forwards the plane-format-dependent entry points of the conv3.hip family to the build the context asks for
 // (pp_ctx_set_planes_format: 0 = bf16 pairs / bf16x3 arithmetic, 1 = P16 / f16c8 arithmetic; csrc/planes_fmt.h).
-#include "pp_internal.h"
+#include "conv_common.h"
 
 extern "C" int pp_row_block_list_fmt0(pp_ctx* ctx, const float* x, int rows, int ld, int cols, unsigned char* flags, int* list);
 extern "C" int pp_row_block_list_fmt1(pp_ctx* ctx, const float* x, int rows, int ld, int cols, unsigned char* flags, int* list);
@@ -72,4 +72,60 @@ extern "C" int pp_conv2d_nhwc_bwd_data_bf16x3(pp_ctx* ctx, const pp_conv_desc* d
 }
 extern "C" int pp_conv2d_nhwc_bwd_weight_bf16x3(pp_ctx* ctx, const pp_conv_desc* d, const float* x, const float* dy, const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, float* dw, float* dbias, const pp_conv_opts* opts) {
   return (ctx && ctx->planes_fmt == 1) ? pp_conv2d_nhwc_bwd_weight_bf16x3_fmt1(ctx, d, x, dy, x_hi, x_lo, dy_hi, dy_lo, dw, dbias, opts) : pp_conv2d_nhwc_bwd_weight_bf16x3_fmt0(ctx, d, x, dy, x_hi, x_lo, dy_hi, dy_lo, dw, dbias, opts);
+}
+
+// The plan of a call as text, without a context (include/pyrapose_hip.h): the facts come from the same functions the entry points
+// of conv3.hip use, the plans from conv_plan.h.
+extern "C" int pp_conv_plan_text(const pp_conv_desc* d, int pass, unsigned forms, int planes_fmt, int n_cu, size_t ws_bytes, char* buf,
+                                 int buf_bytes) {
+  if (!buf || buf_bytes <= 0 || pass < PP_PLAN_FWD || pass > PP_PLAN_BWD_WEIGHT) return PP_ERR_ARG;
+  const int rc = check_desc(nullptr, d, "pp_conv_plan_text");
+  if (rc) return rc;
+  const bool planes_in = forms & PP_PLAN_PLANES_IN, planes_out = forms & PP_PLAN_PLANES_OUT, f32_out = (forms & PP_PLAN_F32_OUT) || !planes_out,
+             capture = forms & PP_PLAN_CAPTURE, list = forms & PP_PLAN_LIST, lazy_in = forms & PP_PLAN_LAZY_IN;
+  const bool ws = ws_bytes > 0;
+  int at = 0;
+  buf[0] = 0;
+  if (pass == PP_PLAN_BWD_WEIGHT) {
+    if (d->cin % 64 != 0) return PP_ERR_SHAPE;
+    Wgrad3Params p;
+    memset(&p, 0, sizeof(p));
+    wgrad_geometry(nullptr, d, p);
+    const PpWgradFacts f = wgrad_facts(p, planes_in, list, lazy_in, planes_fmt, n_cu, ws, (long long)ws_bytes, true, true);
+    return pp_plan_print(buf, buf_bytes, at, f, pp_plan_wgrad(f), true);
+  }
+  IgemmParams p;
+  memset(&p, 0, sizeof(p));
+  if (pass == PP_PLAN_FWD) {
+    if (d->cin % 32 != 0) return PP_ERR_SHAPE;
+    igemm_geometry_fwd(nullptr, d, p);
+    PpIgemmFacts f = igemm_facts(p, d->cout, d->cin / 8, planes_in, !planes_in, planes_out, f32_out, capture, false, n_cu, ws, (long long)ws_bytes);
+    if (list) {  // pp_conv_opts.out_flags
+      if (!fwd_listed_ok(d, f, false)) return PP_ERR_SHAPE;
+      f.listed = true;
+      f.listed_tm = 2;
+    }
+    return pp_plan_print(buf, buf_bytes, at, f, pp_plan_igemm(f), true);
+  }
+  if (d->cin % 16 != 0) return PP_ERR_SHAPE;
+  igemm_geometry_bwd_data(nullptr, d, p);
+  const int w_rows = d->cin, w_ld8 = p.Cred / 8;
+  const PpIgemmFacts f = igemm_facts(p, w_rows, w_ld8, planes_in, !planes_in, planes_out, f32_out, capture, list, n_cu, ws, (long long)ws_bytes);
+  DgradRoute route;
+  dgrad_route(d, p, f, list, &route);
+  if (lazy_in && !route.listed) return pp_plan_append(buf, buf_bytes, at, "igemm3 refused: lazy dy without a listed-block launch\n");
+  dgrad_launches(
+      route, p,
+      [&](IgemmParams& q, bool is_class, bool listed) {
+        PpIgemmFacts fq = igemm_facts(q, w_rows, w_ld8, planes_in, !planes_in, planes_out, f32_out, capture && !is_class, list && !is_class, n_cu, ws,
+                                      (long long)ws_bytes);
+        fq.listed = listed;
+        fq.listed_tm = route.listed_tm;
+        at = pp_plan_print(buf, buf_bytes, at, fq, pp_plan_igemm(fq), true);
+      },
+      [&](IgemmParams& q) {
+        at = pp_plan_append(buf, buf_bytes, at, "class M %d N %d: no taps class_fill | grid=%u\n", q.M, q.Nout,
+                            pp_finish_blocks(q.M, q.Nout, pp_cus(n_cu)));
+      });
+  return at;
 }

@@ -1132,15 +1132,14 @@ __global__ __launch_bounds__(512, 1) void wgrad3w_kernel(const Wgrad3Params p, c
 }  // namespace
 
 void PP_API(pp4_launch_igemm4p)(hipStream_t st, IgemmParams& p, const void* ahi, const void* whi, const void* wlo, int w_rows, int w_ld8,
-                                void* ohi, void* olo, int splits, float* ws, int n_cu, int nst) {
+                                void* ohi, void* olo, int splits, float* ws, unsigned grid, int nst) {
   p.n_tiles_n = (p.Nout + 127) / 128;
   const int n_items = ((p.M + 127) / 128) * p.n_tiles_n * splits;
-  const int grid = n_items < n_cu ? n_items : n_cu;
   const long long a_bytes = p.src_rows * (long long)p.ld_src * 4;
   const long long w_bytes = (long long)p.w_taps * w_rows * w_ld8 * 16;
   const bool op = ohi != nullptr && splits == 1;
   auto go = [&](auto opc, auto nstc) {
-    hipLaunchKernelGGL((igemm4p_kernel<decltype(opc)::value, decltype(nstc)::value>), dim3((unsigned)grid), dim3(256), 0, st, p, ahi, (unsigned)a_bytes, whi,
+    hipLaunchKernelGGL((igemm4p_kernel<decltype(opc)::value, decltype(nstc)::value>), dim3(grid), dim3(256), 0, st, p, ahi, (unsigned)a_bytes, whi,
                        wlo, (unsigned)w_bytes, p.bias, p.addend, p.mask_src, p.out, (uint2*)(op ? ohi : nullptr), (uint2*)(op ? olo : nullptr), w_rows, w_ld8,
                        splits, ws, n_items, (p.Cred / 32) / splits, (p.Cred / 32) % splits);
   };
@@ -1153,69 +1152,15 @@ void PP_API(pp4_launch_igemm4p)(hipStream_t st, IgemmParams& p, const void* ahi,
   }
 }
 
-// the tap-row-reuse weight gradient (wgrad3r_kernel); returns false when the launch does not meet its conditions (the caller then
-// takes wgrad3f).  list: the listed 32-row blocks of dy (pp_row_block_list) or NULL.
-bool PP_API(pp4_launch_wgrad3r)(hipStream_t st, Wgrad3Params& p, const void* xhi, const void* xlo, const void* dhi, const void* dlo, float* dw,
-                                float* dbias, const int* list, int n_cu, int variant) {
-  if (!(p.kh == 3 && p.kw == 3 && p.stride == 1 && p.pad_t == 1 && p.pad_l == 1 && p.Cin % 128 == 0 && xhi && dhi)) return false;
-  if (variant == 2 && list) return false;  // wgrad3w: dense reductions only
-  int min_ow = 1 << 30;
-  long long pos = 0;
-  for (int i = 0; i < p.n_seg; ++i) {
-    if (p.seg[i].OH != p.seg[i].SH || p.seg[i].OW != p.seg[i].SW || p.seg[i].row_begin != p.seg[i].src_row_begin) return false;
-    if (list && i + 1 < p.n_seg && p.seg[i + 1].row_begin % 32 != 0) return false;  // (a listed 32-row block never straddles two levels)
-    min_ow = p.seg[i].OW < min_ow ? p.seg[i].OW : min_ow;
-    // the dense reduction walks positions: every image row followed by one pad
-    const long long rows = (i + 1 < p.n_seg ? p.seg[i + 1].row_begin : p.M) - p.seg[i].row_begin;
-    p.pos_begin[i] = (int)pos;
-    pos += rows / p.seg[i].OW * (p.seg[i].OW + 1);
-  }
-  p.Mp = (int)pos;
-  const long long x_bytes = p.src_rows * (long long)p.ld_src * 4, d_bytes = (long long)p.M * p.ld_dy * 4;
-  if (!(min_ow >= (list ? 12 : 2) && x_bytes < (1ll << 31) && d_bytes < (1ll << 31) && pos < (1 << 24) && p.src_rows > 0)) return false;
-  p.k_tiles_per_tap = p.Cin / 128;
-  p.n_tiles_k = 3 * p.k_tiles_per_tap;
-  p.n_tiles_n = (p.Cout + 127) / 128;
-  const int tiles = p.n_tiles_k * p.n_tiles_n;
-  const int R = list ? p.M : p.Mp;  // length of the reduction space
-  // row splits: one workgroup per CU and ~1 us per 3-tap step; every split adds a |dW| of f32 atomics (~1.3 TB/s, about half of it
-  // under other workgroups' loops)
-  int max_splits = (R + 255) / 256;  // at least 8 steps per workgroup
-  if (max_splits > 128) max_splits = 128;
-  if (max_splits < 1) max_splits = 1;
-  const double atomic_steps_per_split = 0.5 * (double)tiles * 3.0 * 128.0 * 128.0 * 4.0 / 1.3e6 / 1.0;
-  int splits = 1;
-  double best = 1e300;
-  for (int sp = 1; sp <= max_splits; ++sp) {
-    const double steps = (double)((R + sp - 1) / sp + 31) / 32.0 + 6.0;
-    const double rounds = (double)(((long long)tiles * sp + n_cu - 1) / n_cu);
-    const double cost = rounds * steps + atomic_steps_per_split * sp;
-    if (cost < best * 0.995) {
-      best = cost;
-      splits = sp;
-    }
-  }
-  if (const char* e = getenv("PP_WGRAD3R_SPLITS")) {
-    const int v = atoi(e);
-    if (v >= 1 && v <= max_splits) splits = v;
-  }
-  int rps = (R + splits - 1) / splits;
-  rps = (rps + 31) / 32 * 32;
-  splits = (R + rps - 1) / rps;
-  p.splits = splits;
-  p.rows_per_split = rps;
-  if (p.sp_min_steps < 1) p.sp_min_steps = 1;
-  if (getenv("PP_CONV_DEBUG")) fprintf(stderr, "wgrad3r tiles %d (3 taps each) splits %d (M %d)%s\n", tiles, splits, p.M, list ? " listed blocks" : "");
-  if (variant == 2) {  // wgrad3w: producer / consumer waves (dense reductions; listed blocks stay with wgrad3f)
-    hipLaunchKernelGGL(wgrad3w_kernel, dim3((unsigned)(tiles * splits)), dim3(512), 0, st, p, xhi, xlo, (unsigned)x_bytes, dhi, dlo,
-                       (unsigned)d_bytes, dw, dbias);
-    return true;
-  }
-  if (list)
-    hipLaunchKernelGGL((wgrad3r_kernel<true>), dim3((unsigned)(tiles * splits)), dim3(256), 0, st, p, xhi, xlo, (unsigned)x_bytes, dhi, dlo,
-                       (unsigned)d_bytes, dw, dbias, list);
+// the tap-row-reuse weight gradient (wgrad3r_kernel, or wgrad3w_kernel: producer / consumer waves, dense reductions only) as
+// pp_plan_wgrad laid it out in p.  list: the listed 32-row blocks of dy (pp_row_block_list) or NULL.
+void PP_API(pp4_launch_wgrad3r)(hipStream_t st, const Wgrad3Params& p, unsigned grid, bool w, const void* xhi, const void* xlo, const void* dhi,
+                                const void* dlo, float* dw, float* dbias, const int* list) {
+  const unsigned x_bytes = (unsigned)(p.src_rows * (long long)p.ld_src * 4), d_bytes = (unsigned)((long long)p.M * p.ld_dy * 4);
+  if (w)
+    hipLaunchKernelGGL(wgrad3w_kernel, dim3(grid), dim3(512), 0, st, p, xhi, xlo, x_bytes, dhi, dlo, d_bytes, dw, dbias);
+  else if (list)
+    hipLaunchKernelGGL((wgrad3r_kernel<true>), dim3(grid), dim3(256), 0, st, p, xhi, xlo, x_bytes, dhi, dlo, d_bytes, dw, dbias, list);
   else
-    hipLaunchKernelGGL((wgrad3r_kernel<false>), dim3((unsigned)(tiles * splits)), dim3(256), 0, st, p, xhi, xlo, (unsigned)x_bytes, dhi, dlo,
-                       (unsigned)d_bytes, dw, dbias, (const int*)nullptr);
-  return true;
+    hipLaunchKernelGGL((wgrad3r_kernel<false>), dim3(grid), dim3(256), 0, st, p, xhi, xlo, x_bytes, dhi, dlo, d_bytes, dw, dbias, (const int*)nullptr);
 }

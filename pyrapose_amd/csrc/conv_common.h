@@ -1,11 +1,12 @@
 // Shared pieces of the implicit-GEMM convolution kernels (conv.hip: f32 MFMA; conv3.hip: 3 x bf16 MFMA):
 // row-space geometry, the gather (row -> source offset per tap), the XCD-aware tile order, descriptor checks
-// and the launch-shape cost model.
+// and the facts conv_plan.h's planners read.
 #pragma once
 #include <stdlib.h>
 
 #include <type_traits>
 
+#include "conv_plan.h"
 #include "pp_internal.h"
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
@@ -183,22 +184,142 @@ static int check_desc(pp_ctx* ctx, const pp_conv_desc* d, const char* who) {
 }
 
 
-// ---- launch-shape cost model (measured with tools/conv_bench.py on MI355X; DESIGN.md §Tile choice) ----
-// A CU that holds c equal workgroups retires them at a relative MFMA rate thr(c) (one 4-wave workgroup per CU
-// cannot hide its own staging latency: 0.62; four: 0.82 of the f32-MFMA peak).  Equal-length workgroups
-// finish in lock-step rounds, so  time / L = full_rounds * S / thr(S) + c_tail / thr(c_tail)  with S the
-// co-resident slots per CU, c_tail = ceil(remainder / CUs) and L the time of one workgroup alone at full rate.
-static double est_rounds(long long blocks, int slots, int cus) {
-  static const double thr[5] = {1.0, 0.62, 0.78, 0.81, 0.82};
-  const long long per_round = (long long)cus * slots;
-  const long long full = blocks / per_round;
-  const long long rem = blocks - full * per_round;
-  const int s_idx = slots < 4 ? slots : 4;
-  double t = (double)full * slots / thr[s_idx];
-  if (rem > 0) {
-    const int c = (int)((rem + cus - 1) / cus);
-    t += (double)c / thr[c < 4 ? c : 4];
-  }
-  return t;
+// ---- the descriptor's part of the launch parameters, per pass (the entry points add pointers and epilogue fields) ----
+static void igemm_geometry_fwd(pp_ctx* ctx, const pp_conv_desc* d, IgemmParams& p) {
+  p.ld_src = d->ld_x; p.ld_w = d->ld_w; p.ld_out = d->ld_y;
+  p.n_seg = d->in.n_seg;
+  fill_segs(ctx, d, true, p.seg, &p.M, &p.src_rows);
+  p.Cred = d->cin; p.Nout = d->cout; p.w_tap_rows = d->cin;
+  p.kh = d->kh; p.kw = d->kw;
+  p.mul = d->stride; p.tsign = 1; p.off_y = -d->pad_t; p.off_x = -d->pad_l; p.div = 1;
+  p.w_ty0 = 0; p.w_tx0 = 0; p.w_tstep = 1; p.w_kw = d->kw; p.w_taps = d->kh * d->kw;
+}
+static void igemm_geometry_bwd_data(pp_ctx* ctx, const pp_conv_desc* d, IgemmParams& p) {
+  p.ld_src = d->ld_y; p.ld_w = d->ld_w; p.ld_out = d->ld_x;
+  p.n_seg = d->in.n_seg;
+  fill_segs(ctx, d, false, p.seg, &p.M, &p.src_rows);
+  p.Cred = (d->cout + 31) / 32 * 32; p.Nout = d->cin; p.w_tap_rows = d->cin;
+  p.kh = d->kh; p.kw = d->kw;
+  p.mul = 1; p.tsign = -1; p.off_y = d->pad_t; p.off_x = d->pad_l; p.div = d->stride;
+  p.w_ty0 = 0; p.w_tx0 = 0; p.w_tstep = 1; p.w_kw = d->kw; p.w_taps = d->kh * d->kw;
+}
+static void wgrad_geometry(pp_ctx* ctx, const pp_conv_desc* d, Wgrad3Params& p) {
+  p.ld_src = d->ld_x; p.ld_dy = d->ld_y; p.ld_w = d->ld_w;
+  p.n_seg = d->in.n_seg;
+  fill_segs(ctx, d, true, p.seg, &p.M, &p.src_rows);
+  p.Cin = d->cin; p.Cout = d->cout;
+  p.kh = d->kh; p.kw = d->kw; p.stride = d->stride; p.pad_t = d->pad_t; p.pad_l = d->pad_l;
 }
 
+// every level: enumerated grid == gathered grid (a "same" convolution on an unchanged grid)
+static bool segs_same_grid(const SegGeo* seg, int n_seg) {
+  bool same = true;
+  for (int i = 0; i < n_seg && same; ++i) same = seg[i].OH == seg[i].SH && seg[i].OW == seg[i].SW && seg[i].row_begin == seg[i].src_row_begin;
+  return same;
+}
+
+// ---- the facts of a launch (conv_plan.h), from its parameters, operand forms and resources ----
+static PpIgemmFacts igemm_facts(const IgemmParams& p, int w_rows, int w_ld8, bool planes_in, bool f32_in, bool planes_out, bool f32_out,
+                                bool capture, bool flags, int n_cu, bool ws, long long ws_bytes) {
+  PpIgemmFacts f = {};
+  f.M = p.M; f.Nout = p.Nout; f.Cred = p.Cred; f.kh = p.kh; f.kw = p.kw; f.ld_out = p.ld_out; f.ld_src = p.ld_src;
+  f.w_rows = w_rows; f.w_ld8 = w_ld8; f.w_taps = p.w_taps; f.div = p.div; f.mul = p.mul; f.sc_on = p.sc_on; f.w_tstep = p.w_tstep; f.w_tx0 = p.w_tx0;
+  f.src_rows = p.src_rows;
+  for (int i = 0; i < p.n_seg; ++i) f.max_sw = p.seg[i].SW > f.max_sw ? p.seg[i].SW : f.max_sw;
+  f.same_grid = segs_same_grid(p.seg, p.n_seg);
+  f.planes_in = planes_in; f.f32_in = f32_in; f.planes_out = planes_out; f.f32_out = f32_out; f.capture = capture; f.flags = flags;
+  f.n_cu = pp_cus(n_cu); f.ws = ws; f.ws_bytes = ws_bytes;
+  return f;
+}
+
+// fills p.pos_begin / p.Mp (wgrad3r's position space: every image row followed by one pad) on the way
+static PpWgradFacts wgrad_facts(Wgrad3Params& p, bool planes, bool list, bool lazy_in, int fmt, int n_cu, bool ws, long long ws_bytes,
+                                bool dw_aligned, bool dbias_aligned) {
+  PpWgradFacts f = {};
+  f.M = p.M; f.Cin = p.Cin; f.Cout = p.Cout; f.kh = p.kh; f.kw = p.kw; f.stride = p.stride; f.pad_t = p.pad_t; f.pad_l = p.pad_l;
+  f.ld_src = p.ld_src; f.ld_dy = p.ld_dy; f.ld_w = p.ld_w; f.src_rows = p.src_rows;
+  f.min_ow = f.min_hw = 1 << 30;
+  f.list_levels_aligned = true;
+  long long pos = 0;
+  for (int i = 0; i < p.n_seg; ++i) {
+    f.min_ow = p.seg[i].OW < f.min_ow ? p.seg[i].OW : f.min_ow;
+    f.min_hw = p.seg[i].OH * p.seg[i].OW < f.min_hw ? p.seg[i].OH * p.seg[i].OW : f.min_hw;
+    if (i + 1 < p.n_seg && p.seg[i + 1].row_begin % 32 != 0) f.list_levels_aligned = false;
+    const long long rows = (i + 1 < p.n_seg ? p.seg[i + 1].row_begin : p.M) - p.seg[i].row_begin;
+    p.pos_begin[i] = (int)pos;
+    pos += rows / p.seg[i].OW * (p.seg[i].OW + 1);
+  }
+  p.Mp = (int)pos;
+  f.Mp = pos;
+  f.same_grid = segs_same_grid(p.seg, p.n_seg);
+  f.planes = planes; f.list = list; f.lazy_in = lazy_in; f.fmt = fmt;
+  f.n_cu = pp_cus(n_cu); f.ws = ws; f.ws_bytes = ws_bytes; f.dw_aligned = dw_aligned; f.dbias_aligned = dbias_aligned;
+  return f;
+}
+
+// Stride-2 bwd-data as four stride-1 launches, one per parity class (cy, cx) of the input grid: input cell
+// (2y'+cy, 2x'+cx) only receives the taps ty = ty0 + 2i with ty0 = (cy + pad_t) & 1 (x alike), from output cell
+// y' + (cy + pad_t - ty0)/2 - i.  The single-launch form spends 3/4 of its MFMAs on taps that the divisibility
+// mask zeroes; here every MFMA is useful and classes without taps (1x1 kernels) only run the epilogue.
+// p: the whole data gradient; false when a class does not meet igemm3f's conditions (the caller keeps the one launch).
+static bool igemm_parity_classes(const pp_conv_desc* d, const IgemmParams& p, bool all_planes, IgemmParams cls[4]) {
+  const int H = d->in.h[0], W = d->in.w[0];
+  for (int c = 0; c < 4; ++c) {
+    const int cy = c >> 1, cx = c & 1;
+    IgemmParams& r = cls[c];
+    r = p;
+    r.div = 1;
+    const int ty0 = (cy + d->pad_t) & 1, tx0 = (cx + d->pad_l) & 1;
+    r.kh = ty0 < d->kh ? (d->kh - ty0 + 1) / 2 : 0;
+    r.kw = tx0 < d->kw ? (d->kw - tx0 + 1) / 2 : 0;
+    r.off_y = (cy + d->pad_t - ty0) / 2;
+    r.off_x = (cx + d->pad_l - tx0) / 2;
+    r.w_ty0 = ty0; r.w_tx0 = tx0; r.w_tstep = 2; r.w_kw = d->kw;
+    if (r.kh == 0 || r.kw == 0) r.kh = r.kw = 0;  // no taps: class_fill_kernel
+    r.seg[0].OH = (H - cy + 1) / 2;
+    r.seg[0].OW = (W - cx + 1) / 2;
+    r.M = d->in.n_img * r.seg[0].OH * r.seg[0].OW;
+    r.sc_on = 1; r.sc_H = H; r.sc_W = W; r.sc_cy = cy; r.sc_cx = cx;
+    if (r.M > 0 && r.kh > 0 &&
+        !(pp_igemm_fast_ok(igemm_facts(r, d->cin, r.Cred / 8, all_planes, !all_planes, all_planes, !all_planes, false, false, 0, false, 0)) && r.M < (1 << 24)))
+      return false;
+  }
+  return true;
+}
+
+// ---- which launches a call is made of: one function each for the entry points of conv3.hip and for pp_conv_plan_text ----
+// pp_conv_opts.out_flags of the forward pass (only the flagged 32-row output blocks): plane-stored input, one output form, 3x3
+// stride 1 pad 1 on an unchanged grid, no residual
+static bool fwd_listed_ok(const pp_conv_desc* d, const PpIgemmFacts& f, bool residual) {
+  return f.planes_in && f.f32_out != f.planes_out && !f.capture && !residual && d->stride == 1 && d->kh == 3 && d->kw == 3 && d->pad_t == 1 &&
+         d->pad_l == 1 && pp_igemm_fast_ok(f) && f.same_grid;
+}
+
+struct DgradRoute {
+  bool listed;    // one launch over the listed blocks, tile 64 listed_tm x 128
+  int listed_tm;
+  bool classes;   // stride 2: the parity classes cls[] (those without taps only fill)
+  IgemmParams cls[4];
+};
+// p, f: the whole data gradient.  A lazy dy needs r->listed.
+static void dgrad_route(const pp_conv_desc* d, const IgemmParams& p, const PpIgemmFacts& f, bool skip_scratch, DgradRoute* r) {
+  const bool all_f32 = f.f32_in && f.f32_out && !f.planes_in && !f.planes_out, all_planes = f.planes_in && f.planes_out && !f.f32_out;
+  const PpDgradRouteFacts rf = {d->stride, d->kh, d->kw, d->pad_t, d->pad_l, d->in.n_seg, all_f32, all_planes, f.capture, p.bias != nullptr,
+                                f.flags, skip_scratch, pp_igemm_fast_ok(f), f.same_grid};
+  r->listed = pp_dgrad_listed_ok(rf);
+  r->listed_tm = pp_conv_switches().sparse_dgrad == 22 ? 2 : 1;
+  r->classes = pp_dgrad_classes_ok(rf) && igemm_parity_classes(d, p, all_planes, r->cls);
+}
+// the launches in order: gemm(params, is_class, listed) for every GEMM, fill(params) for a class without taps
+template <class Gemm, class Fill>
+static void dgrad_launches(DgradRoute& r, IgemmParams& p, Gemm gemm, Fill fill) {
+  if (!r.classes) {
+    gemm(p, false, r.listed);
+    return;
+  }
+  for (int c = 0; c < 4; ++c) {
+    if (r.cls[c].M <= 0) continue;
+    if (r.cls[c].kh > 0) gemm(r.cls[c], true, false);
+    else fill(r.cls[c]);
+  }
+}

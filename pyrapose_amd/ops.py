@@ -94,6 +94,19 @@ def make_conv_desc(n_img, in_shapes, out_shapes, cin, cout, k, stride, pad_t, pa
     return d
 
 
+PLAN_FWD, PLAN_BWD_DATA, PLAN_BWD_WEIGHT = 0, 1, 2
+PLAN_PLANES_IN, PLAN_PLANES_OUT, PLAN_F32_OUT, PLAN_CAPTURE, PLAN_LIST, PLAN_LAZY_IN, PLAN_LAZY_OUT = 1, 2, 4, 8, 16, 32, 64
+
+
+def conv_plan_text(d, pass_, forms=0, planes_fmt=1, n_cu=256, ws_bytes=0):
+    """Which kernels the bf16x3 entry points would launch for descriptor d (pp_conv_plan_text: host only, no context, no GPU):
+    one line per launch, the PP_CONV_DEBUG wording + the kernel family + ' | ' + the plan's numbers as key=value"""
+    buf = C.create_string_buffer(4096)
+    n = lib.pp_conv_plan_text(C.byref(d), int(pass_), int(forms), int(planes_fmt), int(n_cu), int(ws_bytes), buf, len(buf))
+    check(min(n, 0), None, "pp_conv_plan_text")
+    return buf.value.decode()
+
+
 def conv_fwd(ctx, d, x, w, bias, residual, relu, y):
     ld_res = residual.stride(0) if residual is not None else 0
     check(lib.pp_conv2d_nhwc_fwd(ctx.handle, C.byref(d), _ptr(x), _ptr(w), _ptr(bias), _ptr(residual), ld_res,

@@ -482,6 +482,16 @@ def test_lazy_sparse_gradients(ctx):
         ops.conv_bwd_weight3(ctx, d_a, None, None, torch.zeros_like(wa), None, x_planes=xa, dy_planes=xa, lazy_in=True)
 
 
+def planned(ctx, d, pass_, forms):
+    """the launch lines pp_conv_plan_text gives for the call that follows -- this context's CUs, plane format and scratch, the
+    current switches (host only) --, each ending in the kernel family"""
+    from pyrapose_amd import ops
+    ws = getattr(ctx, "workspace", None)
+    ws_bytes = ws.numel() * 4 if ws is not None else 0
+    text = ops.conv_plan_text(d, pass_, forms, ctx.planes_fmt, ctx.device_info()[0], ws_bytes)
+    return [line.split(" | ")[0] for line in text.splitlines()]
+
+
 def test_lds_dma_kernel_matches_register_staged(ctx, monkeypatch):
     """igemm4x (csrc/conv3.hip): the head-conv launch on the multi-stage LDS-DMA pipeline -- taken for planes in / planes out, 3x3
     stride 1, cout % 128 == 0 and at least two rounds of 256 x 128 tiles, with the rows of the last partly filled round going to a
@@ -514,6 +524,9 @@ def test_lds_dma_kernel_matches_register_staged(ctx, monkeypatch):
     try:
         for dma in ("0", "1"):
             monkeypatch.setenv("PP_CONV3_DMA", dma)
+            for desc, pass_ in ((d, ops.PLAN_FWD), (dT, ops.PLAN_BWD_DATA)):   # the two sides are two kernels, never one twice
+                line, = planned(ctx, desc, pass_, ops.PLAN_PLANES_IN | ops.PLAN_PLANES_OUT)
+                assert line.endswith(" igemm4x" if dma == "1" else " igemm3x[planes->planes]"), line
             yp = nan_planes(res)
             ops.conv_fwd3(ctx, d, None, fh, fl, bias, None, True, None, x_planes=xp, y_planes=yp, res_planes=rp)
             dxp = nan_planes(res)
@@ -571,6 +584,9 @@ def test_lds_dma_kernel_two_workgroups_per_cu_matches_register_staged(ctx, monke
     try:
         for dma in ("0", "1"):
             monkeypatch.setenv("PP_CONV3_DMA2", dma)
+            for desc, pass_ in ((d, ops.PLAN_FWD), (dT, ops.PLAN_BWD_DATA)):   # the two sides are two kernels, never one twice
+                line, = planned(ctx, desc, pass_, ops.PLAN_PLANES_IN | ops.PLAN_PLANES_OUT)
+                assert line.endswith(" igemm4x<NWM=2>" if dma == "1" else " igemm3x[planes->planes]"), line
             yp = nan_planes(res)
             ops.conv_fwd3(ctx, d, None, fh, fl, bias, None, True, None, x_planes=xp, y_planes=yp, res_planes=rp)
             dxp = nan_planes(res)
@@ -622,6 +638,8 @@ def test_persistent_1x1_gemm_matches_register_staged(ctx, monkeypatch, case):
             else:
                 monkeypatch.setenv("PP_CONV4P_SPLITS", "1")
                 monkeypatch.setenv("PP_CONV3_SPLITS", "1")
+            line, = planned(ctx, d, ops.PLAN_FWD if kind == "fwd" else ops.PLAN_BWD_DATA, ops.PLAN_PLANES_IN | ops.PLAN_PLANES_OUT)
+            assert line.endswith(" igemm4p") == (variant != "0") and (variant != "0" or line.endswith(" igemm3f")), line
             if kind == "fwd":
                 yp = nan_planes(res)
                 ops.conv_fwd3(ctx, d, None, fh, fl, bias, None, True, None, x_planes=xp, y_planes=yp, res_planes=rp)
@@ -685,6 +703,8 @@ def test_tap_row_reuse_weight_gradient_matches_wgrad3f(ctx, monkeypatch, case):
     out = {}
     for r in ("0", "1", "2"):  # wgrad3f / wgrad3r / wgrad3w (producer + consumer waves)
         monkeypatch.setenv("PP_WGRAD3R", r)
+        line, = planned(ctx, d, ops.PLAN_BWD_WEIGHT, ops.PLAN_PLANES_IN)
+        assert line.endswith({"0": " wgrad3f[planes]", "1": " wgrad3r", "2": " wgrad3w"}[r]), line
         dw, db = torch.zeros((k * k * cin, ld_w), device="cuda"), torch.zeros((ld_w,), device="cuda")
         ops.conv_bwd_weight3(ctx, d, None, None, dw, db, x_planes=xp, dy_planes=gp)
         dws, dbs = torch.zeros((k * k * cin, ld_w), device="cuda"), torch.zeros((ld_w,), device="cuda")
