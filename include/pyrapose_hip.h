@@ -852,6 +852,88 @@ int pp_farthest_points_f64(pp_ctx* ctx, int n_model, int n_total, const double* 
                            int k, int rule, const double* min_dist, const int* start, void* workspace, size_t workspace_bytes,
                            int* index);
 
+/* ---- 2-D detection average precision (csrc/det_eval.hip) -----------------------------------------------------------------
+ * utils/eval.py:147-235 (evaluate, the 'mAP' of callbacks/eval.py) and BOP's detection score (COCO AP with ignored ground
+ * truth) on the device: greedy matching per image, then true / false positive scans, precision envelope and the integral per
+ * (threshold, class).  float64, every product, quotient and sum rounded on its own; no atomics: bit-identical run to run and
+ * independent of the batch an image sits in.  The reference rule is pinned to the reference's evaluate through
+ * tests/golden/detection_ap.npz; the COCO rule and the 101-point integration restate pycocotools (cocoeval.py evaluateImg /
+ * accumulate) and their parity with it is unpinned.  All of it is restated in tests/det_eval_np.py.
+ *
+ * pp_det_match: detections of `batch` images against their ground truth, at n_thr IoU thresholds in one launch.
+ *   in   det_boxes [B,D,4] (x1, y1, x2, y2), det_scores [B,D] float64, det_labels [B,D] int32 -- the layout
+ *        pp_filter_detections_batch writes, widened to float64.  A slot whose label is outside [0, n_class) is padding (-1 is
+ *        what the filter writes); padding may sit anywhere in a row.  Scores must not be NaN, boxes must be finite.
+ *        gt_boxes [G,4] float64, gt_labels [G] int32, gt_ignore [G] uint8 or NULL (none ignored), gt_offsets [B+1] int32 from 0
+ *        to G, given twice as pp_farthest_points_f64's are: the HOST copy is checked before anything is launched, the kernel
+ *        reads the device copy.  A ground truth whose label is outside [0, n_class) matches nothing and is not counted.
+ *        thresholds [n_thr] float64 on the HOST, strictly increasing within [0, 1].
+ *   out  match [T,B,D] int32: the global ground-truth index (into gt_boxes) the detection is matched to, or -1
+ *        det_ignored [T,B,D] uint8: 1 for a detection that counts neither as true nor as false positive
+ *        npos [n_class] int32: ground truth per class over the whole batch, the ignored ones left out
+ *   Detections of an image are visited in descending score, equal scores (float compare: -0 == +0) by the lower slot.
+ *   rule PP_DET_RULE_REFERENCE (utils/eval.py:187-211):
+ *     IoU of pp_compute_overlap_f64 (the "+1" convention; the same device function, detection as `boxes` row, ground truth as
+ *     `query` row).  A detection looks at EVERY ground truth of its own label in its image, taken or not, and picks the first
+ *     maximum (np.argmax: the lowest index on ties).  It is a true positive (match = that index) iff that maximum is >= the
+ *     threshold and that ground truth has not been taken; otherwise a false positive (-1) -- no fall-back to the second best.
+ *     No ground truth of its label: false positive.  det_ignored is all 0; gt_ignore must be NULL (PP_ERR_ARG).
+ *   rule PP_DET_RULE_COCO (pycocotools evaluateImg without crowd and area ranges):
+ *     IoU = i / (area_d + area_g - i), i = w h of the intersection, areas (x2 - x1)(y2 - y1), no "+1"; 0 unless w > 0 and h > 0.
+ *     Ground truth of the detection's label is visited not-ignored first, then ignored, each in input order; taken ones are
+ *     skipped.  The detection takes the one with the highest IoU >= min(threshold, 1 - 1e-10); among equal IoUs the LATER one in
+ *     visiting order; the search stops at the first ignored ground truth once a not-ignored match is held, so an ignored one is
+ *     taken only when no not-ignored one qualifies.  A matched ground truth is consumed, ignored or not; a detection matched
+ *     to an ignored one has det_ignored = 1.  Unmatched: match -1, det_ignored 0 (a false positive).
+ *   Layout: one workgroup per image, one wave per threshold.  The score order is computed once per workgroup by rank
+ *   counting in LDS; a wave's lanes stride over the image's ground truth (held in LDS), each lane owning the taken flags
+ *   (LDS, per threshold) of its own ground truth; a 64-lane butterfly under the rule's tie-break picks the match.
+ *   Limits (PP_ERR_ARG before anything is launched): 1 <= n_thr <= PP_DET_MAX_THR; 0 <= D <= PP_DET_MAX_DET; at most
+ *   PP_DET_MAX_GT ground truths in one image; offsets that decrease or do not run from 0 to G; batch, n_class < 1;
+ *   T * B * D >= 2^31; thresholds not increasing or outside [0, 1]; unknown rule; null pointers (D = 0: the detection tensors
+ *   and outputs may be NULL and only npos is written).  Labels live on the device and are not looked at by this entry point:
+ *   the Python wrapper (ops.det_match) refuses labels >= n_class; here they are padding as said above.
+ *
+ * pp_det_pr_curve: the curves of every (threshold, class) over the detections of all images in one global order.
+ *   in   order [N] int32: flat slots b * D + d of the non-padding detections, class-major; class_offsets [n_class+1] int32
+ *        (device) into it; within a class the caller's order stands (ops.det_order: descending score, then ascending slot).
+ *        match, det_ignored [T,n_slots] and npos [n_class] as pp_det_match wrote them, n_slots = B * D.
+ *   out  tp, fp [T,N] int32: inclusive running counts within the class's segment; a detection with det_ignored adds to neither
+ *        recall [T,N]   = tp / npos                          (utils/eval.py:228; 0 where npos is 0)
+ *        prec_env [T,N] = reverse running maximum, from the segment's end, of tp / max(tp + fp, 2^-52)   (:229, :46-47)
+ *   One workgroup per (class, threshold) scans its segment in chunks of PP_DET_SCAN_CHUNK with a carry, forward for the
+ *   counts, backward for the envelope; any segment length works, an empty one writes nothing.
+ *   Errors: n_thr outside 1..PP_DET_MAX_THR, n_class < 1, N < 0 or > n_slots, T * n_slots >= 2^31, null pointers: PP_ERR_ARG.
+ *
+ * pp_det_ap: ap [T,n_class] and recall_final [T,n_class] (the segment's last recall, 0 for an empty segment) from those curves.
+ *   mode PP_DET_AP_AREA (_compute_ap, utils/eval.py:42-54): with r_-1 = 0, the sum over the segment's points j where
+ *     r_j != r_j-1 of (r_j - r_j-1) * prec_env_j -- each r a quotient as stored, the difference taken of the two quotients (the
+ *     closing term of _compute_ap, (1 - r_last) * 0, adds nothing).  Order of the sum, n the segment length: thread k of 256
+ *     adds the terms of j in [k per, min(n, (k + 1) per)), per = ceil(n / 256), in ascending j onto 0.0; the 256 partials
+ *     p_k are then folded by the halving tree p_k += p_k+s for s = 128, 64, ..., 1 (k < s); the result is p_0.
+ *     A class with npos = 0: ap = 0, recall_final = 0 (eval.py:214-216 returns (0, 0)).
+ *   mode PP_DET_AP_101 (COCO accumulate): for k = 0..100, r_k = k * 0.01 (1.0 for k = 100: np.linspace(0, 1, 101)), i_k = the
+ *     first j with recall_j >= r_k (np.searchsorted, side 'left'), q_k = prec_env at i_k, or 0 when there is none;
+ *     ap = (((q_0 + q_1) + q_2) + ... + q_100) / 101.  A class with npos = 0: ap = -1, recall_final = -1 (left out of means).
+ *   Errors: unknown mode, n_thr outside 1..PP_DET_MAX_THR, n_class < 1, N < 0, T * N >= 2^31, null pointers: PP_ERR_ARG. */
+#define PP_DET_RULE_REFERENCE 0
+#define PP_DET_RULE_COCO 1
+#define PP_DET_AP_AREA 0
+#define PP_DET_AP_101 1
+#define PP_DET_MAX_THR 16
+#define PP_DET_MAX_DET 1024
+#define PP_DET_MAX_GT 1024
+#define PP_DET_SCAN_CHUNK 256
+int pp_det_match(pp_ctx* ctx, int batch, int n_det, int n_gt, int n_class, const double* det_boxes, const double* det_scores,
+                 const int* det_labels, const double* gt_boxes, const int* gt_labels, const unsigned char* gt_ignore,
+                 const int* gt_offsets_host, const int* gt_offsets_dev, int n_thr, const double* thresholds, int rule, int* match,
+                 unsigned char* det_ignored, int* npos);
+int pp_det_pr_curve(pp_ctx* ctx, int n_thr, int n_order, int n_class, long long n_slots, const int* order, const int* class_offsets,
+                    const int* match, const unsigned char* det_ignored, const int* npos, int* tp, int* fp, double* recall,
+                    double* prec_env);
+int pp_det_ap(pp_ctx* ctx, int n_thr, int n_order, int n_class, const int* class_offsets, const int* npos, const double* recall,
+              const double* prec_env, int mode, double* ap, double* recall_final);
+
 #ifdef __cplusplus
 }
 #endif

@@ -121,3 +121,42 @@ class PoseEval(Callback):
             logs["recall"], logs["detections"] = self.last["recall_all"], self.last["detections_all"]
         if self.verbose:
             print("epoch %d: ADD(-S) recall %.4f, detections %.4f" % (epoch + 1, self.last["recall_all"], self.last["detections_all"]))
+
+
+class Evaluate(Callback):
+    """callbacks/eval.py:21-97: at the end of every epoch run utils.eval.evaluate (per-class VOC-style AP, matched and
+    integrated on the device) on `generator` with this callback's model and set logs['mAP'] and self.mean_ap: the mean of the
+    per-class APs over the classes that have annotations, or with weighted_average the mean weighted by their annotation
+    counts.  save_path goes to evaluate (which draws nothing and refuses it); tensorboard other than None is ignored, with one
+    warning."""
+
+    def __init__(self, generator, iou_threshold=0.5, score_threshold=0.05, max_detections=100, save_path=None, tensorboard=None,
+                 weighted_average=False, verbose=1):
+        super(Evaluate, self).__init__()
+        self.generator, self.iou_threshold, self.score_threshold = generator, iou_threshold, score_threshold
+        self.max_detections, self.save_path, self.tensorboard = max_detections, save_path, tensorboard
+        self.weighted_average, self.verbose, self.mean_ap = weighted_average, verbose, None
+        if tensorboard is not None:
+            import warnings
+            warnings.warn("Evaluate: there is no TensorBoard writer here; the tensorboard argument is ignored")
+
+    def on_epoch_end(self, epoch, logs=None):
+        from .utils import eval as _eval  # (looked up per call: the device library loads with the first evaluation)
+        logs = logs if logs is not None else {}
+        average_precisions = _eval.evaluate(self.generator, self.model, iou_threshold=self.iou_threshold,
+                                            score_threshold=self.score_threshold, max_detections=self.max_detections,
+                                            save_path=self.save_path)
+        total_instances, precisions = [], []
+        for label, (average_precision, num_annotations) in average_precisions.items():
+            if self.verbose == 1:
+                print("{:.0f} instances of class".format(num_annotations), self.generator.label_to_name(label),
+                      "with average precision: {:.4f}".format(average_precision))
+            total_instances.append(num_annotations)
+            precisions.append(average_precision)
+        if self.weighted_average:
+            self.mean_ap = sum([a * b for a, b in zip(total_instances, precisions)]) / sum(total_instances)
+        else:
+            self.mean_ap = sum(precisions) / sum(x > 0 for x in total_instances)
+        logs["mAP"] = self.mean_ap
+        if self.verbose == 1:
+            print("mAP: {:.4f}".format(self.mean_ap))

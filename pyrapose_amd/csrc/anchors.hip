@@ -10,6 +10,7 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include "box_iou.h"
 #include "pp_internal.h"
 
 // ------------------------------------------------------------------------------------------ T1 (host)
@@ -104,15 +105,7 @@ extern "C" int pp_anchors_shift_f32(pp_ctx* ctx, int n_levels, const int* fh, co
 }
 
 // ------------------------------------------------------------------------------------------ T3
-__device__ __forceinline__ double iou_plus1(double bx1, double by1, double bx2, double by2, double qx1, double qy1, double qx2,
-                                            double qy2, double q_area) {
-  const double iw = fmin(bx2, qx2) - fmax(bx1, qx1) + 1;
-  if (!(iw > 0)) return 0.0;
-  const double ih = fmin(by2, qy2) - fmax(by1, qy1) + 1;
-  if (!(ih > 0)) return 0.0;
-  const double ua = (bx2 - bx1 + 1) * (by2 - by1 + 1) + q_area - iw * ih;
-  return iw * ih / ua;
-}
+// iou_plus1 (the "+1" overlap of compute_overlap.pyx): box_iou.h, shared with det_eval.hip
 
 __global__ void overlap_kernel(int n, const double* __restrict__ boxes, int k, const double* __restrict__ query,
                                double* __restrict__ out) {

@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from ._lib import ConvDesc, ConvOpts, ParamDesc, RowSpace, TView, check, lib
+from ._lib import check as check_status  # for wrappers that take a `check` argument of their own
 
 
 def _ptr(t):
@@ -1224,3 +1225,143 @@ def farthest_points(ctx, pts, offsets, k, rule="min", min_dist=None, start=None)
                                      FPS_RULES[rule], _ptr(min_dist), _ptr(start), _ptr(ws), nbytes, _ptr(index)), ctx.handle,
           "pp_farthest_points_f64")
     return index
+
+
+DET_RULES = {"reference": 0, "coco": 1}       # PP_DET_RULE_*
+DET_INTEGRATIONS = {"area": 0, "101": 1}      # PP_DET_AP_*
+DET_MAX_THR = 16      # thresholds per pp_det_match launch (one wave each)
+DET_MAX_DET = 1024    # detection slots per image its LDS layout holds
+DET_MAX_GT = 1024     # ground truth per image it holds
+DET_SCAN_CHUNK = 256  # detections per scan step of pp_det_pr_curve
+
+
+def _det_labels_ok(what, name, labels, n_class, padding):
+    """labels (cuda int32) all inside [0, n_class), or -1 where `padding` is allowed; a host look (one sync)"""
+    if labels.numel() == 0:
+        return
+    lo, hi = int(labels.min()), int(labels.max())
+    if hi >= n_class or lo < (-1 if padding else 0):
+        raise ValueError("%s: %s must lie in [0, %d)%s, got %d..%d" % (what, name, n_class, " or be -1 (padding)" if padding else "", lo, hi))
+
+
+def det_match(ctx, det_boxes, det_scores, det_labels, gt_boxes, gt_labels, gt_offsets, n_class, thresholds, rule="reference",
+              gt_ignore=None, check=True):
+    """Detections of B images matched to their ground truth at T IoU thresholds in one launch (pp_det_match): cuda tensors
+    det_boxes float64 [B,D,4], det_scores float64 [B,D], det_labels int32 [B,D] (-1 = padding, anywhere in a row), gt_boxes
+    float64 [G,4], gt_labels int32 [G], gt_offsets int32 [B+1] from 0 to G, gt_ignore uint8 [G] or None; thresholds: 1..16
+    host floats, increasing within [0, 1]; rule 'reference' (utils/eval.py: "+1" IoU, first-maximum ground truth, no second
+    choice; gt_ignore must be None) or 'coco' (pycocotools' evaluateImg without crowd, restated) -> (match int32 [T,B,D] global
+    ground-truth index or -1, det_ignored uint8 [T,B,D], npos int32 [n_class] ground truth per class that is not ignored).
+    D <= 1024 and at most 1024 ground truths per image.  The offsets are always looked at on the host; check=False skips the
+    look at the labels (one more sync): labels outside [0, n_class) then count as padding / match nothing."""
+    what = "det_match"
+    if rule not in DET_RULES:
+        raise ValueError("%s: unknown rule %r (reference | coco)" % (what, rule))
+    thr = np.ascontiguousarray(np.asarray(thresholds, np.float64).reshape(-1))
+    T = int(thr.size)
+    if not 1 <= T <= DET_MAX_THR:
+        raise ValueError("%s: need 1..%d thresholds, got %d" % (what, DET_MAX_THR, T))
+    if not (np.all(thr >= 0.0) and np.all(thr <= 1.0) and np.all(np.diff(thr) > 0.0)):
+        raise ValueError("%s: thresholds must increase within [0, 1]" % what)
+    n_class = int(n_class)
+    if n_class < 1:
+        raise ValueError("%s: n_class must be >= 1" % what)
+    det_scores = _arg(what, "det_scores", det_scores, _F64, (None, None))
+    B, D = (int(s) for s in det_scores.shape)
+    det_boxes = _arg(what, "det_boxes", det_boxes, _F64, (B, D, 4))
+    det_labels = _arg(what, "det_labels", det_labels, _I32, (B, D))
+    gt_boxes = _arg(what, "gt_boxes", gt_boxes, _F64, (None, 4))
+    G = int(gt_boxes.shape[0])
+    gt_labels = _arg(what, "gt_labels", gt_labels, _I32, (G,))
+    gt_ignore = _arg(what, "gt_ignore", gt_ignore, _U8, (G,), optional=True)
+    if gt_ignore is not None and rule == "reference":
+        raise ValueError("%s: the reference rule has no ignored ground truth (gt_ignore must be None)" % what)
+    if B < 1 or D > DET_MAX_DET or T * B * D >= 2 ** 31:
+        raise ValueError("%s: need B >= 1, D <= %d and T * B * D < 2^31, got B = %d, D = %d" % (what, DET_MAX_DET, B, D))
+    gt_offsets, off = _check_offsets(what, gt_offsets, G, True, name="gt_offsets")
+    if off.size != B + 1:
+        raise ValueError("%s: gt_offsets must hold B + 1 = %d entries, got %d" % (what, B + 1, off.size))
+    if B and int(np.diff(off).max()) > DET_MAX_GT:
+        raise ValueError("%s: an image has %d ground truths, the limit is %d" % (what, int(np.diff(off).max()), DET_MAX_GT))
+    if check:
+        _det_labels_ok(what, "det_labels", det_labels, n_class, True)
+        _det_labels_ok(what, "gt_labels", gt_labels, n_class, False)
+    off = np.ascontiguousarray(off, np.int32)
+    match, ign = _out(det_scores, (T, B, D), _I32), _out(det_scores, (T, B, D), _U8)
+    npos = _out(det_scores, (n_class,), _I32)
+    check_status(lib.pp_det_match(ctx.handle, B, D, G, n_class, _ptr(det_boxes), _ptr(det_scores), _ptr(det_labels), _ptr(gt_boxes),
+                                  _ptr(gt_labels), _ptr(gt_ignore), off.ctypes.data_as(C.POINTER(C.c_int)), _ptr(gt_offsets), T,
+                                  thr.ctypes.data_as(C.POINTER(C.c_double)), DET_RULES[rule], _ptr(match), _ptr(ign), _ptr(npos)),
+                 ctx.handle, "pp_det_match")
+    return match, ign, npos
+
+
+def det_order(det_scores, det_labels, n_class):
+    """The global order pp_det_pr_curve scans: cuda det_scores [B,D], det_labels int32 [B,D] -> (order int32 [N]: the flat
+    slots b * D + d of the detections with a label in [0, n_class), class-major, then descending score, then ascending flat
+    slot; class_offsets int32 [n_class+1] into it).  torch.sort(stable=True) on the device: plumbing, not the hot path.
+    The tie-break between equal scores is the library's own: the reference's np.argsort(-scores) (utils/eval.py:219, a
+    quicksort) leaves the order of ties undefined, pycocotools sorts with a stable mergesort over its own detection list;
+    the ascending flat slot is the stable order of the layout the detections arrive in."""
+    n_class = int(n_class)
+    s, l = det_scores.reshape(-1), det_labels.reshape(-1)
+    slot = torch.nonzero((l >= 0) & (l < n_class)).reshape(-1)
+    slot = slot[torch.sort(s[slot], descending=True, stable=True).indices]
+    lab = l[slot].long()
+    order = slot[torch.sort(lab, stable=True).indices].to(_I32)
+    counts = torch.bincount(lab, minlength=n_class)
+    offsets = torch.zeros((n_class + 1,), dtype=_I32, device=s.device)
+    offsets[1:] = torch.cumsum(counts, 0)
+    return order, offsets
+
+
+def _det_curve_args(what, class_offsets, npos, N, check):
+    npos = _arg(what, "npos", npos, _I32, (None,))
+    n_class = int(npos.shape[0])
+    if n_class < 1:
+        raise ValueError("%s: npos must hold at least one class" % what)
+    class_offsets, off = _check_offsets(what, class_offsets, N, check, name="class_offsets")
+    if class_offsets.numel() != n_class + 1:
+        raise ValueError("%s: class_offsets must hold n_class + 1 = %d entries, got %d" % (what, n_class + 1, class_offsets.numel()))
+    return class_offsets, npos, n_class
+
+
+def det_pr_curve(ctx, order, class_offsets, match, det_ignored, npos, check=True):
+    """True / false positive scans, recall and precision envelope of every (threshold, class) (pp_det_pr_curve): order int32
+    [N] and class_offsets int32 [C+1] from det_order, match int32 [T,B,D], det_ignored uint8 [T,B,D] and npos int32 [C] from
+    det_match -> (tp int32 [T,N], fp int32 [T,N] inclusive running counts within each class, recall float64 [T,N] = tp /
+    npos, prec_env float64 [T,N] = reverse running maximum of tp / max(tp + fp, eps)).  check=False skips the host look at
+    class_offsets (a sync); they must then rise from 0 to N."""
+    what = "det_pr_curve"
+    order = _arg(what, "order", order, _I32, (None,))
+    N = int(order.shape[0])
+    match = _arg(what, "match", match, _I32, (None, None, None))
+    T, n_slots = int(match.shape[0]), int(match.shape[1]) * int(match.shape[2])
+    det_ignored = _arg(what, "det_ignored", det_ignored, _U8, tuple(match.shape))
+    if not 1 <= T <= DET_MAX_THR or N > n_slots or T * n_slots >= 2 ** 31:
+        raise ValueError("%s: need 1..%d thresholds, N <= B * D and T * B * D < 2^31" % (what, DET_MAX_THR))
+    class_offsets, npos, n_class = _det_curve_args(what, class_offsets, npos, N, check)
+    tp, fp = _out(order, (T, N), _I32), _out(order, (T, N), _I32)
+    recall, env = _out(order, (T, N)), _out(order, (T, N))
+    check_status(lib.pp_det_pr_curve(ctx.handle, T, N, n_class, n_slots, _ptr(order), _ptr(class_offsets), _ptr(match), _ptr(det_ignored),
+                                     _ptr(npos), _ptr(tp), _ptr(fp), _ptr(recall), _ptr(env)), ctx.handle, "pp_det_pr_curve")
+    return tp, fp, recall, env
+
+
+def det_ap(ctx, class_offsets, npos, recall, prec_env, integration="area", check=True):
+    """Average precision per (threshold, class) from det_pr_curve's curves (pp_det_ap): integration 'area' (the reference's
+    _compute_ap: sum of recall steps times the envelope; a class without ground truth gives 0) or '101' (COCO's 101 recall
+    points; such a class gives -1 and is left out of means) -> (ap float64 [T,C], recall_final float64 [T,C])."""
+    what = "det_ap"
+    if integration not in DET_INTEGRATIONS:
+        raise ValueError("%s: unknown integration %r (area | 101)" % (what, integration))
+    recall = _arg(what, "recall", recall, _F64, (None, None))
+    T, N = (int(s) for s in recall.shape)
+    prec_env = _arg(what, "prec_env", prec_env, _F64, (T, N))
+    if not 1 <= T <= DET_MAX_THR or T * N >= 2 ** 31:
+        raise ValueError("%s: need 1..%d thresholds and T * N < 2^31" % (what, DET_MAX_THR))
+    class_offsets, npos, n_class = _det_curve_args(what, class_offsets, npos, N, check)
+    ap, rf = _out(recall, (T, n_class)), _out(recall, (T, n_class))
+    check_status(lib.pp_det_ap(ctx.handle, T, N, n_class, _ptr(class_offsets), _ptr(npos), _ptr(recall), _ptr(prec_env),
+                               DET_INTEGRATIONS[integration], _ptr(ap), _ptr(rf)), ctx.handle, "pp_det_ap")
+    return ap, rf
