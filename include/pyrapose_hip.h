@@ -231,6 +231,19 @@ int pp_conv2d_nhwc_bwd_data_bf16x3(pp_ctx* ctx, const pp_conv_desc* d, const flo
                                    const void* dy_lo, const void* w_dgrad_hi, const void* w_dgrad_lo,
                                    const float* addend, int ld_add, const float* relu_src, int ld_rs, float* dx,
                                    void* dx_hi, void* dx_lo, const pp_conv_opts* opts);
+/* The stride-2 data gradient in ONE launch: same arguments and, bit for bit, the same dx as pp_conv2d_nhwc_bwd_data_bf16x3, which
+ * runs such a gradient as one launch per parity class (cy, cx) of the input grid and fills the classes no tap reaches (three of
+ * four for a 1x1 kernel) with a pointwise pass.  Here the tile grids of the classes are one grid, heaviest class first, and a class
+ * without taps runs the epilogue alone: dx = relu_src?(addend or 0) there.  For stride 2, one level, operands all float32 (dy, dx)
+ * or all planes (dy_hi / dy_lo, dx_hi / dx_lo, dx NULL); of pp_conv_opts only add_hi / add_lo / mask_hi.  Every other call is refused
+ * with PP_ERR_ARG before anything is launched -- it never falls back to another route. */
+int pp_conv2d_nhwc_bwd_data_s2_bf16x3(pp_ctx* ctx, const pp_conv_desc* d, const float* dy, const void* dy_hi,
+                                      const void* dy_lo, const void* w_dgrad_hi, const void* w_dgrad_lo,
+                                      const float* addend, int ld_add, const float* relu_src, int ld_rs, float* dx,
+                                      void* dx_hi, void* dx_lo, const pp_conv_opts* opts);
+/* 1 unless PP_CONV3_S2MERGED=0 (read at every call): whether a caller that has both routes should take the one above -- the
+ * Engine asks when it builds its backward plan.  The entry points themselves do not look at the switch. */
+int pp_conv_s2_merged(void);
 /* dw += x^T (*) dy; operands either f32 (split on the fly) or all four planes; same contract as
  * pp_conv2d_nhwc_bwd_weight, cin % 64 == 0. */
 int pp_conv2d_nhwc_bwd_weight_bf16x3(pp_ctx* ctx, const pp_conv_desc* d, const float* x, const float* dy,
@@ -248,6 +261,7 @@ int pp_conv2d_nhwc_bwd_weight_bf16x3(pp_ctx* ctx, const pp_conv_desc* d, const f
 #define PP_PLAN_FWD 0
 #define PP_PLAN_BWD_DATA 1
 #define PP_PLAN_BWD_WEIGHT 2
+#define PP_PLAN_BWD_DATA_S2 3 /* pp_conv2d_nhwc_bwd_data_s2_bf16x3: one line, or a "refused" line where the call would return PP_ERR_ARG */
 #define PP_PLAN_PLANES_IN 1u
 #define PP_PLAN_PLANES_OUT 2u
 #define PP_PLAN_F32_OUT 4u

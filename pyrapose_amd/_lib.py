@@ -131,6 +131,8 @@ _SIGS = {
     "pp_conv_split_weights_bf16x3_batch": (_i, [_p, _i, _p, _i]),
     "pp_conv2d_nhwc_fwd_bf16x3": (_i, [_p, C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, C.POINTER(ConvOpts)]),
     "pp_conv2d_nhwc_bwd_data_bf16x3": (_i, [_p, C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, C.POINTER(ConvOpts)]),
+    "pp_conv2d_nhwc_bwd_data_s2_bf16x3": (_i, [_p, C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, C.POINTER(ConvOpts)]),
+    "pp_conv_s2_merged": (_i, []),
     "pp_conv2d_nhwc_bwd_weight_bf16x3": (_i, [_p, C.POINTER(ConvDesc), _p, _p, _p, _p, _p, _p, _p, _p, C.POINTER(ConvOpts)]),
     "pp_conv_plan_text": (_i, [C.POINTER(ConvDesc), _i, C.c_uint, _i, _i, _sz, C.c_char_p, _i]),
     "pp_maxpool3x3s2_fwd": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p]),

@@ -205,13 +205,16 @@ __global__ __launch_bounds__(256, (TM * TN >= 8) ? 2 : ((TM * TN == 4) ? 3 : 4))
 // indices; pp_conv_opts.skip_flags: the blocks of the data gradient that a non-zero of dy can reach), four (two) blocks
 // to a tile; the grid is sized for the dense case and workgroups past the end of the list leave at once.  Rows keep their
 // own gather offsets (this loop never assumed that the rows of a tile are consecutive); rl_fill_kernel writes the rest.
-template <int TM, int TN, bool AP, bool OP, bool SC = false, bool RL = false>
-__global__ __launch_bounds__(256, (TM * TN >= 8) ? 2 : ((TM * TN == 4) ? 3 : 4)) void igemm3f_kernel(
-    const IgemmParams p, const void* __restrict__ g_a0, const void* __restrict__ g_a1, unsigned a_bytes,
+// MG (merged stride-2 data gradient, igemm3m_kernel): the workgroup is number `bid` of the `n_wg_in` workgroups of ITS parity
+// class, p holds that class's geometry, and a class may have no taps: no step is staged or run, the accumulators stay zero and
+// the epilogue writes mask?(addend or 0).
+template <int TM, int TN, bool AP, bool OP, bool SC, bool RL, bool MG>
+__device__ __forceinline__ void igemm3f_body(
+    const IgemmParams& p, const int bid, const int n_wg_in, const void* __restrict__ g_a0, const void* __restrict__ g_a1, unsigned a_bytes,
     const void* __restrict__ g_whi, const void* __restrict__ g_wlo, unsigned w_bytes,
     const float* __restrict__ g_bias, const float* __restrict__ g_addend, const float* __restrict__ g_mask,
     float* __restrict__ g_out, uint2* __restrict__ g_ohi, uint2* __restrict__ g_olo, int w_rows, int w_ld8, int splits,
-    float* __restrict__ g_ws, const int* __restrict__ g_rl = nullptr, const unsigned char* __restrict__ g_srcflags = nullptr) {
+    float* __restrict__ g_ws, const int* __restrict__ g_rl, const unsigned char* __restrict__ g_srcflags) {
   constexpr int BM = 64 * TM, BN = 64 * TN, BK = 32, NO = BK / 8;
   constexpr int SMEM_U4 = 2 * NO * (BM + BN);
   constexpr int ES = 4;  // bytes per gathered element: f32, or packed planes (hi at the group's offset, lo 16 bytes behind = rs_a1)
@@ -223,13 +226,14 @@ __global__ __launch_bounds__(256, (TM * TN >= 8) ? 2 : ((TM * TN == 4) ? 3 : 4))
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  int n_wg = (int)gridDim.x;
+  int n_wg = n_wg_in;
   if (RL) {  // the grid is sized for the dense case: only the first ceil(count / blocks per tile) x n_tiles_n workgroups work,
              // and the XCD remap runs over THEM (over the whole grid the listed tiles would all land on the first XCDs)
     n_wg = ((g_rl[0] + BM / 32 - 1) / (BM / 32)) * p.n_tiles_n * splits;
-    if ((int)blockIdx.x >= n_wg) return;  // workgroup-uniform, before any barrier
+    if (bid >= n_wg) return;  // workgroup-uniform, before any barrier
   }
-  const int lbs = xcd_remap((int)blockIdx.x, n_wg);
+  // (MG: workgroups bid = b (mod 8) of one class share an XCD -- the class's first workgroup only shifts WHICH one)
+  const int lbs = xcd_remap(bid, n_wg);
   const int split = lbs % splits, lb = lbs / splits;  // split-K: `splits` workgroups share one output tile
   const int tile_n = lb % p.n_tiles_n, tile_m = lb / p.n_tiles_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
@@ -288,7 +292,7 @@ __global__ __launch_bounds__(256, (TM * TN >= 8) ? 2 : ((TM * TN == 4) ? 3 : 4))
   uint4 rah[TM], ral[TM];
   uint4 rbh[TN], rbl[TN];
   int tap = s_begin / steps_per_tap, red0 = (s_begin - tap * steps_per_tap) * BK;
-  int ty = tap / p.kw, tx = tap - ty * p.kw;
+  int ty = tap / (MG ? max(p.kw, 1) : p.kw), tx = tap - ty * p.kw;  // (MG: a class without taps has kw == 0)
 
   auto load_step = [&]() {
     const int a_uni = tx * x_pitch + red0 * ES;
@@ -357,9 +361,11 @@ __global__ __launch_bounds__(256, (TM * TN >= 8) ? 2 : ((TM * TN == 4) ? 3 : 4))
 
   const int il = lane & 31, h = lane >> 5;
 
-  load_step();
-  split_step();
-  store_step();
+  if (!MG || s_begin < s_end) {  // (workgroup-uniform)
+    load_step();
+    split_step();
+    store_step();
+  }
   __syncthreads();
 
   for (int step = s_begin; step < s_end; ++step) {
@@ -395,6 +401,40 @@ __global__ __launch_bounds__(256, (TM * TN >= 8) ? 2 : ((TM * TN == 4) ? 3 : 4))
     return;
   }
   epilogue3<TM, TN, OP, PP_EPI_GF, SC, false, RL>(p, acc, smem, m0, n0, tid, wm, wn, il, h, g_bias, g_addend, g_mask, g_out, g_ohi, g_olo, rl_blk);
+}
+
+template <int TM, int TN, bool AP, bool OP, bool SC = false, bool RL = false>
+__global__ __launch_bounds__(256, (TM * TN >= 8) ? 2 : ((TM * TN == 4) ? 3 : 4)) void igemm3f_kernel(
+    const IgemmParams p, const void* __restrict__ g_a0, const void* __restrict__ g_a1, unsigned a_bytes,
+    const void* __restrict__ g_whi, const void* __restrict__ g_wlo, unsigned w_bytes,
+    const float* __restrict__ g_bias, const float* __restrict__ g_addend, const float* __restrict__ g_mask,
+    float* __restrict__ g_out, uint2* __restrict__ g_ohi, uint2* __restrict__ g_olo, int w_rows, int w_ld8, int splits,
+    float* __restrict__ g_ws, const int* __restrict__ g_rl = nullptr, const unsigned char* __restrict__ g_srcflags = nullptr) {
+  igemm3f_body<TM, TN, AP, OP, SC, RL, false>(p, (int)blockIdx.x, (int)gridDim.x, g_a0, g_a1, a_bytes, g_whi, g_wlo, w_bytes, g_bias, g_addend,
+                                              g_mask, g_out, g_ohi, g_olo, w_rows, w_ld8, splits, g_ws, g_rl, g_srcflags);
+}
+
+// ---- igemm3m: the stride-2 data gradient, all parity classes in one launch (pp_conv2d_nhwc_bwd_data_s2_bf16x3) ----
+// The grid is the classes' tile grids one behind the other (conv_plan.h: pp_s2_merge, heaviest class first).  A workgroup
+// compares its index with at most three prefix sums -- workgroup-uniform, scalar selects, no division --, takes that class's
+// geometry into its copy of the parameters and runs igemm3f's body on it: every tile runs the products the per-class launch
+// runs, in the same order, so the results are bit-identical to pp_conv2d_nhwc_bwd_data_bf16x3; a class without taps writes what
+// class_fill_kernel writes.  p: the whole gradient with the fields all classes share (sc_on, sc_H, sc_W, w_tstep = 2, div = 1).
+template <int TM, int TN, bool AP, bool OP>
+__global__ __launch_bounds__(256, (TM * TN >= 8) ? 2 : ((TM * TN == 4) ? 3 : 4)) void igemm3m_kernel(
+    const IgemmParams p0, const PpS2Merged g, const void* __restrict__ g_a0, const void* __restrict__ g_a1, unsigned a_bytes,
+    const void* __restrict__ g_whi, const void* __restrict__ g_wlo, unsigned w_bytes, const float* __restrict__ g_addend,
+    const float* __restrict__ g_mask, float* __restrict__ g_out, uint2* __restrict__ g_ohi, uint2* __restrict__ g_olo, int w_rows, int w_ld8) {
+  const int bid = (int)blockIdx.x;
+  PpS2Class c = g.c[0];
+#pragma unroll
+  for (int j = 1; j < 4; ++j)
+    if (j < g.n_cls && bid >= g.c[j].blk_begin) c = g.c[j];
+  IgemmParams p = p0;
+  p.n_seg = 1;  // (host-checked; as a constant it removes the level loop of decode_row, whose indexing would keep this copy in memory)
+  igemm_set_class(p, c);
+  igemm3f_body<TM, TN, AP, OP, true, false, true>(p, bid - c.blk_begin, c.tiles, g_a0, g_a1, a_bytes, g_whi, g_wlo, w_bytes, nullptr, g_addend, g_mask,
+                                                  g_out, g_ohi, g_olo, w_rows, w_ld8, 1, nullptr, nullptr, nullptr);
 }
 
 // ---- igemm3x: 3-wide stride-1 "same" convolutions with the gathered tile shared by the three taps of a kernel row ----
@@ -1501,6 +1541,28 @@ static void dispatch3(pp_ctx* ctx, IgemmParams& p, const Igemm3Args& a) {
   else launch_igemm3<1, 1>(ctx->stream, p, a, pl);
 }
 
+// the merged stride-2 data gradient: one launch on the route's tile (p: the shared fields of its classes)
+template <int TM, int TN>
+static void launch_igemm3m(hipStream_t st, IgemmParams& p, const Igemm3Args& a, const DgradS2Route& r) {
+  const dim3 grid(r.g.grid), wg(256);
+  const unsigned a_bytes = (unsigned)(p.src_rows * (long long)p.ld_src * 4), w_bytes = (unsigned)((long long)p.w_taps * a.w_rows * a.w_ld8 * 16);
+  p.n_tiles_n = r.pl.n_tiles_n;
+  if (a.ahi)
+    hipLaunchKernelGGL((igemm3m_kernel<TM, TN, true, true>), grid, wg, 0, st, p, r.g, a.ahi, a.alo, a_bytes, a.whi, a.wlo, w_bytes, p.addend, p.mask_src,
+                       p.out, (uint2*)a.ohi, (uint2*)a.olo, a.w_rows, a.w_ld8);
+  else
+    hipLaunchKernelGGL((igemm3m_kernel<TM, TN, false, false>), grid, wg, 0, st, p, r.g, (const void*)p.src, nullptr, a_bytes, a.whi, a.wlo, w_bytes,
+                       p.addend, p.mask_src, p.out, (uint2*)nullptr, (uint2*)nullptr, a.w_rows, a.w_ld8);
+}
+static void dispatch3m(pp_ctx* ctx, IgemmParams& p, const Igemm3Args& a, const DgradS2Route& r) {
+  pp_plan_debug(r.f, r.pl, r.g);
+  if (r.pl.tm == 4) launch_igemm3m<4, 2>(ctx->stream, p, a, r);
+  else if (r.pl.tm == 2 && r.pl.tn == 2) launch_igemm3m<2, 2>(ctx->stream, p, a, r);
+  else if (r.pl.tm == 1 && r.pl.tn == 2) launch_igemm3m<1, 2>(ctx->stream, p, a, r);
+  else if (r.pl.tm == 2 && r.pl.tn == 1) launch_igemm3m<2, 1>(ctx->stream, p, a, r);
+  else launch_igemm3m<1, 1>(ctx->stream, p, a, r);
+}
+
 // the launch over the listed 32-row blocks (tm: 2 = 128 x 128 tiles, 1 = 64 x 128)
 static void dispatch3_rowlist(pp_ctx* ctx, IgemmParams& p, const Igemm3Args& a, int tm, const unsigned char* dy_flags, unsigned char* out_flags,
                               int* out_list, bool fill) {
@@ -1623,40 +1685,42 @@ extern "C" int PP_API(pp_stem7x7s2_fwd_bf16x3)(pp_ctx* ctx, int n_img, int H, in
 }
 namespace {
 
-}  // namespace
-extern "C" int PP_API(pp_conv2d_nhwc_bwd_data_bf16x3)(pp_ctx* ctx, const pp_conv_desc* d, const float* dy, const void* dy_hi, const void* dy_lo,
-                                              const void* w_hi, const void* w_lo, const float* addend, int ld_add,
-                                              const float* relu_src, int ld_rs, float* dx, void* dx_hi, void* dx_lo,
-                                              const pp_conv_opts* opts) {
+// both data-gradient entry points (who): merged = pp_conv2d_nhwc_bwd_data_s2_bf16x3, which takes the epilogue planes as its only
+// options, launches igemm3m where its route applies and refuses every other call
+static int bwd_data_impl(pp_ctx* ctx, const char* who, bool merged, const pp_conv_desc* d, const float* dy, const void* dy_hi, const void* dy_lo,
+                         const void* w_hi, const void* w_lo, const float* addend, int ld_add, const float* relu_src, int ld_rs, float* dx,
+                         void* dx_hi, void* dx_lo, const pp_conv_opts* opts) {
   PP_REQUIRE_CTX(ctx);
-  int rc = pp_conv_opts_take(ctx, opts, PP_OPT_CAPTURE | PP_OPT_ADD | PP_OPT_MASK | PP_OPT_SKIP | PP_OPT_LAZY_OUT | PP_OPT_LAZY_IN,
-                             "pp_conv2d_nhwc_bwd_data_bf16x3");
+  int rc = pp_conv_opts_take(ctx, opts,
+                             merged ? (PP_OPT_ADD | PP_OPT_MASK)
+                                    : (PP_OPT_CAPTURE | PP_OPT_ADD | PP_OPT_MASK | PP_OPT_SKIP | PP_OPT_LAZY_OUT | PP_OPT_LAZY_IN),
+                             who);
   if (rc) return rc;
   void *const chi = opts->capture_hi, *const clo = opts->capture_lo;
   unsigned char* const skip_flags = opts->skip_flags;
   const bool skip_scratch_ok = skip_flags != nullptr && opts->skip_list != nullptr;
   const void *const ep_ah = opts->add_hi, *const ep_al = opts->add_lo, *const ep_mh = opts->mask_hi;
-  rc = check_desc(ctx, d, "pp_conv2d_nhwc_bwd_data_bf16x3");
+  rc = check_desc(ctx, d, who);
   PP_CHECK_ARG(ctx, !(ep_ah && addend) && !(ep_mh && relu_src), PP_ERR_ARG,
-               "pp_conv2d_nhwc_bwd_data_bf16x3: addend / relu_src given both as f32 and as planes");
+               "%s: addend / relu_src given both as f32 and as planes", who);
   PP_CHECK_ARG(ctx, (!ep_ah || (ld_add >= d->cin && ld_add % 4 == 0)) && (!ep_mh || (ld_rs >= d->cin && ld_rs % 4 == 0)), PP_ERR_SHAPE,
-               "pp_conv2d_nhwc_bwd_data_bf16x3: addend / relu_src planes");
+               "%s: addend / relu_src planes", who);
   if (rc) return rc;
-  PP_CHECK_ARG(ctx, !chi || (dy && !dy_hi && pp_is_packed(chi, clo)), PP_ERR_ARG, "pp_conv2d_nhwc_bwd_data_bf16x3: split capture needs the f32 operand");
-  PP_CHECK_ARG(ctx, (dy || (dy_hi && dy_lo)) && w_hi && w_lo && (dx || (dx_hi && dx_lo)), PP_ERR_ARG, "pp_conv2d_nhwc_bwd_data_bf16x3: null tensor");
-  PP_CHECK_ARG(ctx, (dy_hi == nullptr) == (dy_lo == nullptr) && d->ld_y % 8 == 0, PP_ERR_ARG, "pp_conv2d_nhwc_bwd_data_bf16x3: planes / ld_y");
+  PP_CHECK_ARG(ctx, !chi || (dy && !dy_hi && pp_is_packed(chi, clo)), PP_ERR_ARG, "%s: split capture needs the f32 operand", who);
+  PP_CHECK_ARG(ctx, (dy || (dy_hi && dy_lo)) && w_hi && w_lo && (dx || (dx_hi && dx_lo)), PP_ERR_ARG, "%s: null tensor", who);
+  PP_CHECK_ARG(ctx, (dy_hi == nullptr) == (dy_lo == nullptr) && d->ld_y % 8 == 0, PP_ERR_ARG, "%s: planes / ld_y", who);
   PP_CHECK_ARG(ctx, pp_is_packed(dy_hi, dy_lo) && pp_is_packed(dx_hi, dx_lo), PP_ERR_ALIGN,
-               "pp_conv2d_nhwc_bwd_data_bf16x3: planes must be packed (lo = hi + 16 bytes, 16-byte aligned)");
+               "%s: planes must be packed (lo = hi + 16 bytes, 16-byte aligned)", who);
   PP_CHECK_ARG(ctx, (!dx_hi || (d->cin % 8 == 0 && d->ld_x % 8 == 0)) && (!ep_ah || ld_add % 8 == 0) && (!ep_mh || ld_rs % 8 == 0), PP_ERR_SHAPE,
-               "pp_conv2d_nhwc_bwd_data_bf16x3: planes need channel counts and leading dimensions %% 8 == 0");
+               "%s: planes need channel counts and leading dimensions %% 8 == 0", who);
   const int cred = (d->cout + 31) / 32 * 32;
   PP_CHECK_ARG(ctx, d->cin % 16 == 0 && d->ld_y >= cred && d->ld_y % 4 == 0, PP_ERR_SHAPE,
-               "pp_conv2d_nhwc_bwd_data_bf16x3: dy needs ld_y >= %d (cout rounded up to 32, zero padded)", cred);
+               "%s: dy needs ld_y >= %d (cout rounded up to 32, zero padded)", who, cred);
   PP_CHECK_ARG(ctx, (!dy || pp_is_aligned16(dy)) && pp_is_aligned16(w_hi) && pp_is_aligned16(w_lo) && (!dx || pp_is_aligned16(dx)), PP_ERR_ALIGN,
-               "pp_conv2d_nhwc_bwd_data_bf16x3: tensors must be 16-byte aligned");
+               "%s: tensors must be 16-byte aligned", who);
   PP_CHECK_ARG(ctx, (!addend || (ld_add >= d->cin && ld_add % 4 == 0 && pp_is_aligned16(addend))) &&
                         (!relu_src || (ld_rs >= d->cin && ld_rs % 4 == 0 && pp_is_aligned16(relu_src))),
-               PP_ERR_SHAPE, "pp_conv2d_nhwc_bwd_data_bf16x3: addend / relu_src");
+               PP_ERR_SHAPE, "%s: addend / relu_src", who);
   IgemmParams p;
   memset(&p, 0, sizeof(p));
   p.src = dy; p.out = dx; p.bias = nullptr; p.addend = addend; p.mask_src = relu_src;
@@ -1665,16 +1729,27 @@ extern "C" int PP_API(pp_conv2d_nhwc_bwd_data_bf16x3)(pp_ctx* ctx, const pp_conv
   p.ld_add = ld_add; p.ld_mask = ld_rs;
   p.relu = 0;
   PP_CHECK_ARG(ctx, (dx_hi == nullptr) == (dx_lo == nullptr) && (!dx_hi || (d->ld_x % 4 == 0 && pp_is_aligned16(dx_hi) && pp_is_aligned16(dx_lo))),
-               PP_ERR_ARG, "pp_conv2d_nhwc_bwd_data_bf16x3: output planes");
+               PP_ERR_ARG, "%s: output planes", who);
   const Igemm3Args a = {dy_hi, dy_lo, w_hi, w_lo, d->cin, cred / 8, dx_hi, dx_lo, chi, clo, skip_flags, ctx->ws};
+  if (merged) {
+    DgradS2Route s2;
+    dgrad_s2_route(d, p, igemm3_facts(ctx, p, a), &s2);
+    PP_CHECK_ARG(ctx, s2.ok, PP_ERR_ARG,
+                 "%s: needs stride 2, one level, operands all float32 or all planes, and classes the branch-free loop can run "
+                 "(pp_conv2d_nhwc_bwd_data_bf16x3 takes every other call)", who);
+    IgemmParams q = s2.cls[0];  // (the fields the classes share; the kernel takes the rest from the class of each workgroup)
+    dispatch3m(ctx, q, a, s2);
+    PP_CHECK_LAUNCH(ctx, who);
+    return PP_OK;
+  }
   DgradRoute route;
   dgrad_route(d, p, igemm3_facts(ctx, p, a), skip_scratch_ok, &route);
   // Contract of the hint's scratch (pp_row_block_list_planes_within relies on it): after this call the second n_blocks bytes
   // of the flags buffer flag every 32-row block of dx that may hold a non-zero -- the dilated list when the listed launch
   // runs, everything otherwise.
   PP_CHECK_ARG(ctx, !opts->lazy_in || route.listed, PP_ERR_ARG,
-               "pp_conv2d_nhwc_bwd_data_bf16x3: dy was declared lazy (unwritten outside its flagged blocks) but the listed-block launch "
-               "does not apply to this call");
+               "%s: dy was declared lazy (unwritten outside its flagged blocks) but the listed-block launch "
+               "does not apply to this call", who);
   const int nb = (p.M + 31) / 32;
   if (skip_scratch_ok && !route.listed) PP_HIP(ctx, hipMemsetAsync(skip_flags + nb, 1, (size_t)nb, ctx->stream));
   const Igemm3Args ac = {dy_hi, dy_lo, w_hi, w_lo, d->cin, cred / 8, dx_hi, dx_lo, nullptr, nullptr, nullptr, ctx->ws};
@@ -1689,8 +1764,23 @@ extern "C" int PP_API(pp_conv2d_nhwc_bwd_data_bf16x3)(pp_ctx* ctx, const pp_conv
         hipLaunchKernelGGL(class_fill_kernel, dim3(pp_finish_blocks(q.M, q.Nout, pp_cus(ctx->n_cu))), dim3(256), 0, ctx->stream, q, addend, relu_src,
                            dx, dx_hi, dx_lo);
       });
-  PP_CHECK_LAUNCH(ctx, "pp_conv2d_nhwc_bwd_data_bf16x3");
+  PP_CHECK_LAUNCH(ctx, who);
   return PP_OK;
+}
+}  // namespace
+extern "C" int PP_API(pp_conv2d_nhwc_bwd_data_bf16x3)(pp_ctx* ctx, const pp_conv_desc* d, const float* dy, const void* dy_hi, const void* dy_lo,
+                                              const void* w_hi, const void* w_lo, const float* addend, int ld_add,
+                                              const float* relu_src, int ld_rs, float* dx, void* dx_hi, void* dx_lo,
+                                              const pp_conv_opts* opts) {
+  return bwd_data_impl(ctx, "pp_conv2d_nhwc_bwd_data_bf16x3", false, d, dy, dy_hi, dy_lo, w_hi, w_lo, addend, ld_add, relu_src, ld_rs, dx, dx_hi,
+                       dx_lo, opts);
+}
+extern "C" int PP_API(pp_conv2d_nhwc_bwd_data_s2_bf16x3)(pp_ctx* ctx, const pp_conv_desc* d, const float* dy, const void* dy_hi, const void* dy_lo,
+                                                 const void* w_hi, const void* w_lo, const float* addend, int ld_add,
+                                                 const float* relu_src, int ld_rs, float* dx, void* dx_hi, void* dx_lo,
+                                                 const pp_conv_opts* opts) {
+  return bwd_data_impl(ctx, "pp_conv2d_nhwc_bwd_data_s2_bf16x3", true, d, dy, dy_hi, dy_lo, w_hi, w_lo, addend, ld_add, relu_src, ld_rs, dx,
+                       dx_hi, dx_lo, opts);
 }
 namespace {
 

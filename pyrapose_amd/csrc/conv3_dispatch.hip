@@ -27,7 +27,9 @@ extern "C" int pp_row_block_dilate_fmt1(pp_ctx* ctx, const pp_conv_desc* d, cons
 extern "C" int pp_stem7x7s2_fwd_bf16x3_fmt0(pp_ctx* ctx, int n_img, int H, int W, int Hp, int Wp, const float* x4p, const void* w_hi, const void* w_lo, int cout, const float* bias, int relu, float* y, int ld_y);
 extern "C" int pp_stem7x7s2_fwd_bf16x3_fmt1(pp_ctx* ctx, int n_img, int H, int W, int Hp, int Wp, const float* x4p, const void* w_hi, const void* w_lo, int cout, const float* bias, int relu, float* y, int ld_y);
 extern "C" int pp_conv2d_nhwc_bwd_data_bf16x3_fmt0(pp_ctx* ctx, const pp_conv_desc* d, const float* dy, const void* dy_hi, const void* dy_lo, const void* w_dgrad_hi, const void* w_dgrad_lo, const float* addend, int ld_add, const float* relu_src, int ld_rs, float* dx, void* dx_hi, void* dx_lo, const pp_conv_opts* opts);
+extern "C" int pp_conv2d_nhwc_bwd_data_s2_bf16x3_fmt0(pp_ctx* ctx, const pp_conv_desc* d, const float* dy, const void* dy_hi, const void* dy_lo, const void* w_dgrad_hi, const void* w_dgrad_lo, const float* addend, int ld_add, const float* relu_src, int ld_rs, float* dx, void* dx_hi, void* dx_lo, const pp_conv_opts* opts);
 extern "C" int pp_conv2d_nhwc_bwd_data_bf16x3_fmt1(pp_ctx* ctx, const pp_conv_desc* d, const float* dy, const void* dy_hi, const void* dy_lo, const void* w_dgrad_hi, const void* w_dgrad_lo, const float* addend, int ld_add, const float* relu_src, int ld_rs, float* dx, void* dx_hi, void* dx_lo, const pp_conv_opts* opts);
+extern "C" int pp_conv2d_nhwc_bwd_data_s2_bf16x3_fmt1(pp_ctx* ctx, const pp_conv_desc* d, const float* dy, const void* dy_hi, const void* dy_lo, const void* w_dgrad_hi, const void* w_dgrad_lo, const float* addend, int ld_add, const float* relu_src, int ld_rs, float* dx, void* dx_hi, void* dx_lo, const pp_conv_opts* opts);
 extern "C" int pp_conv2d_nhwc_bwd_weight_bf16x3_fmt0(pp_ctx* ctx, const pp_conv_desc* d, const float* x, const float* dy, const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, float* dw, float* dbias, const pp_conv_opts* opts);
 extern "C" int pp_conv2d_nhwc_bwd_weight_bf16x3_fmt1(pp_ctx* ctx, const pp_conv_desc* d, const float* x, const float* dy, const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, float* dw, float* dbias, const pp_conv_opts* opts);
 
@@ -70,15 +72,20 @@ extern "C" int pp_stem7x7s2_fwd_bf16x3(pp_ctx* ctx, int n_img, int H, int W, int
 extern "C" int pp_conv2d_nhwc_bwd_data_bf16x3(pp_ctx* ctx, const pp_conv_desc* d, const float* dy, const void* dy_hi, const void* dy_lo, const void* w_dgrad_hi, const void* w_dgrad_lo, const float* addend, int ld_add, const float* relu_src, int ld_rs, float* dx, void* dx_hi, void* dx_lo, const pp_conv_opts* opts) {
   return (ctx && ctx->planes_fmt == 1) ? pp_conv2d_nhwc_bwd_data_bf16x3_fmt1(ctx, d, dy, dy_hi, dy_lo, w_dgrad_hi, w_dgrad_lo, addend, ld_add, relu_src, ld_rs, dx, dx_hi, dx_lo, opts) : pp_conv2d_nhwc_bwd_data_bf16x3_fmt0(ctx, d, dy, dy_hi, dy_lo, w_dgrad_hi, w_dgrad_lo, addend, ld_add, relu_src, ld_rs, dx, dx_hi, dx_lo, opts);
 }
+extern "C" int pp_conv2d_nhwc_bwd_data_s2_bf16x3(pp_ctx* ctx, const pp_conv_desc* d, const float* dy, const void* dy_hi, const void* dy_lo, const void* w_dgrad_hi, const void* w_dgrad_lo, const float* addend, int ld_add, const float* relu_src, int ld_rs, float* dx, void* dx_hi, void* dx_lo, const pp_conv_opts* opts) {
+  return (ctx && ctx->planes_fmt == 1) ? pp_conv2d_nhwc_bwd_data_s2_bf16x3_fmt1(ctx, d, dy, dy_hi, dy_lo, w_dgrad_hi, w_dgrad_lo, addend, ld_add, relu_src, ld_rs, dx, dx_hi, dx_lo, opts) : pp_conv2d_nhwc_bwd_data_s2_bf16x3_fmt0(ctx, d, dy, dy_hi, dy_lo, w_dgrad_hi, w_dgrad_lo, addend, ld_add, relu_src, ld_rs, dx, dx_hi, dx_lo, opts);
+}
 extern "C" int pp_conv2d_nhwc_bwd_weight_bf16x3(pp_ctx* ctx, const pp_conv_desc* d, const float* x, const float* dy, const void* x_hi, const void* x_lo, const void* dy_hi, const void* dy_lo, float* dw, float* dbias, const pp_conv_opts* opts) {
   return (ctx && ctx->planes_fmt == 1) ? pp_conv2d_nhwc_bwd_weight_bf16x3_fmt1(ctx, d, x, dy, x_hi, x_lo, dy_hi, dy_lo, dw, dbias, opts) : pp_conv2d_nhwc_bwd_weight_bf16x3_fmt0(ctx, d, x, dy, x_hi, x_lo, dy_hi, dy_lo, dw, dbias, opts);
 }
+
+extern "C" int pp_conv_s2_merged(void) { return pp_sw_s2_merged() ? 1 : 0; }
 
 // The plan of a call as text, without a context (include/pyrapose_hip.h): the facts come from the same functions the entry points
 // of conv3.hip use, the plans from conv_plan.h.
 extern "C" int pp_conv_plan_text(const pp_conv_desc* d, int pass, unsigned forms, int planes_fmt, int n_cu, size_t ws_bytes, char* buf,
                                  int buf_bytes) {
-  if (!buf || buf_bytes <= 0 || pass < PP_PLAN_FWD || pass > PP_PLAN_BWD_WEIGHT) return PP_ERR_ARG;
+  if (!buf || buf_bytes <= 0 || pass < PP_PLAN_FWD || pass > PP_PLAN_BWD_DATA_S2) return PP_ERR_ARG;
   const int rc = check_desc(nullptr, d, "pp_conv_plan_text");
   if (rc) return rc;
   const bool planes_in = forms & PP_PLAN_PLANES_IN, planes_out = forms & PP_PLAN_PLANES_OUT, f32_out = (forms & PP_PLAN_F32_OUT) || !planes_out,
@@ -111,6 +118,13 @@ extern "C" int pp_conv_plan_text(const pp_conv_desc* d, int pass, unsigned forms
   igemm_geometry_bwd_data(nullptr, d, p);
   const int w_rows = d->cin, w_ld8 = p.Cred / 8;
   const PpIgemmFacts f = igemm_facts(p, w_rows, w_ld8, planes_in, !planes_in, planes_out, f32_out, capture, list, n_cu, ws, (long long)ws_bytes);
+  if (pass == PP_PLAN_BWD_DATA_S2) {  // pp_conv2d_nhwc_bwd_data_s2_bf16x3: its options are the epilogue planes alone
+    DgradS2Route s2;
+    s2.ok = false;
+    if (!(forms & (PP_PLAN_LIST | PP_PLAN_LAZY_IN | PP_PLAN_LAZY_OUT))) dgrad_s2_route(d, p, f, &s2);
+    if (!s2.ok) return pp_plan_append(buf, buf_bytes, at, "igemm3 s2 refused: not a stride-2, one-level, all-f32 or all-planes data gradient\n");
+    return pp_plan_print(buf, buf_bytes, at, s2.f, s2.pl, s2.g, true);
+  }
   DgradRoute route;
   dgrad_route(d, p, f, list, &route);
   if (lazy_in && !route.listed) return pp_plan_append(buf, buf_bytes, at, "igemm3 refused: lazy dy without a listed-block launch\n");

@@ -262,24 +262,27 @@ static PpWgradFacts wgrad_facts(Wgrad3Params& p, bool planes, bool list, bool la
 // y' + (cy + pad_t - ty0)/2 - i.  The single-launch form spends 3/4 of its MFMAs on taps that the divisibility
 // mask zeroes; here every MFMA is useful and classes without taps (1x1 kernels) only run the epilogue.
 // p: the whole data gradient; false when a class does not meet igemm3f's conditions (the caller keeps the one launch).
+// the fields of a launch that differ between the parity classes (host: one launch per class; device: the merged launch, where
+// every workgroup takes the geometry of its own class)
+__host__ __device__ __forceinline__ void igemm_set_class(IgemmParams& r, const PpS2Class& c) {
+  r.kh = c.kh; r.kw = c.kw;
+  r.off_y = c.off_y; r.off_x = c.off_x;
+  r.w_ty0 = c.w_ty0; r.w_tx0 = c.w_tx0;
+  r.seg[0].OH = c.OH; r.seg[0].OW = c.OW;
+  r.M = c.M;
+  r.sc_cy = c.cy; r.sc_cx = c.cx;
+}
 static bool igemm_parity_classes(const pp_conv_desc* d, const IgemmParams& p, bool all_planes, IgemmParams cls[4]) {
   const int H = d->in.h[0], W = d->in.w[0];
+  PpS2Class geo[4];
+  pp_s2_classes(d->in.n_img, H, W, d->kh, d->kw, d->pad_t, d->pad_l, geo);
   for (int c = 0; c < 4; ++c) {
-    const int cy = c >> 1, cx = c & 1;
     IgemmParams& r = cls[c];
     r = p;
     r.div = 1;
-    const int ty0 = (cy + d->pad_t) & 1, tx0 = (cx + d->pad_l) & 1;
-    r.kh = ty0 < d->kh ? (d->kh - ty0 + 1) / 2 : 0;
-    r.kw = tx0 < d->kw ? (d->kw - tx0 + 1) / 2 : 0;
-    r.off_y = (cy + d->pad_t - ty0) / 2;
-    r.off_x = (cx + d->pad_l - tx0) / 2;
-    r.w_ty0 = ty0; r.w_tx0 = tx0; r.w_tstep = 2; r.w_kw = d->kw;
-    if (r.kh == 0 || r.kw == 0) r.kh = r.kw = 0;  // no taps: class_fill_kernel
-    r.seg[0].OH = (H - cy + 1) / 2;
-    r.seg[0].OW = (W - cx + 1) / 2;
-    r.M = d->in.n_img * r.seg[0].OH * r.seg[0].OW;
-    r.sc_on = 1; r.sc_H = H; r.sc_W = W; r.sc_cy = cy; r.sc_cx = cx;
+    r.w_tstep = 2; r.w_kw = d->kw;
+    igemm_set_class(r, geo[c]);  // (kh == 0: no taps -- class_fill_kernel, or the epilogue alone in the merged launch)
+    r.sc_on = 1; r.sc_H = H; r.sc_W = W;
     if (r.M > 0 && r.kh > 0 &&
         !(pp_igemm_fast_ok(igemm_facts(r, d->cin, r.Cred / 8, all_planes, !all_planes, all_planes, !all_planes, false, false, 0, false, 0)) && r.M < (1 << 24)))
       return false;
@@ -309,6 +312,33 @@ static void dgrad_route(const pp_conv_desc* d, const IgemmParams& p, const PpIge
   r->listed = pp_dgrad_listed_ok(rf);
   r->listed_tm = pp_conv_switches().sparse_dgrad == 22 ? 2 : 1;
   r->classes = pp_dgrad_classes_ok(rf) && igemm_parity_classes(d, p, all_planes, r->cls);
+}
+// The merged stride-2 data gradient (pp_conv2d_nhwc_bwd_data_s2_bf16x3, PP_PLAN_BWD_DATA_S2): the same classes in ONE launch.
+// Every class runs on the tile the planner gives the class with the most taps (f, pl: its facts and plan -- what the per-class
+// route launches it with); g: the concatenated grid.  p, f_all: the whole data gradient.  ok = false: the call is refused.
+struct DgradS2Route {
+  bool ok;
+  IgemmParams cls[4];
+  PpIgemmFacts f;
+  PpIgemmPlan pl;
+  PpS2Merged g;
+};
+static void dgrad_s2_route(const pp_conv_desc* d, const IgemmParams& p, const PpIgemmFacts& f_all, DgradS2Route* r) {
+  const bool all_f32 = f_all.f32_in && f_all.f32_out && !f_all.planes_in && !f_all.planes_out,
+             all_planes = f_all.planes_in && f_all.planes_out && !f_all.f32_out;
+  const PpDgradRouteFacts rf = {d->stride, d->kh, d->kw, d->pad_t, d->pad_l, d->in.n_seg, all_f32, all_planes, f_all.capture, p.bias != nullptr,
+                                f_all.flags, false, pp_igemm_fast_ok(f_all), f_all.same_grid};
+  r->ok = pp_dgrad_s2_ok(rf) && !f_all.capture && !f_all.flags && igemm_parity_classes(d, p, all_planes, r->cls);
+  if (!r->ok) return;
+  PpS2Class geo[4];
+  pp_s2_classes(d->in.n_img, d->in.h[0], d->in.w[0], d->kh, d->kw, d->pad_t, d->pad_l, geo);
+  const PpS2Merged order = pp_s2_merge(geo, 64, 64, p.Nout);  // (any tile: only the order is read)
+  const IgemmParams& heavy = r->cls[2 * order.c[0].cy + order.c[0].cx];
+  r->f = igemm_facts(heavy, f_all.w_rows, f_all.w_ld8, all_planes, !all_planes, all_planes, !all_planes, false, false, f_all.n_cu, f_all.ws,
+                     f_all.ws_bytes);
+  r->pl = pp_plan_igemm(r->f);
+  r->g = pp_s2_merge(geo, 64 * r->pl.tm, 64 * r->pl.tn, p.Nout);
+  r->ok = r->pl.family == PP_IGEMM3F_CLASS && r->pl.splits == 1 && order.c[0].kh > 0;
 }
 // the launches in order: gemm(params, is_class, listed) for every GEMM, fill(params) for a class without taps
 template <class Gemm, class Fill>

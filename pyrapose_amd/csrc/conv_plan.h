@@ -63,6 +63,10 @@ inline bool pp_sw_conv4p() { return pp_env_is1("PP_CONV4P"); }             // ig
 inline int pp_sw_conv4p_nst() { const char* e = getenv("PP_CONV4P_NST"); return e && atoi(e) == 3 ? 3 : 4; }
 inline int pp_sw_conv4p_splits() { return pp_env_int("PP_CONV4P_SPLITS", 0); }
 inline bool pp_sw_wgrad_det() { return pp_env_is1("PP_WGRAD3_DETERMINISTIC"); }
+// PP_CONV3_S2MERGED (on): the engine's stride-2 data gradients go through pp_conv2d_nhwc_bwd_data_s2_bf16x3 (one launch for all
+// parity classes); 0 = through pp_conv2d_nhwc_bwd_data_bf16x3 (one launch per class).  Read whenever a backward plan is built
+// (pp_conv_s2_merged): the A/B and the bit-identity test build both plans in one process.  Neither entry point looks at it.
+inline bool pp_sw_s2_merged() { return pp_env_not0("PP_CONV3_S2MERGED"); }
 // PP_WGRAD3R: -1 unset, else its first character's digit (0 / 1 / 2; anything else counts as 0)
 inline int pp_sw_wgrad3r() { const char* e = getenv("PP_WGRAD3R"); return !e ? -1 : ((e[0] == '1' || e[0] == '2') ? e[0] - '0' : 0); }
 // "tm,tn" tuning hooks (PP_CONV_TILE, PP_CONV3_TILE, PP_WGRAD3_TILE): the two characters, or false
@@ -124,11 +128,11 @@ struct PpIgemmFacts {
 
 enum PpIgemmFamily {
   PP_IGEMM3, PP_IGEMM3F, PP_IGEMM3F_CLASS, PP_IGEMM3X_CAPTURE, PP_IGEMM3X_PP, PP_IGEMM3X_PF, PP_IGEMM3X_FP, PP_IGEMM3X_FF, PP_IGEMM4X,
-  PP_IGEMM4X2, PP_IGEMM4P, PP_IGEMM3F_LIST
+  PP_IGEMM4X2, PP_IGEMM4P, PP_IGEMM3F_LIST, PP_IGEMM3F_S2
 };
 static const char* const pp_igemm_family_name[] = {
     "igemm3", "igemm3f", "igemm3f[parity class]", "igemm3x[capture]", "igemm3x[planes->planes]", "igemm3x[planes->f32]",
-    "igemm3x[f32->planes]", "igemm3x[f32->f32]", "igemm4x", "igemm4x<NWM=2>", "igemm4p", "igemm3f[row list]"};
+    "igemm3x[f32->planes]", "igemm3x[f32->f32]", "igemm4x", "igemm4x<NWM=2>", "igemm4p", "igemm3f[row list]", "igemm3f[stride-2 merged]"};
 
 struct PpIgemmPlan {
   int family;
@@ -399,6 +403,65 @@ inline bool pp_dgrad_classes_ok(const PpDgradRouteFacts& r) {
   return r.stride == 2 && pp_conv_switches().s2_classes && (r.all_f32 || r.all_planes) && r.n_seg == 1;
 }
 
+// ---- the parity classes of a stride-2 data gradient, and their merged launch (pp_conv2d_nhwc_bwd_data_s2_bf16x3) ----
+// Input cell (2y' + cy, 2x' + cx) only receives the taps ty = ty0 + 2i with ty0 = (cy + pad_t) & 1 (x alike), from output cell
+// y' + (cy + pad_t - ty0) / 2 - i: class (cy, cx) is a stride-1 gather of kh x kw taps over its own OH x OW grid.
+struct PpS2Class {
+  int cy, cx;                        // the class
+  int kh, kw;                        // its taps (0 x 0: none -- the class only runs the epilogue)
+  int off_y, off_x, w_ty0, w_tx0;    // gather offset; first weight tap (the weight taps step by 2)
+  int OH, OW, M;                     // the class grid; its rows over all images (0: the class does not exist)
+  int tiles, blk_begin;              // merged launch: workgroups of the class, and the first of them in the grid
+};
+// cls[2 * cy + cx]
+inline void pp_s2_classes(int n_img, int H, int W, int kh, int kw, int pad_t, int pad_l, PpS2Class cls[4]) {
+  for (int c = 0; c < 4; ++c) {
+    PpS2Class& r = cls[c];
+    r.cy = c >> 1;
+    r.cx = c & 1;
+    const int ty0 = (r.cy + pad_t) & 1, tx0 = (r.cx + pad_l) & 1;
+    r.kh = ty0 < kh ? (kh - ty0 + 1) / 2 : 0;
+    r.kw = tx0 < kw ? (kw - tx0 + 1) / 2 : 0;
+    r.off_y = (r.cy + pad_t - ty0) / 2;
+    r.off_x = (r.cx + pad_l - tx0) / 2;
+    r.w_ty0 = ty0;
+    r.w_tx0 = tx0;
+    if (r.kh == 0 || r.kw == 0) r.kh = r.kw = 0;
+    r.OH = (H - r.cy + 1) / 2;
+    r.OW = (W - r.cx + 1) / 2;
+    r.M = n_img * r.OH * r.OW;
+    r.tiles = r.blk_begin = 0;
+  }
+}
+// The merged launch: the tile grids of the classes that have rows, one behind the other, the class with the most taps first (4, 2,
+// 2, 1, 0 for a 3x3 kernel: the light tiles fill the last round); a workgroup finds its class by comparing its index with
+// c[1 ..].blk_begin.  Passed to the kernel by value.
+struct PpS2Merged {
+  int n_cls;
+  unsigned grid;
+  PpS2Class c[4];
+};
+inline PpS2Merged pp_s2_merge(const PpS2Class cls[4], int BM, int BN, int Nout) {
+  PpS2Merged g = {};
+  for (int c = 0; c < 4; ++c) {
+    if (cls[c].M <= 0) continue;
+    int at = g.n_cls++;
+    for (; at > 0 && g.c[at - 1].kh * g.c[at - 1].kw < cls[c].kh * cls[c].kw; --at) g.c[at] = g.c[at - 1];  // stable: ties keep class order
+    g.c[at] = cls[c];
+  }
+  const long long ntn = (Nout + BN - 1) / BN;
+  long long at = 0;
+  for (int i = 0; i < g.n_cls; ++i) {
+    g.c[i].tiles = (int)(((g.c[i].M + BM - 1) / BM) * ntn);
+    g.c[i].blk_begin = (int)at;
+    at += g.c[i].tiles;
+  }
+  g.grid = (unsigned)at;
+  return g;
+}
+// the route applies to what the per-class route applies to (the entry point refuses everything else: no fall-back)
+inline bool pp_dgrad_s2_ok(const PpDgradRouteFacts& r) { return r.stride == 2 && (r.all_f32 || r.all_planes) && r.n_seg == 1; }
+
 // ---- weight-gradient launches (conv3.hip: wgrad3 / wgrad3f, conv4.hip: wgrad3r / wgrad3w) ----
 struct PpWgradFacts {
   int M, Cin, Cout, kh, kw, stride, pad_t, pad_l, ld_src, ld_dy, ld_w;
@@ -618,10 +681,28 @@ inline int pp_plan_print(char* buf, int cap, int at, const PpWgradFacts& f, cons
                         pl.finish_blocks, pl.ws_need);
   return pp_plan_append(buf, cap, at, "\n");
 }
+// the merged stride-2 data gradient: f, pl = facts and plan of its heaviest class (the tile every class runs on)
+inline int pp_plan_print(char* buf, int cap, int at, const PpIgemmFacts& f, const PpIgemmPlan& pl, const PpS2Merged& g, bool detail) {
+  at = pp_plan_append(buf, cap, at, "igemm3 s2 N %d -> tile %dx%d, %d classes:", f.Nout, 64 * pl.tm, 64 * pl.tn, g.n_cls);
+  for (int i = 0; i < g.n_cls; ++i)
+    at = pp_plan_append(buf, cap, at, " (%d,%d) M %d steps %d", g.c[i].cy, g.c[i].cx, g.c[i].M, g.c[i].kh * g.c[i].kw * (f.Cred / 32));
+  at = pp_plan_append(buf, cap, at, " %s", pp_igemm_family_name[PP_IGEMM3F_S2]);
+  if (detail) {
+    at = pp_plan_append(buf, cap, at, " | grid=%u n_tiles_n=%d class_grids=", g.grid, pl.n_tiles_n);
+    for (int i = 0; i < g.n_cls; ++i) at = pp_plan_append(buf, cap, at, i ? "+%d" : "%d", g.c[i].tiles);
+  }
+  return pp_plan_append(buf, cap, at, "\n");
+}
 template <class Facts, class Plan>
 inline void pp_plan_debug(const Facts& f, const Plan& pl) {
   if (!pp_sw_debug()) return;
   char line[512];
   pp_plan_print(line, (int)sizeof(line), 0, f, pl, false);
+  fputs(line, stderr);
+}
+inline void pp_plan_debug(const PpIgemmFacts& f, const PpIgemmPlan& pl, const PpS2Merged& g) {
+  if (!pp_sw_debug()) return;
+  char line[512];
+  pp_plan_print(line, (int)sizeof(line), 0, f, pl, g, false);
   fputs(line, stderr);
 }

@@ -389,6 +389,7 @@ class Engine(object):
             self.prefix_lane = len(self.streams) - 1
         self.acts = OrderedDict()
         self._plane_grads = []
+        self._s2_grads = []  # (layer, Grad, route) of every stride-2 data gradient: "merged" (one launch) or "classes"
         self.step_count = 0
         self._build_forward()
         self.levels = arch.level_shapes(self.H, self.W, arch.PYRAMID_LEVELS[pyramid])
@@ -900,11 +901,25 @@ class Engine(object):
                     m_t, m_hi = (mask.t, None) if mask.t is not None else (None, mask.pl[0])
                 if gcap is not None:
                     assert dy_t is not None
-                self.bwd_ops.append(Op(lambda d=op["desc"], dy_t=dy_t, dy_pl=dy_pl, dh=pl["dg_hi"], dl=pl["dg_lo"], a_t=a_t, a_pl=a_pl, m_t=m_t,
-                                       m_hi=m_hi, out=out, gcap=gcap, sk=sk, lazy_out=lazy_out, lazy_in=lazy_in:
-                                       ops.conv_bwd_data3(ctx, d, dy_t, dh, dl, a_t, m_t, out.t, dy_pl, out.pl, gcap, sk, a_pl, m_hi,
-                                                          lazy_out=lazy_out, lazy_in=lazy_in), "conv_dgrad",
-                                       op["spec"].name, op["flops"]))
+                # stride 2: all parity classes in one launch where that entry point takes the call (the planner says so: all-f32 or
+                # all-planes operands, no capture, no row-block skip); PP_CONV3_S2MERGED=0 keeps the launch per class
+                forms = (ops.PLAN_PLANES_IN if dy_pl is not None else 0) | (ops.PLAN_PLANES_OUT if out.pl is not None else 0) | \
+                        (ops.PLAN_F32_OUT if out.t is not None else 0)
+                if (op["desc"].stride == 2 and gcap is None and sk is None and ops.conv_s2_merged()
+                        and "refused" not in ops.conv_plan_text(op["desc"], ops.PLAN_BWD_DATA_S2, forms, act.fmt)):
+                    self.bwd_ops.append(Op(lambda d=op["desc"], dy_t=dy_t, dy_pl=dy_pl, dh=pl["dg_hi"], dl=pl["dg_lo"], a_t=a_t, a_pl=a_pl, m_t=m_t,
+                                           m_hi=m_hi, out=out:
+                                           ops.conv_bwd_data3_s2(ctx, d, dy_t, dh, dl, a_t, m_t, out.t, dy_pl, out.pl, a_pl, m_hi), "conv_dgrad",
+                                           op["spec"].name, op["flops"]))
+                    self._s2_grads.append((op["spec"].name, out, "merged"))
+                else:
+                    if op["desc"].stride == 2:
+                        self._s2_grads.append((op["spec"].name, out, "classes"))
+                    self.bwd_ops.append(Op(lambda d=op["desc"], dy_t=dy_t, dy_pl=dy_pl, dh=pl["dg_hi"], dl=pl["dg_lo"], a_t=a_t, a_pl=a_pl, m_t=m_t,
+                                           m_hi=m_hi, out=out, gcap=gcap, sk=sk, lazy_out=lazy_out, lazy_in=lazy_in:
+                                           ops.conv_bwd_data3(ctx, d, dy_t, dh, dl, a_t, m_t, out.t, dy_pl, out.pl, gcap, sk, a_pl, m_hi,
+                                                              lazy_out=lazy_out, lazy_in=lazy_in), "conv_dgrad",
+                                           op["spec"].name, op["flops"]))
                 # a row-block-skip launch without addend leaves zeros (lazy: nothing at all) outside the blocks it flags in the second
                 # half of its scratch
                 out.within = sk[0][sk[0].numel() // 2:] if (sk is not None and acc is None and _os.environ.get("PP_SPARSE_WITHIN", "1") != "0") else None

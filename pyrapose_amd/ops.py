@@ -95,7 +95,7 @@ def make_conv_desc(n_img, in_shapes, out_shapes, cin, cout, k, stride, pad_t, pa
     return d
 
 
-PLAN_FWD, PLAN_BWD_DATA, PLAN_BWD_WEIGHT = 0, 1, 2
+PLAN_FWD, PLAN_BWD_DATA, PLAN_BWD_WEIGHT, PLAN_BWD_DATA_S2 = 0, 1, 2, 3
 PLAN_PLANES_IN, PLAN_PLANES_OUT, PLAN_F32_OUT, PLAN_CAPTURE, PLAN_LIST, PLAN_LAZY_IN, PLAN_LAZY_OUT = 1, 2, 4, 8, 16, 32, 64
 
 
@@ -360,6 +360,24 @@ def conv_bwd_data3(ctx, d, dy, w_hi, w_lo, addend, relu_src, dx, dy_planes=None,
                                              _conv_opts(capture=dy_capture, add=addend_planes, mask_hi=relu_src_hi, skip=dy_skip,
                                                         lazy_out=lazy_out, lazy_in=lazy_in)), ctx.handle,
           "pp_conv2d_nhwc_bwd_data_bf16x3")
+
+
+def conv_bwd_data3_s2(ctx, d, dy, w_hi, w_lo, addend, relu_src, dx, dy_planes=None, dx_planes=None, addend_planes=None, relu_src_hi=None):
+    """pp_conv2d_nhwc_bwd_data_s2_bf16x3: the stride-2 data gradient with all parity classes in one launch -- the operands of
+    conv_bwd_data3 (all float32 or all planes; no capture, no row-block skip) and bit for bit its result; any other call fails."""
+    ld_add = addend.stride(0) if addend is not None else (planes_ld(addend_planes) if addend_planes is not None else 0)
+    ld_rs = relu_src.stride(0) if relu_src is not None else (relu_src_hi.stride(0) // 2 if relu_src_hi is not None else 0)
+    dh, dl = dy_planes if dy_planes is not None else (None, None)
+    xh, xl = dx_planes if dx_planes is not None else (None, None)
+    check(lib.pp_conv2d_nhwc_bwd_data_s2_bf16x3(ctx.handle, C.byref(d), _ptr(dy), _ptr(dh), _ptr(dl), _ptr(w_hi), _ptr(w_lo), _ptr(addend),
+                                                ld_add, _ptr(relu_src), ld_rs, _ptr(dx), _ptr(xh), _ptr(xl),
+                                                _conv_opts(add=addend_planes, mask_hi=relu_src_hi)), ctx.handle,
+          "pp_conv2d_nhwc_bwd_data_s2_bf16x3")
+
+
+def conv_s2_merged():
+    """pp_conv_s2_merged: False under PP_CONV3_S2MERGED=0 (the Engine then keeps conv_bwd_data3 for its stride-2 data gradients)"""
+    return bool(lib.pp_conv_s2_merged())
 
 
 def conv_bwd_weight3(ctx, d, x, dy, dw, dbias, x_planes=None, dy_planes=None, dy_skip=None, lazy_in=False):
