@@ -216,30 +216,67 @@ def refine(R, t, X, uv, K4, mask, iters=10):
     return R, t
 
 
+def hypotheses(obj, img, K4, iterations, seed=0, problem=0, points_per_vote=8):
+    """stage 1 -> (float64 [iterations,12]: R row-major then t, samples): row `it` is all NaN where the kernel writes its NaN
+    marker (no sample possible, or a degenerate one); samples[it] is the index list of the sample, None when impossible.
+    A sample drawn twice (a vote met again after 'every vote once') is solved once: same input, same arithmetic."""
+    obj = np.asarray(obj, np.float64).reshape(-1, 3); img = np.asarray(img, np.float64).reshape(-1, 2)
+    n = obj.shape[0]
+    fx, fy, cx, cy = [float(v) for v in K4]
+    xn = np.stack([(img[:, 0] - cx) / fx, (img[:, 1] - cy) / fy], axis=1)
+    hyps = np.full((iterations, 12), np.nan)
+    samples, solved = [], {}
+    for it in range(iterations):
+        idx = sample(seed, problem, it, n, points_per_vote)
+        samples.append(idx)
+        if idx is None:
+            continue
+        key = tuple(idx)
+        if key not in solved:
+            hyp = dlt_pose(obj[idx], xn[idx])
+            if hyp is not None:
+                # the DLT ignores that [R|t] has 6 degrees of freedom: polish on the sample itself before scoring
+                R, t = refine(hyp[0], hyp[1], obj[idx], img[idx], (fx, fy, cx, cy), np.ones(len(idx), bool), iters=POLISH_ITERS)
+                hyp = np.concatenate([R.reshape(9), t])
+            solved[key] = hyp
+        if solved[key] is not None:
+            hyps[it] = solved[key]
+    return hyps, samples
+
+
+def score(hyps, obj, img, K4, reproj_error):
+    """stage 2 -> int [iterations]: points in front of the camera with squared reprojection error below reproj_error^2,
+    -1 for a NaN row"""
+    obj = np.asarray(obj, np.float64).reshape(-1, 3); img = np.asarray(img, np.float64).reshape(-1, 2)
+    K4 = tuple(float(v) for v in K4)
+    thr2 = float(reproj_error) ** 2
+    counts = np.full(len(hyps), -1, np.int64)
+    for it, h in enumerate(hyps):
+        if h[0] != h[0]:
+            continue
+        e, ok = reproj_sq(h[:9].reshape(3, 3), h[9:], obj, img, K4)
+        counts[it] = int((ok & (e < thr2)).sum())
+    return counts
+
+
+def winner(counts):
+    """the lowest iteration with the largest count; -1 when there is no iteration"""
+    counts = np.asarray(counts)
+    return int(np.argmax(counts)) if counts.size else -1
+
+
 def solve_pnp_ransac(obj, img, K4, iterations=300, reproj_error=5.0, seed=0, problem=0, points_per_vote=8):
     """obj [n,3], img [n,2] float64, K4 = (fx, fy, cx, cy) -> (ok, R [3,3], t [3], inlier mask [n] bool)"""
     obj = np.asarray(obj, np.float64); img = np.asarray(img, np.float64)
     n = obj.shape[0]
     fx, fy, cx, cy = [float(v) for v in K4]
-    xn = np.stack([(img[:, 0] - cx) / fx, (img[:, 1] - cy) / fy], axis=1)
     thr2 = float(reproj_error) ** 2
-    best = (-1, -1, None, None)
-    for it in range(iterations):
-        idx = sample(seed, problem, it, n, points_per_vote)
-        if idx is None:
-            break
-        hyp = dlt_pose(obj[idx], xn[idx])
-        if hyp is None:
-            continue
-        # the DLT ignores that [R|t] has 6 degrees of freedom: polish on the sample itself before scoring
-        R, t = refine(hyp[0], hyp[1], obj[idx], img[idx], (fx, fy, cx, cy), np.ones(len(idx), bool), iters=POLISH_ITERS)
-        e, ok = reproj_sq(R, t, obj, img, (fx, fy, cx, cy))
-        cnt = int((ok & (e < thr2)).sum())
-        if cnt > best[0]:
-            best = (cnt, it, R, t)
-    if best[0] < 4:
+    hyps, _ = hypotheses(obj, img, (fx, fy, cx, cy), iterations, seed, problem, points_per_vote)
+    counts = score(hyps, obj, img, (fx, fy, cx, cy), reproj_error)
+    best = winner(counts)
+    if best < 0 or counts[best] < 4:
         return False, np.eye(3), np.zeros(3), np.zeros(n, bool)
-    _, _, R, t = best
+    R, t = hyps[best, :9].reshape(3, 3), hyps[best, 9:]
     for _ in range(2):
         e, ok = reproj_sq(R, t, obj, img, (fx, fy, cx, cy))
         mask = ok & (e < thr2)
