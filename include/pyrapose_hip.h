@@ -858,7 +858,25 @@ int pp_vote_cluster(pp_ctx* ctx, int batch, int n, int n_class, int cap, const f
  *   index [n_model,k] int32: the picks as indices WITHIN their model.  Fixed order: bit-identical run to run.
  *   Errors before anything is launched: n_model, n_total or k < 1, an empty model, k > a model's size under rule 0:
  *   PP_ERR_SHAPE; null pointers (min_dist may be NULL under rule 0), rule outside {0, 1}, offsets that decrease or do not run
- *   from 0 to n_total, workspace_bytes < pp_farthest_points_workspace_bytes(n_total): PP_ERR_ARG. */
+ *   from 0 to n_total, workspace_bytes < pp_farthest_points_workspace_bytes(n_total): PP_ERR_ARG.
+ *
+ * pp_sym_hausdorff_f64: how far each of n_cand rigid transformations moves a point set off a target set -- the score behind
+ *   utils.model_info.find_symmetries / symmetry_residuals (the 'symmetries_discrete' / 'symmetries_continuous' entries of
+ *   models_info).  src [n_src,3], tgt [n_tgt,3] (may be the same pointer), S_R [n_cand,3,3] row-major, S_t [n_cand,3]; for
+ *   every candidate k
+ *     d2 [k]     = max over i of min over j of d2(S_k src_i, tgt_j), the SQUARED one-sided Hausdorff distance of the moved
+ *                  source to the target; S_k p = R[0] x + R[1] y + R[2] z + t[0] (and rows 1, 2), summed left to right as the
+ *                  pose errors move a point; the root is the host's
+ *     arg [k,2]  = int32 (i, j): the lowest i that attains the maximum, and for that i the lowest j that attains its minimum.
+ *   Points past n_src / n_tgt take no part (a partial tile's tail is not a set of zero points).  Maxima and minima only, no
+ *   float atomics: bit-identical to the numpy restatement (tests/model_sym_np.py) and run to run.  All n_cand n_src n_tgt pairs
+ *   are visited in one launch plus one finish launch.  Inputs must be finite.
+ *   Errors before anything is launched: n_src or n_tgt outside 1..2^24, n_cand outside 1..65535: PP_ERR_SHAPE; null pointers,
+ *   workspace_bytes < pp_sym_hausdorff_workspace_bytes(n_src, n_cand) (0: bad n_src or n_cand): PP_ERR_ARG.
+ *   Parity with any dataset's hand-annotated symmetries is unpinned: no dataset was at hand. */
+size_t pp_sym_hausdorff_workspace_bytes(int n_src, int n_cand);
+int pp_sym_hausdorff_f64(pp_ctx* ctx, int n_src, const double* src, int n_tgt, const double* tgt, int n_cand, const double* S_R,
+                         const double* S_t, void* workspace, size_t workspace_bytes, double* d2, int* arg);
 size_t pp_pts_diameter_workspace_bytes(int n);
 int pp_pts_diameter_f64(pp_ctx* ctx, int n, const double* pts, void* workspace, size_t workspace_bytes, double* d2, int* pair);
 size_t pp_farthest_points_workspace_bytes(int n_total);

@@ -211,6 +211,8 @@ _SIGS = {
     "pp_pts_diameter_f64": (_i, [_p, _i, _p, _p, _sz, _p, _p]),
     "pp_farthest_points_workspace_bytes": (_sz, [_i]),
     "pp_farthest_points_f64": (_i, [_p, _i, _i, _p, C.POINTER(_i), _p, _i, _i, _p, _p, _p, _sz, _p]),
+    "pp_sym_hausdorff_workspace_bytes": (_sz, [_i, _i]),
+    "pp_sym_hausdorff_f64": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _sz, _p, _p]),
     "pp_det_match": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, C.POINTER(_i), _p, _i, C.POINTER(_d), _i, _p, _p, _p]),
     "pp_det_pr_curve": (_i, [_p, _i, _i, _i, _ll, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pp_det_ap": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p]),

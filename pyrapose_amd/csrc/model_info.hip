@@ -4,6 +4,8 @@
 //   d2(a, b) = (dx * dx + dy * dy) + dz * dz       with exactly that association (numpy's (diff * diff).sum(axis=1) on rows of 3)
 //   diameter: max over i <= j of d2(p_i, p_j), the pair that attains it (lowest i, then lowest j); the root is the host's
 //   farthest points: k greedy picks per model, argmax of a running score, the lowest index on ties
+//   symmetry score: per candidate transformation S_k, max over i of min over j of d2(S_k p_i, q_j) -- the squared one-sided
+//   Hausdorff distance of the moved source to the target -- and the (i, j) that attains it (lowest i, for it the lowest j)
 // Maxima, minima and (rule 1) sums in the order chosen: results do not depend on timing.
 // Compiled with -ffp-contract=off: products and sums are rounded one by one as written.
 #include "pose_common.h"
@@ -147,6 +149,158 @@ extern "C" int pp_pts_diameter_f64(pp_ctx* ctx, int n, const double* pts, void* 
   hipLaunchKernelGGL(diameter_finish_kernel, dim3(1), dim3(POSE_TILE), 0, ctx->stream, (long long)n_part, (const double*)part_d2,
                      (const int2*)part_ij, d2, pair);
   PP_CHECK_LAUNCH(ctx, "pp_pts_diameter_f64");
+  return PP_OK;
+}
+
+// ---- symmetry score: one-sided Hausdorff distance of a moved point set ------------------------------------------------------
+// d2[k] = max_i min_j d2(S_k src_i, tgt_j).  Workgroup (tile, chunk) holds one source tile, one point per thread, moved once by
+// each of the chunk's SYM_HD_CHUNK candidates (pose.hip's rigid() association) in registers, and sweeps ALL target tiles staged
+// in LDS one at a time (broadcast reads: the three loads of a target point serve SYM_HD_CHUNK pairs).  The sweep keeps the
+// running minimum only; partial[k][tile] = (the tile's largest minimum, the lowest i that has it).  Tail lanes (i >= n_src) hold
+// no point: their minimum counts as -1, below every squared distance.  Tail entries of a target tile are never read.  A last
+// chunk with fewer candidates repeats its last one in the spare slots and drops their results.
+// The finish, one workgroup per candidate: the partials in a fixed order (lowest i on ties), then for that one source point the
+// lowest j whose d2 EQUALS the minimum -- the same operations on the same operands give the same bits.
+
+#define SYM_HD_CHUNK 4
+#define SYM_HD_MAX_CAND 65535
+
+__device__ __forceinline__ void rigid3(const double* __restrict__ R, const double* __restrict__ t, double x, double y, double z, double* ox,
+                                       double* oy, double* oz) {  // pose.hip's rigid(): left to right
+  *ox = R[0] * x + R[1] * y + R[2] * z + t[0];
+  *oy = R[3] * x + R[4] * y + R[5] * z + t[1];
+  *oz = R[6] * x + R[7] * y + R[8] * z + t[2];
+}
+
+__global__ void __launch_bounds__(POSE_TILE)
+sym_hausdorff_tile_kernel(int n_src, int n_tgt, int n_cand, const double* __restrict__ src, const double* __restrict__ tgt,
+                          const double* __restrict__ S_R, const double* __restrict__ S_t, double* __restrict__ part_d2,
+                          int* __restrict__ part_i) {
+  __shared__ double s[3 * POSE_TILE];
+  __shared__ double red[SYM_HD_CHUNK * (POSE_TILE / 64)];
+  __shared__ unsigned long long key[SYM_HD_CHUNK];
+  const int tid = threadIdx.x, tile = blockIdx.x, k0 = blockIdx.y * SYM_HD_CHUNK;
+  const int nk = min(SYM_HD_CHUNK, n_cand - k0);  // >= 1: the grid has ceil(n_cand / SYM_HD_CHUNK) chunks
+  const int i = tile * POSE_TILE + tid;
+  const bool mine = i < n_src;
+  double mx[SYM_HD_CHUNK], my[SYM_HD_CHUNK], mz[SYM_HD_CHUNK], best[SYM_HD_CHUNK];
+  {
+    double x = 0.0, y = 0.0, z = 0.0;
+    if (mine) {
+      x = src[3 * (size_t)i];
+      y = src[3 * (size_t)i + 1];
+      z = src[3 * (size_t)i + 2];
+    }
+#pragma unroll
+    for (int k = 0; k < SYM_HD_CHUNK; ++k) {
+      const int kk = k0 + min(k, nk - 1);
+      rigid3(S_R + 9 * (size_t)kk, S_t + 3 * (size_t)kk, x, y, z, &mx[k], &my[k], &mz[k]);
+      best[k] = __builtin_inf();
+    }
+  }
+  for (int j0 = 0; j0 < n_tgt; j0 += POSE_TILE) {
+    const int lim = min(POSE_TILE, n_tgt - j0);
+    __syncthreads();
+    for (int e = tid; e < 3 * lim; e += POSE_TILE) s[e] = tgt[3 * (size_t)j0 + e];
+    __syncthreads();
+    if (mine) {
+#pragma unroll 4
+      for (int j = 0; j < lim; ++j) {
+        const double qx = s[3 * j], qy = s[3 * j + 1], qz = s[3 * j + 2];
+#pragma unroll
+        for (int k = 0; k < SYM_HD_CHUNK; ++k) {
+          const double q = dist2(mx[k], my[k], mz[k], qx, qy, qz);
+          best[k] = q < best[k] ? q : best[k];
+        }
+      }
+    }
+  }
+  double m[SYM_HD_CHUNK];
+#pragma unroll
+  for (int k = 0; k < SYM_HD_CHUNK; ++k) {
+    best[k] = mine ? best[k] : -1.0;
+    m[k] = best[k];
+  }
+  if (tid < SYM_HD_CHUNK) key[tid] = ~0ull;
+  tile_max256(m, red);  // (its barriers order the reset of key before the minima below)
+#pragma unroll
+  for (int k = 0; k < SYM_HD_CHUNK; ++k)
+    if (mine && best[k] == m[k]) atomicMin(&key[k], (unsigned long long)(unsigned)i);
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int k = 0; k < SYM_HD_CHUNK; ++k)
+      if (k < nk) {
+        const size_t slot = (size_t)(k0 + k) * gridDim.x + tile;
+        part_d2[slot] = m[k];
+        part_i[slot] = (int)key[k];  // (every tile has a point: some lane set the key)
+      }
+  }
+}
+
+// grid (candidates): the candidate's partials, tile by tile -> d2, the lowest i that attains it, then the lowest j of that i
+__global__ void __launch_bounds__(POSE_TILE)
+sym_hausdorff_finish_kernel(int n_tgt, int tiles, const double* __restrict__ src, const double* __restrict__ tgt,
+                            const double* __restrict__ S_R, const double* __restrict__ S_t, const double* __restrict__ part_d2,
+                            const int* __restrict__ part_i, double* __restrict__ d2, int* __restrict__ arg) {
+  __shared__ double red[POSE_TILE / 64];
+  __shared__ unsigned long long key;
+  const int tid = threadIdx.x, k = blockIdx.x;
+  double best = -1.0;
+  int bi = 0, none = 0;
+  for (int t = tid; t < tiles; t += POSE_TILE) {  // rising tiles hold rising i: a strict comparison keeps the lowest
+    const double q = part_d2[(size_t)k * tiles + t];
+    if (q > best) {
+      best = q;
+      bi = part_i[(size_t)k * tiles + t];
+    }
+  }
+  best_pair256(best, bi, none, red, &key);
+  double x, y, z;
+  rigid3(S_R + 9 * (size_t)k, S_t + 3 * (size_t)k, src[3 * (size_t)bi], src[3 * (size_t)bi + 1], src[3 * (size_t)bi + 2], &x, &y, &z);
+  if (tid == 0) key = ~0ull;
+  __syncthreads();
+  for (int j = tid; j < n_tgt; j += POSE_TILE)
+    if (dist2(x, y, z, tgt[3 * (size_t)j], tgt[3 * (size_t)j + 1], tgt[3 * (size_t)j + 2]) == best) {
+      atomicMin(&key, (unsigned long long)(unsigned)j);
+      break;  // this thread's further j are higher
+    }
+  __syncthreads();
+  if (tid == 0) {
+    d2[k] = best;
+    arg[2 * k] = bi;
+    arg[2 * k + 1] = key == ~0ull ? 0 : (int)key;  // (no j equals the minimum only when it is NaN)
+  }
+}
+
+static inline size_t sym_hausdorff_partials(int n_src, int n_cand) { return (size_t)n_cand * diameter_tiles(n_src); }
+
+extern "C" size_t pp_sym_hausdorff_workspace_bytes(int n_src, int n_cand) {
+  if (n_src <= 0 || n_src > DIAMETER_MAX_PTS || n_cand <= 0 || n_cand > SYM_HD_MAX_CAND) return 0;
+  return pp_align256(sym_hausdorff_partials(n_src, n_cand) * sizeof(double)) + sym_hausdorff_partials(n_src, n_cand) * sizeof(int);
+}
+
+extern "C" int pp_sym_hausdorff_f64(pp_ctx* ctx, int n_src, const double* src, int n_tgt, const double* tgt, int n_cand, const double* S_R,
+                                    const double* S_t, void* workspace, size_t workspace_bytes, double* d2, int* arg) {
+  PP_REQUIRE_CTX(ctx);
+  PP_CHECK_ARG(ctx, n_src >= 1 && n_src <= DIAMETER_MAX_PTS && n_tgt >= 1 && n_tgt <= DIAMETER_MAX_PTS, PP_ERR_SHAPE,
+               "pp_sym_hausdorff_f64: need 1..%d source and 1..%d target points, got %d and %d", DIAMETER_MAX_PTS, DIAMETER_MAX_PTS, n_src,
+               n_tgt);
+  PP_CHECK_ARG(ctx, n_cand >= 1 && n_cand <= SYM_HD_MAX_CAND, PP_ERR_SHAPE, "pp_sym_hausdorff_f64: need 1..%d candidates, got %d",
+               SYM_HD_MAX_CAND, n_cand);
+  PP_CHECK_ARG(ctx, src && tgt && S_R && S_t && workspace && d2 && arg, PP_ERR_ARG, "pp_sym_hausdorff_f64: null argument");
+  PP_CHECK_ARG(ctx, workspace_bytes >= pp_sym_hausdorff_workspace_bytes(n_src, n_cand), PP_ERR_ARG,
+               "pp_sym_hausdorff_f64: workspace of %zu bytes, need %zu (pp_sym_hausdorff_workspace_bytes)", workspace_bytes,
+               pp_sym_hausdorff_workspace_bytes(n_src, n_cand));
+  const int tiles = diameter_tiles(n_src), chunks = (n_cand + SYM_HD_CHUNK - 1) / SYM_HD_CHUNK;
+  const size_t n_part = sym_hausdorff_partials(n_src, n_cand);
+  double* part_d2 = (double*)workspace;
+  int* part_i = (int*)((char*)workspace + pp_align256(n_part * sizeof(double)));
+  hipLaunchKernelGGL(sym_hausdorff_tile_kernel, dim3(tiles, chunks), dim3(POSE_TILE), 0, ctx->stream, n_src, n_tgt, n_cand, src, tgt, S_R, S_t,
+                     part_d2, part_i);
+  hipLaunchKernelGGL(sym_hausdorff_finish_kernel, dim3(n_cand), dim3(POSE_TILE), 0, ctx->stream, n_tgt, tiles, src, tgt, S_R, S_t,
+                     (const double*)part_d2, (const int*)part_i, d2, arg);
+  PP_CHECK_LAUNCH(ctx, "pp_sym_hausdorff_f64");
   return PP_OK;
 }
 

@@ -1245,6 +1245,29 @@ def farthest_points(ctx, pts, offsets, k, rule="min", min_dist=None, start=None)
     return index
 
 
+SYM_HD_CHUNK = 4       # candidates per workgroup of pp_sym_hausdorff_f64: a staged target point serves this many pairs per thread
+SYM_HD_MAX_CAND = 65535  # candidates per launch
+
+
+def sym_hausdorff(ctx, src, tgt, S_R, S_t):
+    """How far each of K rigid transformations moves src off tgt (pp_sym_hausdorff_f64): cuda float64 src [n,3], tgt [m,3] or
+    None (= src), S_R [K,3,3], S_t [K,3] -> (d2 float64 [K] = max_i min_j of (dx dx + dy dy) + dz dz between S_k src_i and
+    tgt_j, arg int32 [K,2] = the lowest i that attains the maximum and for it the lowest j that attains the minimum).  The
+    distance is math.sqrt(d2) on the host.  1 <= n, m <= 2^24, 1 <= K <= 65535; all K n m pairs are visited in one launch."""
+    src = _arg("sym_hausdorff", "src", src, _F64, (None, 3))
+    tgt = src if tgt is None else _arg("sym_hausdorff", "tgt", tgt, _F64, (None, 3))
+    S_R = _arg("sym_hausdorff", "S_R", S_R, _F64, (None, 3, 3))
+    K = int(S_R.shape[0])
+    S_t = _arg("sym_hausdorff", "S_t", S_t, _F64, (K, 3))
+    n, m = int(src.shape[0]), int(tgt.shape[0])
+    nbytes = lib.pp_sym_hausdorff_workspace_bytes(n, K)
+    ws = _workspace(nbytes)
+    d2, arg = _out(src, (K,)), _out(src, (K, 2), _I32)
+    check(lib.pp_sym_hausdorff_f64(ctx.handle, n, _ptr(src), m, _ptr(tgt), K, _ptr(S_R), _ptr(S_t), _ptr(ws), nbytes, _ptr(d2), _ptr(arg)),
+          ctx.handle, "pp_sym_hausdorff_f64")
+    return d2, arg
+
+
 DET_RULES = {"reference": 0, "coco": 1}       # PP_DET_RULE_*
 DET_INTEGRATIONS = {"area": 0, "101": 1}      # PP_DET_AP_*
 DET_MAX_THR = 16      # thresholds per pp_det_match launch (one wave each)
