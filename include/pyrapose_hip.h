@@ -966,6 +966,43 @@ int pp_det_pr_curve(pp_ctx* ctx, int n_thr, int n_order, int n_class, long long 
 int pp_det_ap(pp_ctx* ctx, int n_thr, int n_order, int n_class, const int* class_offsets, const int* npos, const double* recall,
               const double* prec_env, int mode, double* ap, double* recall_final);
 
+/* ---- normal images from depth maps (csrc/depth_image.hip) ----------------------------------------------------------------
+ * The reference's get_normal (annotation_scripts/Augmentations.py:394-467, copied into its annotate_* / augment_* scripts):
+ * the surface-normal image it writes as every sample's _dep.png, and the smoothed depth.  float64 from the first filter tap on,
+ * every product, sum and quotient rounded on its own; maxima by integer atomics on the bits of non-negative doubles, no float
+ * atomics: bit-identical to the numpy restatement (tests/depth_normals_np.py) and run to run.  Pinned to the reference's own
+ * function through tests/golden/depth_normals.npz wherever its smoothed depth is not exactly 0 (there its cross product of two
+ * parallel tangents is rounding noise).  Its three-value variants with cv2.inpaint are not covered.
+ *
+ * pp_depth_normals_f64: n_img images in one call (the batch rides on a grid dimension).
+ *   in   depth [n,H,W] float32 (device), finite and >= 0 (NaN is not handled); intr [n,3] float64 (device) = (fx, cx, cy) per
+ *        image -- fy takes no part, as in the reference; fx != 0 and |x - cx|, |y - cy| < 32768 (the reference's int16 table is
+ *        not wrapped); taps [17] float64 on the HOST: the weights exp(-x^2 / 8) / sum of
+ *        scipy.ndimage.gaussian_filter(depth, 2), each in (0, 1), from the caller so that it and its check share one exp.
+ *   1. d = the separable filter, rows (axis 0) then columns, border mode 'reflect' (d c b a | a b c d, mirrored again and again
+ *      where a line is shorter than the radius 8); a pass adds its 17 products onto the first one in increasing tap index.
+ *   2. u = trunc(x - cx), v = trunc(y - cy) toward zero, c = 1 / fx; (gy, gx) = np.gradient(d, 2, edge_order=2): (d[i+1] -
+ *      d[i-1]) / 4 inside, (-0.75 d[0] + d[1]) - 0.25 d[2] and (0.25 d[-3] - d[-2]) + 0.75 d[-1] on the first and last line.
+ *   3. v_x = (d c + (u c) gx, (v c) gx, gx), v_y = ((u c) gy, d c + (v c) gy, gy), n = v_x x v_y (each component a difference
+ *      of two products), n / sqrt((n0 n0 + n1 n1) + n2 n2), NaN -> 0 and +-inf -> +-DBL_MAX (np.nan_to_num), 0 where d > 2000.
+ *   out  each may be NULL (skipped), at least one must not be:
+ *        signed_f64 [n,H,W,3]         that n;  normals_f64 [n,H,W,3] its absolute value (what for_vis = 1 returns first)
+ *        depth_smoothed_f64 [n,H,W]   d (for_vis = 1) or d s (for_vis = 0), the reference's second return value
+ *        normals_u8 [n,H,W,3]         for_vis = 0 only (PP_ERR_ARG with for_vis = 1): with s = 1 / max d and
+ *                                     m = n (1 - (d s - 0.5)), trunc(m (255 / max m)); both maxima per image, max m over all
+ *                                     three components
+ *   Degenerate images: where an image's max d or max m is 0 the reference divides by zero; here that image's normals_u8 and
+ *   depth_smoothed_f64 (for_vis = 0) are all zero.
+ *   Launches: smooth (one launch, both passes from an LDS tile of 32 x 32 pixels with an 8-pixel halo), normals, and for
+ *   for_vis = 0 an encode pass that recomputes the normal instead of storing it; d is kept in the workspace.
+ *   Errors before anything is launched: n_img outside 1..65535, H or W outside 3..16384, n_img H W >= 2^31: PP_ERR_SHAPE; null
+ *   depth / intr / taps / workspace, no output, a tap outside (0, 1), for_vis outside {0, 1}, workspace_bytes <
+ *   pp_depth_normals_workspace_bytes(n_img, H, W) (0: a refused shape): PP_ERR_ARG. */
+size_t pp_depth_normals_workspace_bytes(int n_img, int H, int W);
+int pp_depth_normals_f64(pp_ctx* ctx, int n_img, int H, int W, const float* depth, const double* intr, const double* taps_host,
+                         int for_vis, void* workspace, size_t workspace_bytes, double* normals_f64, unsigned char* normals_u8,
+                         double* depth_smoothed_f64, double* signed_f64);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1406,3 +1406,43 @@ def det_ap(ctx, class_offsets, npos, recall, prec_env, integration="area", check
     check_status(lib.pp_det_ap(ctx.handle, T, N, n_class, _ptr(class_offsets), _ptr(npos), _ptr(recall), _ptr(prec_env),
                                DET_INTEGRATIONS[integration], _ptr(ap), _ptr(rf)), ctx.handle, "pp_det_ap")
     return ap, rf
+
+
+DEPTH_NORMALS_TILE = 32   # pixels per edge of the LDS tile of pp_depth_normals_f64's smoothing launch (its halo: 8 more on every side)
+DEPTH_NORMALS_OUTPUTS = {"normals": (_F64, (3,)), "normals_u8": (_U8, (3,)), "depth": (_F64, ()), "signed": (_F64, (3,))}  # in the ABI's order
+
+
+def gaussian_taps(sigma=2.0, truncate=4.0):
+    """The weights of scipy.ndimage.gaussian_filter(x, sigma) as a float64 host array: exp(-x^2 / (2 sigma^2)) over
+    x = -r..r, r = int(truncate sigma + 0.5), divided by their sum.  pp_depth_normals_f64 takes them from here, so that the
+    library and whoever restates it share one exp."""
+    r = int(truncate * float(sigma) + 0.5)
+    x = np.arange(-r, r + 1)
+    w = np.exp(-0.5 / (float(sigma) * float(sigma)) * x ** 2)
+    return w / w.sum()
+
+
+def depth_normals(ctx, depth, intr, for_vis=True, want=("normals", "depth")):
+    """The reference's get_normal on n depth images (pp_depth_normals_f64): cuda tensors depth float32 [n,H,W] (finite, >= 0),
+    intr float64 [n,3] = (fx, cx, cy) per image (the reference ignores fy); want: any of 'normals' (float64 [n,H,W,3], |unit
+    normal|, 0 where the smoothed depth exceeds 2000), 'signed' (the same before abs), 'depth' (float64 [n,H,W], the smoothed
+    depth; divided by its per-image maximum when for_vis is False) and, with for_vis False only, 'normals_u8' (uint8 [n,H,W,3],
+    the image the reference writes as _dep.png) -> dict of the requested outputs.  An image whose smoothed depth, or whose
+    scaled normal image, is all zero gives an all-zero 'normals_u8' and 'depth' under for_vis False."""
+    what = "depth_normals"
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(o not in DEPTH_NORMALS_OUTPUTS for o in want):
+        raise ValueError("%s: want must name at least one of %s, got %r" % (what, " | ".join(DEPTH_NORMALS_OUTPUTS), want))
+    if for_vis and "normals_u8" in want:
+        raise ValueError("%s: 'normals_u8' is an output of for_vis=False" % what)
+    depth = _arg(what, "depth", depth, _F32, (None, None, None))
+    n, H, W = (int(s) for s in depth.shape)
+    intr = _arg(what, "intr", intr, _F64, (n, 3))
+    nbytes = lib.pp_depth_normals_workspace_bytes(n, H, W)
+    ws = _workspace(nbytes)  # (0 bytes: a refused shape, which the entry point reports)
+    out = {k: _out(depth, (n, H, W) + tail, dt) for k, (dt, tail) in DEPTH_NORMALS_OUTPUTS.items() if k in want}
+    taps = np.ascontiguousarray(gaussian_taps(2.0), np.float64)
+    check(lib.pp_depth_normals_f64(ctx.handle, n, H, W, _ptr(depth), _ptr(intr), taps.ctypes.data_as(C.POINTER(C.c_double)),
+                                   1 if for_vis else 0, _ptr(ws), nbytes, *[_ptr(out.get(k)) for k in DEPTH_NORMALS_OUTPUTS]),
+          ctx.handle, "pp_depth_normals_f64")
+    return out
