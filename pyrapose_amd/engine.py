@@ -7,14 +7,15 @@ Backward = reverse-mode over the same op list with the sum-of-consumers and the 
 into the last data-gradient launch of each tensor (see DESIGN.md §Backward dataflow).
 Loss / optimizer = bin/train.py:95-102.
 """
-import os as _os
+import math
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import arch, ops
-from ._lib import ParamDesc, RowSpace
+from ._lib import MISSING, ParamDesc, RowSpace
+from .switches import EngineSwitches
 
 
 def _ru(v, m):
@@ -264,6 +265,7 @@ class Engine(object):
         # another torch stream re-binds the shared context, never this one, so lane 0 and the fork/join events of the other
         # lanes always speak about the same stream.  Work of the caller's current stream is ordered around every public
         # entry point by _enter() / _leave().
+        self.sw = sw = EngineSwitches.from_env()  # every PP_* switch the plan depends on, read here and nowhere else
         self._own_ctx = ops.Context(ctx.device, ctx.stream)
         ctx = self._own_ctx
         self.ctx, self.C, self.B, self.H, self.W = ctx, int(num_classes), int(batch), int(height), int(width)
@@ -289,9 +291,6 @@ class Engine(object):
                     s.trainable = False
         self.params = ParamStore(self.specs, train)
         self.params.load(weights if weights is not None else arch.init_weights(self.C, seed, backbone, pyramid, self.A))
-        # conv arithmetic: "bf16x3" (default) = 3 x bf16 MFMA per product, f32 accumulation (conv3.hip; ~2^-16 per
-        # product, whole-graph outputs within 2e-5 of the f32 path) for every conv except the 3-channel stem;
-        # "f32" = exact f32 MFMA everywhere (conv.hip).  Both hold the 1e-3 head-output bar.
         # conv_mode / PP_CONV_MODE: "f32" (exact f32 MFMA), or the plane-stored family with one of three arithmetics:
         #   "bf16x3"  every layer on bf16 pairs, three bf16 MFMAs per product (4.5e-6 per launch against float64);
         #   "f16c8"   every layer on P16 planes, one f16 MFMA + half a block-scaled e5m2 MFMA per 16-deep step (2 units per product
@@ -299,9 +298,9 @@ class Engine(object):
         #   "mixed"   (default) the backbone on bf16x3 -- its ~50 HBM- / latency-bound layers are where rounding accumulates and
         #             where MFMA work is not what costs -- and the MFMA-bound FPN + heads on f16c8; C3 / C4 / C5 and the gradients
         #             flowing back into them are re-encoded at the boundary (pp_convert_planes).
-        mode = conv_mode or _os.environ.get("PP_CONV_MODE", "mixed")
+        mode = conv_mode or sw.conv_mode
         assert mode in ("f32", "bf16x3", "f16c8", "mixed"), mode
-        if mode in ("f16c8", "mixed") and _os.environ.get("PP_PLANES", "1") == "0":
+        if mode in ("f16c8", "mixed") and not sw.planes:
             mode = "bf16x3"  # float32 storage (PP_PLANES=0) exists for the bf16x3 arithmetic only
         self.arith = mode
         self.conv_mode = "f32" if mode == "f32" else "bf16x3"  # the kernel family (csrc/conv.hip or csrc/conv3.hip)
@@ -312,26 +311,24 @@ class Engine(object):
         # The products are the same as with the in-loop split (same hi, lo); a value read back from planes (residuals, adds)
         # is within 2^-17 of the float32 it was split from.  float32 stays for: the image, conv1 / pool1 (frozen prefix), the
         # three head outputs (losses, export) and the loss gradients.
-        self.po = self.conv_mode == "bf16x3" and _os.environ.get("PP_PLANES", "1") != "0"
-        self.use_act_planes = False  # (the round-1 "both formats" mode is gone: planes-only supersedes it)
+        self.po = self.conv_mode == "bf16x3" and sw.planes
         # split capture (PP_CAPTURE=1): the forward / bwd-data launch of a 3x3 stride-1 conv also stores the bf16 split of
         # its gathered operand (it has just computed it), and the weight-gradient launch of the layer, enqueued after the
         # layer's bwd-data launch, reads both operands pre-split.  Off by default: the weight-gradient kernel alone gains
         # 11-15 % and the capture costs the 512-channel launches nothing, but the training step does not move (one lane:
         # +0.6 %; two lanes: -1 % -- with both lanes busy the MFMA pipes, not the conversion VALU, are what is shared).
-        self.capture = (self.conv_mode == "bf16x3" and not self.po and _os.environ.get("PP_CAPTURE", "0") == "1")
+        self.capture = (self.conv_mode == "bf16x3" and not self.po and sw.capture)
         # Sparse backward of the 3D-box head (PP_SPARSE_BWD=0 disables): orthogonal_l1 keeps the rows with anchor state 1 only
         # (losses.py:332-333), so the gradient entering that head -- and, dilated by one pixel per 3x3 layer, every gradient
         # inside it -- is exactly zero away from the positive anchors.  One scan per layer lists the 32-row blocks that hold a
         # non-zero (pp_row_block_list); the weight gradient reduces over those blocks only and the data gradient skips the
         # output tiles that cannot see one.  Exact: a zero row adds 0.0 to every sum.
-        self.sparse_bwd = tuple(t for t in _os.environ.get("PP_SPARSE_BWD", "reg").split(",") if t and t != "0") \
-            if self.conv_mode == "bf16x3" else ()
+        self.sparse_bwd = sw.sparse_bwd if self.conv_mode == "bf16x3" else ()
         # opt-in: the FORWARD of that head on the same blocks in training steps (_plan_sparse_forward)
-        self.sparse_fwd = (self.train and self.po and "reg" in self.sparse_bwd and _os.environ.get("PP_SPARSE_FWD", "0") == "1")
+        self.sparse_fwd = (self.train and self.po and "reg" in self.sparse_bwd and sw.sparse_fwd)
         self._sparse_fwd_now = False  # set by _train_forward around the forward of a training step
-        self.capture_min_cin = int(_os.environ.get("PP_CAPTURE_MIN_CIN", "64"))
-        self.capture_skip = tuple(t for t in _os.environ.get("PP_CAPTURE_SKIP", "").split(",") if t)
+        self.capture_min_cin = sw.capture_min_cin
+        self.capture_skip = sw.capture_skip
         self.planes = OrderedDict()  # spec name -> dict(desc, fwd_hi, fwd_lo, dg_hi, dg_lo)
         self.fwd_ops, self.graph_ops, self.bwd_ops = [], [], []
         # Launch lanes: lane 0 is the ctx stream; lanes 1-2 are side streams.  Independent kernel chains (the three
@@ -340,14 +337,13 @@ class Engine(object):
         # workgroups of another -- see DESIGN.md §Concurrency.  PP_LANES=1 serialises everything on lane 0.
         # Measured (tools/phase_times.py, batch 8): forward 8.20 / 8.02 / 8.44 ms and backward 15.45 / 14.19 / 14.13 ms
         # at 1 / 2 / 3 lanes -> two lanes (a third concurrent head chain only adds cache pressure).
-        os = _os
-        self.n_lanes = max(1, min(3, int(os.environ.get("PP_LANES", "2"))))
+        self.n_lanes = sw.lanes
         self.streams = [ctx.stream] + [torch.cuda.Stream(device=ctx.device) for _ in range(self.n_lanes - 1)]
         self.ctxs = [ctx] + [ops.Context(ctx.device, st) for st in self.streams[1:]]
         # split-K scratch (one per lane): the small-M convs of res5 / FPN level 5 cannot fill 256 CUs with output tiles
         # alone (3x3 512->512 on 2400 rows: 112 -> 174 TFLOP/s with 4 slices).  Deterministic (fixed-order slice sum).
         # (also the slices of the weight-gradient launches: splits x |dW| in f32, e.g. 16 x 9.4 MB for the 512-wide head convs)
-        ws_mb = int(os.environ.get("PP_SPLITK_MB", "256"))
+        ws_mb = sw.splitk_mb
         if self.conv_mode == "bf16x3" and ws_mb > 0:
             for c in self.ctxs:
                 c.set_workspace(ws_mb << 20)
@@ -358,16 +354,14 @@ class Engine(object):
         self.gscale = None
         # loss weights above the reference's defaults (orthogonal_l1 weight 0.125, focal alpha 0.25) scale the loss gradients up: take
         # that factor out of the power-of-two gradient scale, so that the headroom under the P16 clamp stays what it is at the defaults
-        import math as _math
         ratio = max(self.loss_params["box"][0] / 0.125, self.loss_params["cls"][0] / 0.25, self.loss_params["mask"][0] / 0.25, 1.0)
-        self.gscale_adjust = -int(_math.ceil(_math.log2(ratio)))
-        from ._lib import MISSING as _missing
-        if self.train and self.po and self.arith in ("f16c8", "mixed") and "pp_grad_scale_from_counts" not in _missing:
+        self.gscale_adjust = -int(math.ceil(math.log2(ratio)))
+        if self.train and self.po and self.arith in ("f16c8", "mixed") and "pp_grad_scale_from_counts" not in MISSING:
             self.gscale = torch.ones((2,), dtype=torch.float32, device="cuda")
             for c in self.ctxs:
                 ops.set_grad_scale(c.twin(1), self.gscale)  # (bf16-pair gradients are unscaled: only the P16 contexts divide it out)
         self._lane = 0
-        self.trunk_lanes = os.environ.get("PP_TRUNK_LANES", "1") != "0"  # backbone shortcut / FPN level 4-5 chains on lane 1
+        self.trunk_lanes = sw.trunk_lanes  # backbone shortcut / FPN level 4-5 chains on lane 1
         # Prefix lane (training with conv1 + res2 frozen, the reference's setting): the frozen prefix is a pure function of
         # the input batch -- no weight of it ever changes -- so the prefix of batch i+1 can run while batch i is still in
         # its trunk / heads (forward(next_x=...): software pipelining over steps; the trunk's launches are small and leave
@@ -380,7 +374,7 @@ class Engine(object):
         self.n_prefix_early = 0
         self._prefetched = None
         frozen_prefix = all(not sp.trainable for sp in self.specs if sp.name == "conv1" or sp.name.startswith("res2"))
-        if self.train and frozen_prefix and self.conv_mode == "bf16x3" and os.environ.get("PP_PREFETCH", "0") == "1":
+        if self.train and frozen_prefix and self.conv_mode == "bf16x3" and sw.prefetch:
             pst = torch.cuda.Stream(device=ctx.device)
             self.streams.append(pst)
             self.ctxs.append(ops.Context(ctx.device, pst))
@@ -427,6 +421,15 @@ class Engine(object):
             c.close()
         self.ctxs = []
         self.fwd_ops, self.bwd_ops, self.graph_ops = [], [], []
+
+    def plan_signature(self):
+        """What the constructor decided, as plain JSON-serialisable data (no tensors, pointers or timings): to print beside a
+        figure, and to compare two builds of the plan (tests/test_gpu_engine_plan.py)."""
+        launches = lambda plan: [[o.kind, o.name, o.lane] for o in plan]
+        return dict(fwd_ops=launches(self.fwd_ops), bwd_ops=launches(self.bwd_ops),
+                    plane_grads=[list(g.shape()) + [g.fmt, bool(g.lazy), g.within is not None] for g in self._plane_grads],
+                    s2_grads=[[layer, route] for layer, _, route in self._s2_grads],
+                    arith=self.arith, n_lanes=self.n_lanes, prefix_lane=self.prefix_lane, switches=self.sw.non_default())
 
     def _enter(self):
         """order the engine's lane 0 after the caller's current stream (no-op when they are the same stream)"""
@@ -592,8 +595,7 @@ class Engine(object):
             self._lane = self.prefix_lane
         pctx = self.ctxs[self._lane]  # the context of the frozen prefix's launches (lane 0, or the prefix lane)
         # (the row-as-tap stem needs the buffer-addressed loop: PP_CONV3_FAST=0 also turns it off)
-        self.stem3 = (self.conv_mode == "bf16x3" and _os.environ.get("PP_STEM3", "1") != "0" and
-                      _os.environ.get("PP_CONV3_FAST", "1") != "0")
+        self.stem3 = self.conv_mode == "bf16x3" and self.sw.stem3 and self.sw.conv3_fast
         if self.stem3:
             # the stem on the bf16 path: the packed image sits at (3, 3) of a zero frame and every kernel ROW is one tap of
             # a 7x1 conv over 32 overlapping "channels" (pp_stem7x7s2_fwd_bf16x3)
@@ -655,7 +657,8 @@ class Engine(object):
         # the mask head (P3 only: 0.6 ms) follows the class head on lane 1 when there are two lanes: the 3D-box head (2.3 ms)
         # has lane 0 to itself and both lanes stay busy for longer (PP_MASK_LANE overrides)
         # (with the sparse forward of the 3D-box head lane 0 is the short one: the mask head goes there)
-        self._lane = int(_os.environ.get("PP_MASK_LANE", ("0" if self.sparse_fwd else "1") if self.n_lanes == 2 else "2")) % self.n_lanes
+        mask_lane = (0 if self.sparse_fwd else 1) if self.n_lanes == 2 else 2
+        self._lane = (mask_lane if self.sw.mask_lane is None else self.sw.mask_lane) % self.n_lanes
         self.mask_out = run_head("mask", P3)
         self._lane = 0
         # interleave the three chains in enqueue order so that every lane has work from the start
@@ -673,7 +676,7 @@ class Engine(object):
         if self.sparse_fwd:
             self._plan_sparse_forward()
         self.pf_trigger = self.n_prefix_early + 1
-        after = _os.environ.get("PP_PREFETCH_AFTER")
+        after = self.sw.prefetch_after
         if after and self.prefix_lane is not None:
             idx = [i for i, o in enumerate(self.fwd_ops) if o.name == after and o.lane == 0]
             assert idx, "PP_PREFETCH_AFTER=%s: no such lane-0 launch" % after
@@ -836,9 +839,12 @@ class Engine(object):
         return out
 
     # ------------------------------------------------------------------------------------ backward plan
+    def _plane_stored(self, ld):
+        return self.po and ld % 8 == 0
+
     def _new_grad(self, rows, ld, fmt=0):
         """an uninitialised gradient matrix in the mode's storage format (fmt: the plane format of the tensor it belongs to)"""
-        if self.po and ld % 8 == 0:
+        if self._plane_stored(ld):
             g = Grad(None, _new_planes(rows, ld), fmt)
             self._plane_grads.append(g)  # (p16_stats() looks at the P16 ones after a step)
             return g
@@ -880,49 +886,14 @@ class Engine(object):
             if pl is not None and pl["dg_hi"] is not None:
                 gcap = op.get("g_cap")
                 sk = op.get("skip")
-                # a sparse data gradient (row-block skip) that only adds to the sum of the earlier ones works in place on that sum:
-                # the rows no non-zero reaches keep their value and nothing else is moved (`acc` of i > 0 is private to this loop)
-                in_place = (sk is not None and i > 0 and mask is None and acc is not None and gcap is None
-                            and _os.environ.get("PP_SPARSE_INPLACE", "1") != "0")
+                in_place, lazy_out, carries_within = self._sparse_dgrad_route(i, len(dgrads), acc, mask, gcap, sk, gy,
+                                                                              self._plane_stored(act.ld), producer)
                 out = acc if in_place else self._new_grad(act.rows, act.ld, act.fmt)
-                # Lazy: the only readers of this gradient are the backward launches of a sparse layer (its scan restricted to the
-                # blocks this launch computes, its listed-block weight gradient, its listed-block data gradient) -- the rows outside
-                # those blocks are never looked at, so the 103 MB fill pass of zeros is not made (3D-box head: four per step)
-                lazy_out = (sk is not None and len(dgrads) == 1 and acc is None and gcap is None and gy.pl is not None and out.pl is not None
-                            and self._lazy_reader(producer) and _os.environ.get("PP_SPARSE_WITHIN", "1") != "0"
-                            and _os.environ.get("PP_SPARSE_LAZY", "1") != "0" and _os.environ.get("PP_SPARSE_DGRAD", "22") != "0")
-                lazy_in = bool(gy.lazy)
-                # every operand in the format it exists in (planes where there is no float32 copy)
-                dy_t, dy_pl = (None, gy.pl) if gy.pl is not None else (gy.t, None)
-                a_t = a_pl = m_t = m_hi = None
-                if acc is not None:
-                    a_t, a_pl = (acc.t, None) if acc.t is not None else (None, acc.pl)
-                if mask is not None:
-                    m_t, m_hi = (mask.t, None) if mask.t is not None else (None, mask.pl[0])
-                if gcap is not None:
-                    assert dy_t is not None
-                # stride 2: all parity classes in one launch where that entry point takes the call (the planner says so: all-f32 or
-                # all-planes operands, no capture, no row-block skip); PP_CONV3_S2MERGED=0 keeps the launch per class
-                forms = (ops.PLAN_PLANES_IN if dy_pl is not None else 0) | (ops.PLAN_PLANES_OUT if out.pl is not None else 0) | \
-                        (ops.PLAN_F32_OUT if out.t is not None else 0)
-                if (op["desc"].stride == 2 and gcap is None and sk is None and ops.conv_s2_merged()
-                        and "refused" not in ops.conv_plan_text(op["desc"], ops.PLAN_BWD_DATA_S2, forms, act.fmt)):
-                    self.bwd_ops.append(Op(lambda d=op["desc"], dy_t=dy_t, dy_pl=dy_pl, dh=pl["dg_hi"], dl=pl["dg_lo"], a_t=a_t, a_pl=a_pl, m_t=m_t,
-                                           m_hi=m_hi, out=out:
-                                           ops.conv_bwd_data3_s2(ctx, d, dy_t, dh, dl, a_t, m_t, out.t, dy_pl, out.pl, a_pl, m_hi), "conv_dgrad",
-                                           op["spec"].name, op["flops"]))
-                    self._s2_grads.append((op["spec"].name, out, "merged"))
-                else:
-                    if op["desc"].stride == 2:
-                        self._s2_grads.append((op["spec"].name, out, "classes"))
-                    self.bwd_ops.append(Op(lambda d=op["desc"], dy_t=dy_t, dy_pl=dy_pl, dh=pl["dg_hi"], dl=pl["dg_lo"], a_t=a_t, a_pl=a_pl, m_t=m_t,
-                                           m_hi=m_hi, out=out, gcap=gcap, sk=sk, lazy_out=lazy_out, lazy_in=lazy_in:
-                                           ops.conv_bwd_data3(ctx, d, dy_t, dh, dl, a_t, m_t, out.t, dy_pl, out.pl, gcap, sk, a_pl, m_hi,
-                                                              lazy_out=lazy_out, lazy_in=lazy_in), "conv_dgrad",
-                                           op["spec"].name, op["flops"]))
+                assert not lazy_out or out.pl is not None
+                self.bwd_ops.append(self._dgrad3_op(ctx, op, gy, acc, mask, out, gcap, sk, lazy_out, act.fmt))
                 # a row-block-skip launch without addend leaves zeros (lazy: nothing at all) outside the blocks it flags in the second
                 # half of its scratch
-                out.within = sk[0][sk[0].numel() // 2:] if (sk is not None and acc is None and _os.environ.get("PP_SPARSE_WITHIN", "1") != "0") else None
+                out.within = sk[0][sk[0].numel() // 2:] if carries_within else None
                 out.lazy = lazy_out
                 assert not lazy_out or out.within is not None
                 pw = op.pop("pending_wgrad", None)
@@ -937,6 +908,50 @@ class Engine(object):
             acc = out
         return acc
 
+    def _dgrad3_op(self, ctx, op, gy, acc, mask, out, gcap, sk, lazy_out, fmt):
+        """the data-gradient launch of the plane-family conv `op`: out = dgrad(gy) (+ acc) (* (mask > 0))"""
+        d, dh, dl = op["desc"], op["planes"]["dg_hi"], op["planes"]["dg_lo"]
+        lazy_in = bool(gy.lazy)
+        # every operand in the format it exists in (planes where there is no float32 copy)
+        dy_t, dy_pl = (None, gy.pl) if gy.pl is not None else (gy.t, None)
+        a_t = a_pl = m_t = m_hi = None
+        if acc is not None:
+            a_t, a_pl = (acc.t, None) if acc.t is not None else (None, acc.pl)
+        if mask is not None:
+            m_t, m_hi = (mask.t, None) if mask.t is not None else (None, mask.pl[0])
+        assert gcap is None or dy_t is not None
+        # stride 2: all parity classes in one launch where that entry point takes the call (the planner says so: all-f32 or
+        # all-planes operands, no capture, no row-block skip); PP_CONV3_S2MERGED=0 keeps the launch per class
+        forms = (ops.PLAN_PLANES_IN if dy_pl is not None else 0) | (ops.PLAN_PLANES_OUT if out.pl is not None else 0) | \
+                (ops.PLAN_F32_OUT if out.t is not None else 0)
+        if (d.stride == 2 and gcap is None and sk is None and ops.conv_s2_merged()
+                and "refused" not in ops.conv_plan_text(d, ops.PLAN_BWD_DATA_S2, forms, fmt)):
+            fn = lambda: ops.conv_bwd_data3_s2(ctx, d, dy_t, dh, dl, a_t, m_t, out.t, dy_pl, out.pl, a_pl, m_hi)
+            self._s2_grads.append((op["spec"].name, out, "merged"))
+        else:
+            if d.stride == 2:
+                self._s2_grads.append((op["spec"].name, out, "classes"))
+            fn = lambda: ops.conv_bwd_data3(ctx, d, dy_t, dh, dl, a_t, m_t, out.t, dy_pl, out.pl, gcap, sk, a_pl, m_hi,
+                                            lazy_out=lazy_out, lazy_in=lazy_in)
+        return Op(fn, "conv_dgrad", op["spec"].name, op["flops"])
+
+    def _sparse_dgrad_route(self, i, n_dgrads, acc, mask, gcap, sk, gy, fresh_is_planes, producer):
+        """(in_place, lazy_out, carries_within) of the `i`-th of a tensor's `n_dgrads` data gradients; all False unless it is a
+        sparse one (sk: its layer's row-block skip).  acc: the sum so far, mask: the ReLU to fold in, gcap: split capture, gy: the
+        incoming gradient, fresh_is_planes: a new gradient of the tensor is plane-stored, producer: the op that reads the result."""
+        sw = self.sw
+        # a sparse data gradient (row-block skip) that only adds to the sum of the earlier ones works in place on that sum:
+        # the rows no non-zero reaches keep their value and nothing else is moved (`acc` of i > 0 is private to _finalize's loop)
+        in_place = sk is not None and i > 0 and mask is None and acc is not None and gcap is None and sw.sparse_inplace
+        # Lazy: the only readers of this gradient are the backward launches of a sparse layer (its scan restricted to the
+        # blocks this launch computes, its listed-block weight gradient, its listed-block data gradient) -- the rows outside
+        # those blocks are never looked at, so the 103 MB fill pass of zeros is not made (3D-box head: four per step)
+        # (acc is None: the output is a newly allocated gradient)
+        lazy_out = (sk is not None and n_dgrads == 1 and acc is None and gcap is None and gy.pl is not None and fresh_is_planes
+                    and self._lazy_reader(producer) and sw.sparse_within and sw.sparse_lazy and sw.sparse_dgrad)
+        carries_within = sk is not None and acc is None and sw.sparse_within
+        return in_place, lazy_out, carries_within
+
     def _lazy_reader(self, producer):
         """is `producer` (the op that made the activation whose gradient is being formed) a layer whose whole backward goes by
         row-block flags?  a sparse 3x3 stride-1 conv without residual, planes on both sides, not the first layer of the graph"""
@@ -945,7 +960,7 @@ class Engine(object):
         s_, pl_, x_, y_ = producer["spec"], producer.get("planes"), producer["x"], producer["y"]
         # (the listed-block launches are forms of the buffer-addressed loops: their conditions, csrc/conv3.hip igemm3_fast_ok /
         # launch_wgrad3 -- the C side refuses a lazy operand where they do not hold, this keeps the plan away from that)
-        geo = (_os.environ.get("PP_CONV3_FAST", "1") != "0" and min(h * w for h, w in x_.shapes) >= 32 and x_.rows < (1 << 24)
+        geo = (self.sw.conv3_fast and min(h * w for h, w in x_.shapes) >= 32 and x_.rows < (1 << 24)
                and x_.rows * x_.ld * 4 < (1 << 31) and y_.rows * y_.ld * 4 < (1 << 31) and list(x_.shapes) == list(y_.shapes))
         return self._sparse_layer(s_) and pl_ is not None and pl_["dg_hi"] is not None and x_.pl is not None and y_.pl is not None and geo
 
