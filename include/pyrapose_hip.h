@@ -1003,6 +1003,71 @@ int pp_depth_normals_f64(pp_ctx* ctx, int n_img, int H, int W, const float* dept
                          int for_vis, void* workspace, size_t workspace_bytes, double* normals_f64, unsigned char* normals_u8,
                          double* depth_smoothed_f64, double* signed_f64);
 
+/* ---- depth-sensor simulation (csrc/depth_aug.hip) -------------------------------------------------------------------------
+ * The reference's augmentDepth (annotation_scripts/Augmentations.py:10-134; augment_syn_LineMOD.py:273-418 and
+ * augment_syn_Tless.py:219-356 with their `method` switch): a rendered depth map made to look like a Kinect frame.  Integer
+ * work on the mask, float64 from the first average on, every product, sum and quotient rounded on its own; no atomics and no
+ * reduction across lanes: bit-identical to the numpy restatement (tests/depth_aug_np.py) and run to run.
+ * Pinned: the majority filter to scipy.signal.medfilt2d and the opening to scipy.ndimage's grey erosion / dilation
+ * (tests/test_depth_aug_cpu.py).  Not pinned, restated from OpenCV's documented rules: morphologyEx's default border, resize
+ * INTER_LINEAR, GaussianBlur's BORDER_REFLECT_101 and tap weights -- and OpenCV computes a float32 image in float32 where this
+ * is float64.  Not the reference's at all: the simplex noise (the project's own; pyfastnoisesimd's bits cannot be had) and the
+ * standard normals, which the caller supplies as a field (the device draws none: log and cos would not be numpy's bits).
+ *
+ * One float64 row of PP_DA_P values per image, on the device (params) and the same rows on the HOST (params_host, validated
+ * and used to decide which launches are needed; the kernels read the device copy): */
+#define PP_DA_K_OPEN 0      /* box of the opening, 1 | 3 | 5 | 7 */
+#define PP_DA_K_MED 1       /* window of the majority (median) filter, 1 | 3 | 5 | 7 */
+#define PP_DA_K_BLUR 2      /* taps of the blur, 1 | 3 | 5 | 7 */
+#define PP_DA_TAPS 3        /* 7 slots: the first k_blur hold cv2.getGaussianKernel's weights, from the caller (one exp for all) */
+#define PP_DA_DEPTH_NOISE 10
+#define PP_DA_SENSOR 11     /* 0 | 1: the half-resolution sensor stage */
+#define PP_DA_SIMPLEX 12    /* 0 | 1: the simplex warp (the reference's method 0 = both, 1 = sensor only, 2 = simplex only) */
+#define PP_DA_FREQ 13       /* in [0, 16] */
+#define PP_DA_OCTAVES 14    /* 1..8 */
+#define PP_DA_LACUNARITY 15 /* in (0, 4] */
+#define PP_DA_GAIN 16
+#define PP_DA_W_XY 17
+#define PP_DA_W_Z 18
+#define PP_DA_JITTER_LO 19  /* 3 values, one per noise field; |.| <= 65536 */
+#define PP_DA_JITTER_HI 22  /* 3 values */
+#define PP_DA_SEED 25       /* an integer in [0, 2^53) */
+#define PP_DA_P 26
+/* pp_depth_augment: n_img images in one call (the batch rides on a grid dimension).
+ *   in   depth [n,H,W] float32 (device; millimetres, finite, >= 0); mask [n,H,W] uint8 (device; non-zero = foreground);
+ *        z [n,h2,w2] float32 standard normals (device; may be NULL when no image has sensor = 1), h2 = rint(H / 2) and
+ *        w2 = rint(W / 2), half to even (cv2's cvRound).
+ *   A  shadow and halve (one launch; a 32 x 32 tile with a 9-pixel halo as bytes in LDS).  m0 = mask != 0; erode with the
+ *      k_open x k_open box, then dilate with it, pixels outside the image taking no part in either; m = (set pixels in the
+ *      zero-padded k_med x k_med window) > k_med^2 / 2; d1 = m ? depth : 0.  With sensor: d2[y,x] = 0.5 a + 0.5 b of rows
+ *      min(2y, H-1) and min(2y+1, H-1), a and b each 0.5 p + 0.5 q of columns min(2x, W-1) and min(2x+1, W-1).
+ *   B  sensor (one launch on the half-size image; a 32 x 32 tile with a 3-pixel halo in LDS).  res = ((d2 / 1000) 1.41421356)^2
+ *      (the square one product); b = the k_blur taps along each row, then along each column, border reflect_101
+ *      (gfedcb|abcdefgh, mirrored again and again on a short line), a pass adding its products onto the first one in
+ *      increasing tap index; q = res != 0 ? rint(b / res) res : 0 (half to even); s = q + (q depth_noise) z.
+ *   C  warp (one launch, a lane per pixel).  D = d1 without sensor; with it the bilinear up-sampling of s, evaluated from s
+ *      where it is needed and never stored: f = (x + 0.5)(w2 / W) - 0.5, sx = floor(f), frac = f - sx; sx < 0 -> (0, 0);
+ *      sx >= w2 - 1 -> (w2 - 1, 0); (1 - frac) l + frac r along the columns of each of the two rows, then between the rows.
+ *      simplex = 0: out = D.  Otherwise V_f, f = 0..2, = sum_o gain^o N(p lacunarity^o; seed + o) / sum_o gain^o (both sums
+ *      from 0.0 in increasing o, the powers by repeated multiplication), p = (j_f freq, y freq, x freq),
+ *      j_f = lo_f + (hi_f - lo_f) u, u = (splitmix64(splitmix64(4 seed + f) + (y W + x)) >> 11) 2^-53; N: Gustavson's 3-D
+ *      simplex noise, its hash, corner order and scale (32) in the comment at the head of csrc/depth_aug.hip.  a = D 0.001;
+ *      fx = x + (a w_xy) V0, fy = y + (a w_xy) V1, clamped to [0, W-1] / [0, H-1], truncated; out = D(fy, fx) + (a w_z) V2,
+ *      then out > 0 ? out : 0.
+ *   out  each may be NULL (skipped, with the launches nobody needs), at least one must not be:
+ *        depth_f32 [n,H,W] out rounded once to float32 (what feeds pp_depth_normals_f64); depth_f64 [n,H,W] out;
+ *        mask_u8 [n,H,W] m as 0 / 255; half_f64 [n,h2,w2] s (zeros for an image without sensor);
+ *        sensor_f64 [n,H,W] D (d1 for an image without sensor)
+ *   Errors before anything is launched: n_img outside 1..65535, H or W outside 8..16384: PP_ERR_SHAPE; a null depth / mask /
+ *   params / params_host / workspace, no output, a kernel size not in {1, 3, 5, 7}, octaves not an integer in 1..8, sensor or
+ *   simplex not 0 / 1, a seed that is no integer in [0, 2^53), freq, lacunarity or a jitter bound out of range, any parameter
+ *   not finite, z NULL while an image has sensor = 1, workspace_bytes < pp_depth_augment_workspace_bytes(n_img, H, W)
+ *   (0: a refused shape): PP_ERR_ARG. */
+size_t pp_depth_augment_workspace_bytes(int n_img, int H, int W);
+int pp_depth_augment(pp_ctx* ctx, int n_img, int H, int W, const float* depth, const unsigned char* mask, const double* params,
+                     const double* params_host, const float* z, void* workspace, size_t workspace_bytes, float* depth_f32,
+                     double* depth_f64, unsigned char* mask_u8, double* half_f64, double* sensor_f64);
+
 #ifdef __cplusplus
 }
 #endif

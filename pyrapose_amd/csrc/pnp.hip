@@ -13,6 +13,7 @@
 //      re-selected, 10 more; fixed-order block reductions.
 // One workgroup of 256 threads per problem (class x image); float64; compiled with -ffp-contract=off.
 #include "pp_internal.h"
+#include "splitmix.h"
 
 #define PNP_THREADS 256
 #define PNP_REFINE_ITERS 10
@@ -35,14 +36,6 @@ struct PnpArgs {
   unsigned char* mask;   // [N]
   int* ok;               // [n_problems]
 };
-
-__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  unsigned long long z = x;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 
 __device__ __forceinline__ unsigned long long pnp_draw(unsigned long long seed, int problem, int it, int j) {
   const unsigned long long key = ((seed & 0xFFFFFFFFull) << 32) ^ ((unsigned long long)(problem & 0xFFF) << 20) ^

@@ -1446,3 +1446,60 @@ def depth_normals(ctx, depth, intr, for_vis=True, want=("normals", "depth")):
                                    1 if for_vis else 0, _ptr(ws), nbytes, *[_ptr(out.get(k)) for k in DEPTH_NORMALS_OUTPUTS]),
           ctx.handle, "pp_depth_normals_f64")
     return out
+
+
+DEPTH_AUG_TILE = 32   # pixels per edge of the LDS tiles of pp_depth_augment (halo: 9 more per side in launch A, 3 in launch B)
+DEPTH_AUG_OUTPUTS = {"depth_f32": _F32, "depth_f64": _F64, "mask_u8": _U8, "half_f64": _F64, "sensor_f64": _F64}  # in the ABI's order
+# a parameter row of pp_depth_augment (PP_DA_* of include/pyrapose_hip.h): name -> (first slot, slots)
+DEPTH_AUG_PARAMS = {"k_open": (0, 1), "k_med": (1, 1), "k_blur": (2, 1), "blur_taps": (3, 7), "depth_noise": (10, 1), "sensor": (11, 1),
+                    "simplex": (12, 1), "freq": (13, 1), "octaves": (14, 1), "lacunarity": (15, 1), "gain": (16, 1), "w_xy": (17, 1),
+                    "w_z": (18, 1), "jitter_lo": (19, 3), "jitter_hi": (22, 3), "seed": (25, 1)}
+DEPTH_AUG_P = 26
+
+
+def depth_aug_half_size(n):
+    """cv2's cvRound(n / 2), half to even: the side of pp_depth_augment's half-size image"""
+    return n // 2 + ((n // 2) & 1 if n & 1 else 0)
+
+
+def depth_aug_blur_taps(k, sigma):
+    """cv2.getGaussianKernel(k, sigma) as a float64 host array: exp(-x^2 / (2 sigma^2)) over x = -(k-1)/2 .. (k-1)/2, divided
+    by their sum; sigma <= 0 means cv2's 0.3 ((k - 1) 0.5 - 1) + 0.8.  pp_depth_augment takes them in its parameter rows, so
+    that the library and whoever restates it share one exp."""
+    k, sigma = int(k), float(sigma)
+    if k not in (1, 3, 5, 7):
+        raise ValueError("depth_aug_blur_taps: k must be 1, 3, 5 or 7, got %r" % (k,))
+    if sigma <= 0:
+        sigma = 0.3 * ((k - 1) * 0.5 - 1) + 0.8
+    x = np.arange(k, dtype=np.float64) - (k - 1) // 2
+    w = np.exp(-(x * x) / (2.0 * sigma * sigma))
+    return w / w.sum()
+
+
+def depth_augment(ctx, depth, mask, params, z=None, want=("depth_f32",)):
+    """The reference's augmentDepth on n depth images (pp_depth_augment): cuda tensors depth float32 [n,H,W] (millimetres,
+    finite, >= 0) and mask uint8 [n,H,W] (non-zero = foreground); params a float64 HOST array [n, DEPTH_AUG_P], one row per
+    image (DEPTH_AUG_PARAMS); z cuda float32 [n,h2,w2] standard normals (h2, w2 = depth_aug_half_size of H, W), needed when a
+    row has sensor = 1; want: any of DEPTH_AUG_OUTPUTS -> dict of the requested outputs: 'depth_f32' / 'depth_f64' [n,H,W]
+    the augmented depth, 'mask_u8' [n,H,W] the shadow mask as 0 / 255, 'half_f64' [n,h2,w2] the half-size sensor image,
+    'sensor_f64' [n,H,W] the depth before the simplex warp."""
+    what = "depth_augment"
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(o not in DEPTH_AUG_OUTPUTS for o in want):
+        raise ValueError("%s: want must name at least one of %s, got %r" % (what, " | ".join(DEPTH_AUG_OUTPUTS), want))
+    depth = _arg(what, "depth", depth, _F32, (None, None, None))
+    n, H, W = (int(s) for s in depth.shape)
+    mask = _arg(what, "mask", mask, _U8, (n, H, W))
+    h2, w2 = depth_aug_half_size(H), depth_aug_half_size(W)
+    z = _arg(what, "z", z, _F32, (n, h2, w2), optional=True)
+    host = np.ascontiguousarray(params, np.float64)
+    if host.shape != (n, DEPTH_AUG_P):
+        raise ValueError("%s: params must be a host array [%d,%d], got %s" % (what, n, DEPTH_AUG_P, host.shape))
+    dev = torch.from_numpy(host).to(depth.device)
+    nbytes = lib.pp_depth_augment_workspace_bytes(n, H, W)
+    ws = _workspace(nbytes)  # (0 bytes: a refused shape, which the entry point reports)
+    shapes = {"half_f64": (n, h2, w2)}
+    out = {k: _out(depth, shapes.get(k, (n, H, W)), dt) for k, dt in DEPTH_AUG_OUTPUTS.items() if k in want}
+    check(lib.pp_depth_augment(ctx.handle, n, H, W, _ptr(depth), _ptr(mask), _ptr(dev), host.ctypes.data_as(C.POINTER(C.c_double)),
+                               _ptr(z), _ptr(ws), nbytes, *[_ptr(out.get(k)) for k in DEPTH_AUG_OUTPUTS]), ctx.handle, "pp_depth_augment")
+    return out

@@ -1,7 +1,9 @@
-"""Normal images from depth maps on the device: the reference's get_normal (annotation_scripts/Augmentations.py:394-467, the
-same function copied into annotate_val_LineMOD.py, annotate_val_LM_BOP.py, annotate_val_LMO_BOP.py, annotate_val_YCBV_BOP.py,
-prepare_val_LineMOD_RGB.py, augment_syn_LineMOD.py and augment_syn_Tless.py), which turns a depth image into the surface-normal
-image the reference writes as every sample's _dep.png and also returns the smoothed depth (csrc/depth_image.hip).
+"""Depth images on the device: the reference's augmentDepth and get_normal, the two steps between a depth render and the
+surface-normal image the reference writes as every sample's _dep.png.
+
+get_normal (annotation_scripts/Augmentations.py:394-467, the same function copied into annotate_val_LineMOD.py,
+annotate_val_LM_BOP.py, annotate_val_LMO_BOP.py, annotate_val_YCBV_BOP.py, prepare_val_LineMOD_RGB.py, augment_syn_LineMOD.py
+and augment_syn_Tless.py) turns a depth image into the normal image and also returns the smoothed depth (csrc/depth_image.hip).
 
 What is and is not the reference's:
   * fy is accepted and ignored, as the reference ignores it: both image axes are scaled by 1 / fx.
@@ -12,7 +14,26 @@ What is and is not the reference's:
     for_vis=False; here its uint8 image and its scaled depth are all zero.
   * The reference's int16 pixel table wraps beyond +-32767 pixels from the principal point; here it does not.
   * The three-value variants of augment_syn_LineMOD.py / augment_syn_Tless.py (cv2.inpaint) are not covered.
-Pinned to the reference's own function by tests/golden/depth_normals.npz, at every pixel whose smoothed depth is not exactly 0."""
+Pinned to the reference's own function by tests/golden/depth_normals.npz, at every pixel whose smoothed depth is not exactly 0.
+
+augmentDepth (annotation_scripts/Augmentations.py:10-134; augment_syn_LineMOD.py:273-418 and augment_syn_Tless.py:219-356 with
+their `method` switch) makes a perfect rendered depth map look like a Kinect frame (csrc/depth_aug.hip): shadow holes from the
+opened and median-filtered foreground mask, a half-resolution blur, quantisation to the sensor's depth resolution with
+depth-proportional Gaussian noise, and a fractal-simplex-noise warp of pixel positions and depth.  The per-image parameters are
+drawn on the host (sample_depth_programs), the pixels are done on the device (augment_depth_batch), bit for bit the numpy
+restatement tests/depth_aug_np.py.
+
+What is and is not the reference's there:
+  * The simplex noise is the project's own (Gustavson's 3-D simplex noise with an integer hash, csrc/depth_aug.hip):
+    pyfastnoisesimd's bits cannot be had, so a seed does not give the reference's field, only one of the same kind.
+  * The standard normals of the sensor noise are supplied as a field z (torch.randn on the device by default) instead of being
+    drawn inside: the result is q + (q depthNoise) z, what np.random.normal(loc=q, scale=q depthNoise) computes from its normals.
+  * The arithmetic after the mask is float64, where cv2 computes float32 images in float32.
+  * The image size is taken from the depth map; the fixed 640 x 480 of the T-LESS copy is not assumed.
+  * cv2 is restated from its documented rules (morphologyEx's default border, resize INTER_LINEAR, GaussianBlur's
+    BORDER_REFLECT_101 and getGaussianKernel) and not pinned; the majority filter is pinned to scipy.signal.medfilt2d and the
+    opening to scipy.ndimage's grey erosion and dilation.
+  * obj_mask is accepted and ignored, as the reference ignores it."""
 import numpy as np
 import torch
 
@@ -62,7 +83,9 @@ def normals_from_depth_batch(depth, K_or_intrinsics, for_vis=True, signed=False,
         normals, smoothed = normals_from_depth_batch(depth, K)
         images, info = scene_gt.render_scenes(scenes, models, K, (640, 480))          # the samples' _rgb
         gt = scene_gt.scene_gt_info(scenes, models, K, im_size=(640, 480))            # .depth: float32 [S,480,640], composed
-        dep_png, _ = normals_from_depth_batch(gt.depth, K, for_vis=False)             # the samples' _dep: uint8 [S,480,640,3]"""
+        programs = sample_depth_programs(np.random.default_rng(0), len(scenes))       # host: one parameter row per image
+        noisy = augment_depth_batch(gt.depth, None, programs)                         # the Kinect look: float32 [S,480,640]
+        dep_png, _ = normals_from_depth_batch(noisy, K, for_vis=False)                # the samples' _dep: uint8 [S,480,640,3]"""
     if signed and not for_vis:
         raise ValueError("normals_from_depth_batch: signed=True goes with for_vis=True (the uint8 image has no sign)")
     d = _depth_stack(depth)
@@ -81,3 +104,92 @@ def get_normal(depth_refine, fx=-1, fy=-1, cx=-1, cy=-1, for_vis=True):
         raise ValueError("get_normal: depth_refine must be [H,W], got %s" % (depth.shape,))
     n, d = normals_from_depth_batch(depth[None], np.array([fx, cx, cy], np.float64), for_vis=for_vis)
     return n[0].cpu().numpy(), d[0].cpu().numpy()
+
+
+def _program_row(k_open, k_med, k_blur, blur_sigma, depth_noise, method, freq, octaves, w_xy, w_z, seed):
+    """one parameter row of pp_depth_augment with the reference's constants: lacunarity 2.1, gain 0.45, the jitter ranges
+    (0.001, 0.01), (0.001, 0.01) and (0.01, 0.1); method 0 | 1 | 2 = both stages | sensor only | simplex only"""
+    if int(method) not in (0, 1, 2):
+        raise ValueError("method must be 0 (both stages), 1 (sensor only) or 2 (simplex only), got %r" % (method,))
+    row = np.zeros(ops.DEPTH_AUG_P, np.float64)
+    at = {k: v[0] for k, v in ops.DEPTH_AUG_PARAMS.items()}
+    row[at["k_open"]], row[at["k_med"]], row[at["k_blur"]] = int(k_open), int(k_med), int(k_blur)
+    row[at["blur_taps"]:at["blur_taps"] + int(k_blur)] = ops.depth_aug_blur_taps(k_blur, blur_sigma)
+    row[at["depth_noise"]] = depth_noise
+    row[at["sensor"]], row[at["simplex"]] = ((1, 1), (1, 0), (0, 1))[int(method)]
+    row[at["freq"]], row[at["octaves"]], row[at["lacunarity"]], row[at["gain"]] = freq, int(octaves), 2.1, 0.45
+    row[at["w_xy"]], row[at["w_z"]] = w_xy, w_z
+    row[at["jitter_lo"]:at["jitter_lo"] + 3] = 0.001, 0.001, 0.01
+    row[at["jitter_hi"]:at["jitter_hi"] + 3] = 0.01, 0.01, 0.1
+    row[at["seed"]] = int(seed)
+    return row
+
+
+def sample_depth_programs(rng, n, method=0, shadowClK=None, shadowMK=None, blurK=None, blurS=None, depthNoise=None):
+    """The reference's draws for n images, on the host, from a numpy Generator -> float64 [n, ops.DEPTH_AUG_P], one parameter
+    row of pp_depth_augment per image: the three kernel sizes uniformly from {3, 5, 7}, blurS ~ U(0, 1.5), depthNoise ~
+    U(0.002, 0.004), a seed below 2^31, freq ~ U(0.05, 0.2), octaves from {4, 8}, Wxy from {1..4} ({2..4} for method 2),
+    Wz ~ U(1e-4, 4e-3).  method 0 | 1 | 2 = both stages | sensor only | simplex only.  A value given for one of the five
+    arguments the reference's augment_syn_* scripts draw themselves replaces that draw (the draw is still made, so the other
+    values do not depend on it)."""
+    rows = []
+    for _ in range(int(n)):
+        k_open, k_med, k_blur = (int(v) for v in rng.choice([3, 5, 7], size=3))
+        sigma, noise = rng.uniform(0.0, 1.5), rng.uniform(0.002, 0.004)
+        seed = int(rng.integers(0, 2 ** 31))
+        freq = rng.uniform(0.05, 0.2)
+        octaves = int(rng.choice([4, 8]))
+        w_xy = int(rng.integers(2, 5)) if int(method) == 2 else int(rng.integers(1, 5))
+        w_z = rng.uniform(0.0001, 0.004)
+        rows.append(_program_row(k_open if shadowClK is None else shadowClK, k_med if shadowMK is None else shadowMK,
+                                 k_blur if blurK is None else blurK, sigma if blurS is None else blurS,
+                                 noise if depthNoise is None else depthNoise, method, freq, octaves, float(w_xy), w_z, seed))
+    return np.stack(rows) if rows else np.zeros((0, ops.DEPTH_AUG_P), np.float64)
+
+
+def augment_depth_batch(depth, mask, programs, z=None, generator=None, ctx=None):
+    """augmentDepth on n depth images in one call: depth [n,H,W] (array or tensor, host or device; converted to float32,
+    millimetres), mask [n,H,W] (non-zero = foreground; None means depth > 0), programs float64 [n, ops.DEPTH_AUG_P] from
+    sample_depth_programs, z [n,h2,w2] the standard normals of the sensor noise (h2, w2 = ops.depth_aug_half_size of H, W;
+    None: torch.randn on the device, from `generator` when given; not drawn when no image has the sensor stage)
+    -> cuda float32 [n,H,W], ready for normals_from_depth_batch."""
+    if len(depth.shape) != 3 or depth.shape[0] < 1 or depth.shape[1] < 8 or depth.shape[2] < 8:
+        raise ValueError("depth must be [n,H,W] with n >= 1 images of at least 8 x 8 pixels, got %s" % (tuple(depth.shape),))
+    d = _depth_stack(depth)
+    n, H, W = (int(v) for v in d.shape)
+    if mask is None:
+        m = (d > 0).to(torch.uint8)
+    else:
+        if tuple(mask.shape) != (n, H, W):
+            raise ValueError("mask must be %s like depth, got %s" % ((n, H, W), tuple(mask.shape)))
+        m = mask if torch.is_tensor(mask) else torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0))
+        m = (m.to(device="cuda") != 0).to(torch.uint8).contiguous()
+    programs = np.ascontiguousarray(programs, np.float64)
+    if programs.shape != (n, ops.DEPTH_AUG_P):
+        raise ValueError("programs must be [%d,%d] (sample_depth_programs), got %s" % (n, ops.DEPTH_AUG_P, programs.shape))
+    h2, w2 = ops.depth_aug_half_size(H), ops.depth_aug_half_size(W)
+    if z is not None:
+        if tuple(z.shape) != (n, h2, w2):
+            raise ValueError("z must be %s, got %s" % ((n, h2, w2), tuple(z.shape)))
+        z = to_device(z, torch.float32)
+    elif programs[:, ops.DEPTH_AUG_PARAMS["sensor"][0]].any():
+        z = torch.randn((n, h2, w2), dtype=torch.float32, device="cuda", generator=generator)
+    return ops.depth_augment(ctx or default_context(), d, m, programs, z, ("depth_f32",))["depth_f32"]
+
+
+def augmentDepth(depth, obj_mask, mask_ori, shadowClK=None, shadowMK=None, blurK=None, blurS=None, depthNoise=None, method=0, rng=None):
+    """The reference's augmentDepth, both signatures: (depth, obj_mask, mask_ori) of Augmentations.py, which draws every
+    parameter itself, and (depth, obj_mask, mask_ori, shadowClK, shadowMK, blurK, blurS, depthNoise, method) of
+    augment_syn_LineMOD.py / augment_syn_Tless.py, which is given five of them and the method switch.  depth [H,W] (numpy,
+    millimetres), mask_ori [H,W] (> 0 = foreground), obj_mask ignored as in the reference -> the augmented depth [H,W] float64
+    (numpy).  The remaining parameters are drawn from `rng` (a numpy Generator; a fresh one by default).  A drop-in for the
+    annotation scripts' own copy."""
+    depth = np.asarray(depth)
+    if depth.ndim != 2:
+        raise ValueError("augmentDepth: depth must be [H,W], got %s" % (depth.shape,))
+    rng = np.random.default_rng() if rng is None else rng
+    programs = sample_depth_programs(rng, 1, method, shadowClK, shadowMK, blurK, blurS, depthNoise)
+    h2, w2 = ops.depth_aug_half_size(depth.shape[0]), ops.depth_aug_half_size(depth.shape[1])
+    z = rng.standard_normal((1, h2, w2), dtype=np.float32)
+    out = augment_depth_batch(depth[None], (np.asarray(mask_ori) > 0)[None], programs, z=z)
+    return out[0].cpu().numpy().astype(np.float64)
