@@ -966,6 +966,93 @@ int pp_det_pr_curve(pp_ctx* ctx, int n_thr, int n_order, int n_class, long long 
 int pp_det_ap(pp_ctx* ctx, int n_thr, int n_order, int n_class, const int* class_offsets, const int* npos, const double* recall,
               const double* prec_env, int mode, double* ap, double* recall_final);
 
+/* ---- segmentation metrics (csrc/mask_eval.hip; pp_det_match_iou in csrc/det_eval.hip) -------------------------------------
+ * The third output of the network, the per-class mask head, and instance masks (utils.scene_gt's mask_visib of ground-truth or
+ * estimated poses): semantic tp / fp / fn against the training target, COCO's mask AP as BOP's segmentation task scores it
+ * (pack -> pairwise IoU -> matching on that IoU -> pp_det_pr_curve / pp_det_ap unchanged) and run-length encodings.  The
+ * reference scores none of this: it thresholds the mask output at 0.5 and writes a picture (linemod_eval.py:336-369); its
+ * rle_encode (annotation_scripts/misc.py:42-51) is pinned through tests/golden/mask_rle.npz.  Integer arithmetic, integer
+ * atomics only (exact in any order) and one float64 division per IoU: byte-identical to the numpy restatement
+ * (tests/mask_eval_np.py) and run to run.  Parity with pycocotools / bop_toolkit is restated, unpinned; the compressed RLE
+ * string, crowd regions and area ranges are out of scope.
+ *
+ * pp_mask_confusion: one pass over the mask head's output.
+ *   in   pred [B,M,C] float32 (device): the sigmoid values; target [B,M,C+1] float32 (device): the training target as
+ *        pp_anchor_targets writes it and pp_count_positives reads it (the last channel, the any-object flag, is not read);
+ *        thresholds [n_thr] float64 on the HOST, 1 <= n_thr <= PP_DET_MAX_THR, any order, not NaN.
+ *   out  counts [T,C,3] int64 (zeroed by the call): tp, fp, fn.  A pixel is predicted at threshold t iff (double)pred > thr_t
+ *        (the reference's obj_mask > 0.5; NaN is not predicted, -0 equals +0); it is set iff target[..., c] != 0.
+ *   A workgroup walks chunks of 16384 consecutive elements of pred, its partial counts as ints in LDS (T C 3 of them, dynamic),
+ *   and folds the non-zero ones into counts with 64-bit integer atomics.
+ *   Errors before anything is launched: n_thr out of range, a NaN threshold, null pointers: PP_ERR_ARG; B, M < 1, C outside
+ *   1..PP_MASK_MAX_CLASS, B M (C + 1) >= 2^31: PP_ERR_SHAPE.
+ *
+ * pp_mask_pack: byte masks to bits.
+ *   in   masks [N,H,W] uint8 (device), non-zero = set.
+ *   out  words [N,ceil(H W / 64)] uint64: bit i of word k is pixel 64 k + i in row-major order, the tail bits of the last word 0;
+ *        area [N] int64; word_range [N,2] int32: the first non-empty word and one past the last, [0, 0) for an empty mask.
+ *   One workgroup of 4 waves per mask; a wave's ballot over 64 pixels is one word.
+ *   Errors: N < 0, H or W < 1, H W >= 2^31: PP_ERR_SHAPE; null pointers (N > 0): PP_ERR_ARG.  N = 0 does nothing.
+ *
+ * pp_mask_iou_pairs: the IoU of every (detection slot, ground truth) pair of each image.
+ *   in   detections in padded slots: slot d of image b is packed mask b D + d of det_words [B D,n_word], det_area, det_range
+ *        (pp_mask_pack's outputs); det_labels [B,D] int32 or NULL: a slot with a label < 0 is padding, its mask is not read and
+ *        its pairs are 0.  Ground truth packed over the batch, gt_words [G,n_word], gt_area, gt_range, with gt_offsets [B+1]
+ *        given twice as pp_det_match's are (the HOST copy is checked, the kernel reads the device copy).
+ *   out  iou [D G] float64: the pair (b, d, g) at pair_offsets[b] + d ng_b + g, pair_offsets[b] = D gt_offsets[b] (the images
+ *        in order, each a [D,ng_b] matrix); inter [D G] int64 in the same layout, or NULL.
+ *        inter = sum of popcount(det word & gt word) over the overlap of the two word ranges; iou = inter / (area_d + area_g -
+ *        inter), the one division in float64 of the exact integers; 0.0 when the union is 0.
+ *   Tiling: a workgroup takes PP_MASK_IOU_TILE_DET slots x PP_MASK_IOU_TILE_GT ground truths of one image; each of its waves
+ *   owns one slot, strides its lanes over the slot's word range and ANDs each word with the tile's ground truths.
+ *   Errors before anything is launched: D > PP_DET_MAX_DET, an image with more than PP_DET_MAX_GT ground truths, offsets that
+ *   decrease or do not run from 0 to G, D G >= 2^31, batch < 1, null pointers: PP_ERR_ARG; H W >= 2^31, too many tiles:
+ *   PP_ERR_SHAPE.  D = 0 or G = 0: nothing to write, PP_OK.
+ *
+ * pp_det_match_iou: pp_det_match with the IoU read from that matrix (iou [D G], never NULL: any one double when there are no
+ *   pairs) instead of computed from boxes.  Ranking, tie-breaks, both rules, gt_ignore, padding, npos, outputs, limits and
+ *   errors are pp_det_match's (the same kernel with a second IoU source; under PP_DET_RULE_REFERENCE the matrix stands where
+ *   the "+1" IoU stood), plus D G >= 2^31: PP_ERR_ARG.  Its outputs feed pp_det_pr_curve / pp_det_ap.
+ *
+ * pp_mask_rle: run lengths of byte masks, COCO's uncompressed `counts`: the lengths of the alternating runs starting with the
+ *   zero run (length 0 when the first pixel is set), in order PP_MASK_ORDER_ROW (row-major: the reference's rle_encode) or
+ *   PP_MASK_ORDER_COLUMN (column-major: COCO's).
+ *   in   masks [N,H,W] uint8 (device); workspace of pp_mask_rle_workspace_bytes(N) bytes; capacity: the int32 entries counts holds.
+ *   out  run_offsets [N+1] int32 (device) and run_offsets_host [N+1] (HOST, always written once the arguments pass): the runs
+ *        of mask n are counts[run_offsets[n] .. run_offsets[n+1]); counts [capacity] int32 (device).
+ *   Three launches: count the boundaries per mask (a wave's ballot flags 64 positions), scan the counts, then write each run
+ *   at its place.  Between the second and the third the call copies run_offsets to the host and waits for the stream (it is
+ *   not capturable): where the runs exceed capacity it returns PP_ERR_ARG naming the first mask that does not fit and the
+ *   total needed, and writes NOTHING to counts -- no run is ever truncated.
+ *   Errors before anything is launched: N < 1, N (H W + 1) >= 2^31: PP_ERR_SHAPE; unknown order, null pointers, a workspace
+ *   that is too small, capacity < 0: PP_ERR_ARG.
+ *
+ * pp_mask_from_rle: the runs back to byte masks of 0 / 255.  run_offsets and counts on the device and the same on the HOST:
+ *   the host copy is checked before anything is launched -- offsets from 0 that do not decrease, no negative length, each
+ *   mask's lengths adding up to H W exactly, else PP_ERR_ARG.  Shapes and order as pp_mask_rle. */
+#define PP_MASK_MAX_CLASS 256
+#define PP_MASK_IOU_TILE_DET 4
+#define PP_MASK_IOU_TILE_GT 4
+#define PP_MASK_ORDER_ROW 0
+#define PP_MASK_ORDER_COLUMN 1
+int pp_mask_confusion(pp_ctx* ctx, int batch, int n_pix, int n_class, const float* pred, const float* target, int n_thr,
+                      const double* thresholds, long long* counts);
+int pp_mask_pack(pp_ctx* ctx, int n_mask, int H, int W, const unsigned char* masks, unsigned long long* words, long long* area,
+                 int* word_range);
+int pp_mask_iou_pairs(pp_ctx* ctx, int batch, int n_det, int n_gt, int H, int W, const unsigned long long* det_words,
+                      const long long* det_area, const int* det_range, const int* det_labels, const unsigned long long* gt_words,
+                      const long long* gt_area, const int* gt_range, const int* gt_offsets_host, const int* gt_offsets_dev, double* iou,
+                      long long* inter);
+int pp_det_match_iou(pp_ctx* ctx, int batch, int n_det, int n_gt, int n_class, const double* iou, const double* det_scores,
+                     const int* det_labels, const int* gt_labels, const unsigned char* gt_ignore, const int* gt_offsets_host,
+                     const int* gt_offsets_dev, int n_thr, const double* thresholds, int rule, int* match, unsigned char* det_ignored,
+                     int* npos);
+size_t pp_mask_rle_workspace_bytes(int n_mask);
+int pp_mask_rle(pp_ctx* ctx, int n_mask, int H, int W, int order, const unsigned char* masks, void* workspace, size_t workspace_bytes,
+                long long capacity, int* run_offsets, int* run_offsets_host, int* counts);
+int pp_mask_from_rle(pp_ctx* ctx, int n_mask, int H, int W, int order, const int* run_offsets_host, const int* counts_host,
+                     const int* run_offsets, const int* counts, unsigned char* masks);
+
 /* ---- normal images from depth maps (csrc/depth_image.hip) ----------------------------------------------------------------
  * The reference's get_normal (annotation_scripts/Augmentations.py:394-467, copied into its annotate_* / augment_* scripts):
  * the surface-normal image it writes as every sample's _dep.png, and the smoothed depth.  float64 from the first filter tap on,

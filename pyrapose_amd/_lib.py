@@ -216,6 +216,13 @@ _SIGS = {
     "pp_det_match": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, C.POINTER(_i), _p, _i, C.POINTER(_d), _i, _p, _p, _p]),
     "pp_det_pr_curve": (_i, [_p, _i, _i, _i, _ll, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "pp_det_ap": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p]),
+    "pp_mask_confusion": (_i, [_p, _i, _i, _i, _p, _p, _i, C.POINTER(_d), _p]),
+    "pp_mask_pack": (_i, [_p, _i, _i, _i, _p, _p, _p, _p]),
+    "pp_mask_iou_pairs": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, C.POINTER(_i), _p, _p, _p]),
+    "pp_det_match_iou": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, C.POINTER(_i), _p, _i, C.POINTER(_d), _i, _p, _p, _p]),
+    "pp_mask_rle_workspace_bytes": (_sz, [_i]),
+    "pp_mask_rle": (_i, [_p, _i, _i, _i, _i, _p, _p, _sz, _ll, _p, C.POINTER(_i), _p]),
+    "pp_mask_from_rle": (_i, [_p, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), _p, _p, _p]),
     "pp_depth_normals_workspace_bytes": (_sz, [_i, _i, _i]),
     "pp_depth_normals_f64": (_i, [_p, _i, _i, _i, _p, _p, C.POINTER(_d), _i, _p, _sz, _p, _p, _p, _p]),
     "pp_depth_augment_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -15,6 +15,8 @@
 #define DET_MAX_GT PP_DET_MAX_GT    // ground truth per image it holds
 #define DET_MAX_THR PP_DET_MAX_THR  // thresholds per launch = waves per workgroup
 #define DET_CHUNK PP_DET_SCAN_CHUNK // detections per scan step of det_pr_curve_kernel = its workgroup size
+#define DET_IOU_BOXES 0  // det_match_kernel computes the IoU from the two boxes (pp_det_match)
+#define DET_IOU_MATRIX 1 // it reads the IoU from a pair matrix, pp_mask_iou_pairs' layout (pp_det_match_iou)
 
 struct det_thresholds {
   double v[DET_MAX_THR];
@@ -33,7 +35,10 @@ __device__ __forceinline__ unsigned long long det_key(double s) {
 //   3. wave t walks s_order.  Lane l owns the ground truth l, l + 64, ... of the image: it alone reads and writes their taken
 //      flags (s_taken[t][.]) and computes their IoU with the detection; a butterfly picks the wave's winner under the rule's
 //      tie-break; the owner of the winner decides and marks it, lane 0 writes the outcome.
-template <int RULE>
+// SRC = DET_IOU_MATRIX: `det_boxes` is the pair matrix instead (the IoU of slot d and ground truth g of image b at
+// D * gt_offsets[b] + d * ng_b + g), `gt_boxes` is not read and s_gt is not filled.  The kernel's arguments are the same for
+// both sources, so the box instantiations are the instructions they were before the second source existed.
+template <int RULE, int SRC>
 __global__ __launch_bounds__(64 * DET_MAX_THR) void det_match_kernel(
     int D, int C, int T, const double* __restrict__ det_boxes, const double* __restrict__ det_scores, const int* __restrict__ det_labels,
     const double* __restrict__ gt_boxes, const int* __restrict__ gt_labels, const unsigned char* __restrict__ gt_ignore,
@@ -51,7 +56,7 @@ __global__ __launch_bounds__(64 * DET_MAX_THR) void det_match_kernel(
   const int g0 = gt_offsets[b];
   int ng = gt_offsets[b + 1] - g0;
   ng = ng < 0 ? 0 : (ng > DET_MAX_GT ? DET_MAX_GT : ng);  // (the entry point has checked the host copy)
-  const double* box_b = det_boxes + (size_t)b * D * 4;
+  const double* box_b = det_boxes + (SRC == DET_IOU_BOXES ? (size_t)b * D * 4 : (size_t)D * (size_t)g0);
   const double* score_b = det_scores + (size_t)b * D;
   const int* label_b = det_labels + (size_t)b * D;
   int* match_t = match + ((size_t)t * B + b) * D;
@@ -59,9 +64,11 @@ __global__ __launch_bounds__(64 * DET_MAX_THR) void det_match_kernel(
 
   if (tid == 0) s_nvalid = 0;
   for (int g = tid; g < ng; g += nthr) {
-    const double* p = gt_boxes + (size_t)(g0 + g) * 4;
-    const double x1 = p[0], y1 = p[1], x2 = p[2], y2 = p[3];
-    s_gt[g][0] = x1; s_gt[g][1] = y1; s_gt[g][2] = x2; s_gt[g][3] = y2;
+    if (SRC == DET_IOU_BOXES) {
+      const double* p = gt_boxes + (size_t)(g0 + g) * 4;
+      const double x1 = p[0], y1 = p[1], x2 = p[2], y2 = p[3];
+      s_gt[g][0] = x1; s_gt[g][1] = y1; s_gt[g][2] = x2; s_gt[g][3] = y2;
+    }
     const int l = gt_labels[g0 + g];
     const bool ig = gt_ignore != nullptr && gt_ignore[g0 + g] != 0;
     s_meta[g] = (l < 0 || l >= C) ? (int)0x80000000 : (ig ? -1 - l : l);
@@ -116,7 +123,11 @@ __global__ __launch_bounds__(64 * DET_MAX_THR) void det_match_kernel(
   for (int k = 0; k < nvalid; ++k) {
     const int d = s_order[k];
     const int label = label_b[d];
-    const double dx1 = box_b[4 * d], dy1 = box_b[4 * d + 1], dx2 = box_b[4 * d + 2], dy2 = box_b[4 * d + 3];
+    double dx1 = 0.0, dy1 = 0.0, dx2 = 0.0, dy2 = 0.0;
+    if (SRC == DET_IOU_BOXES) {
+      dx1 = box_b[4 * d]; dy1 = box_b[4 * d + 1]; dx2 = box_b[4 * d + 2]; dy2 = box_b[4 * d + 3];
+    }
+    const double* iou_d = box_b + (size_t)d * ng;  // (SRC = DET_IOU_MATRIX only)
     // this lane's candidate: `cls` 1 for a ground truth that is not ignored, 0 for an ignored one, -1 for none
     int best_g = -1, best_cls = -1;
     double best = 0.0;
@@ -124,8 +135,13 @@ __global__ __launch_bounds__(64 * DET_MAX_THR) void det_match_kernel(
       const int m = s_meta[g];
       if (RULE == PP_DET_RULE_REFERENCE) {
         if (m != label) continue;
-        const double gx1 = s_gt[g][0], gy1 = s_gt[g][1], gx2 = s_gt[g][2], gy2 = s_gt[g][3];
-        const double v = iou_plus1(dx1, dy1, dx2, dy2, gx1, gy1, gx2, gy2, (gx2 - gx1 + 1) * (gy2 - gy1 + 1));
+        double v;
+        if (SRC == DET_IOU_BOXES) {
+          const double gx1 = s_gt[g][0], gy1 = s_gt[g][1], gx2 = s_gt[g][2], gy2 = s_gt[g][3];
+          v = iou_plus1(dx1, dy1, dx2, dy2, gx1, gy1, gx2, gy2, (gx2 - gx1 + 1) * (gy2 - gy1 + 1));
+        } else {
+          v = iou_d[g];
+        }
         if (best_g < 0 || v > best) {  // first maximum: ascending g, strict >
           best = v;
           best_g = g;
@@ -134,8 +150,13 @@ __global__ __launch_bounds__(64 * DET_MAX_THR) void det_match_kernel(
       } else {
         const int cls = m == label ? 1 : (m == -1 - label ? 0 : -1);
         if (cls < 0 || s_taken[t][g]) continue;
-        const double gx1 = s_gt[g][0], gy1 = s_gt[g][1], gx2 = s_gt[g][2], gy2 = s_gt[g][3];
-        const double v = iou_plain(dx1, dy1, dx2, dy2, gx1, gy1, gx2, gy2, (gx2 - gx1) * (gy2 - gy1));
+        double v;
+        if (SRC == DET_IOU_BOXES) {
+          const double gx1 = s_gt[g][0], gy1 = s_gt[g][1], gx2 = s_gt[g][2], gy2 = s_gt[g][3];
+          v = iou_plain(dx1, dy1, dx2, dy2, gx1, gy1, gx2, gy2, (gx2 - gx1) * (gy2 - gy1));
+        } else {
+          v = iou_d[g];
+        }
         if (!(v >= thr_coco)) continue;
         // a ground truth that is not ignored beats an ignored one (the search stops before them); then the higher IoU; then the
         // later one in visiting order (ascending g within each kind)
@@ -195,44 +216,71 @@ static __global__ __launch_bounds__(POSE_TILE) void det_npos_kernel(int n_gt, co
   if (tid == 0) npos[c] = s[0];
 }
 
-extern "C" int pp_det_match(pp_ctx* ctx, int batch, int n_det, int n_gt, int n_class, const double* det_boxes, const double* det_scores,
-                            const int* det_labels, const double* gt_boxes, const int* gt_labels, const unsigned char* gt_ignore,
-                            const int* gt_offsets_host, const int* gt_offsets_dev, int n_thr, const double* thresholds, int rule,
-                            int* match, unsigned char* det_ignored, int* npos) {
+// pp_det_match and pp_det_match_iou: the common checks and the two launches.  iou == nullptr: boxes.
+static int det_match_launch(pp_ctx* ctx, const char* who, int batch, int n_det, int n_gt, int n_class, const double* det_boxes,
+                            const double* iou, const double* det_scores, const int* det_labels, const double* gt_boxes,
+                            const int* gt_labels, const unsigned char* gt_ignore, const int* gt_offsets_host, const int* gt_offsets_dev,
+                            int n_thr, const double* thresholds, int rule, int* match, unsigned char* det_ignored, int* npos) {
+  const bool boxes = iou == nullptr;
   PP_REQUIRE_CTX(ctx);
-  PP_CHECK_ARG(ctx, rule == PP_DET_RULE_REFERENCE || rule == PP_DET_RULE_COCO, PP_ERR_ARG, "pp_det_match: unknown rule %d", rule);
-  PP_CHECK_ARG(ctx, n_thr >= 1 && n_thr <= DET_MAX_THR, PP_ERR_ARG, "pp_det_match: need 1..%d thresholds, got %d", DET_MAX_THR, n_thr);
-  PP_CHECK_ARG(ctx, batch >= 1 && n_class >= 1 && n_gt >= 0, PP_ERR_ARG, "pp_det_match: batch and n_class must be >= 1, n_gt >= 0");
-  PP_CHECK_ARG(ctx, n_det >= 0 && n_det <= DET_MAX_DET, PP_ERR_ARG, "pp_det_match: %d detection slots per image, the limit is %d", n_det,
+  PP_CHECK_ARG(ctx, rule == PP_DET_RULE_REFERENCE || rule == PP_DET_RULE_COCO, PP_ERR_ARG, "%s: unknown rule %d", who, rule);
+  PP_CHECK_ARG(ctx, n_thr >= 1 && n_thr <= DET_MAX_THR, PP_ERR_ARG, "%s: need 1..%d thresholds, got %d", who, DET_MAX_THR, n_thr);
+  PP_CHECK_ARG(ctx, batch >= 1 && n_class >= 1 && n_gt >= 0, PP_ERR_ARG, "%s: batch and n_class must be >= 1, n_gt >= 0", who);
+  PP_CHECK_ARG(ctx, n_det >= 0 && n_det <= DET_MAX_DET, PP_ERR_ARG, "%s: %d detection slots per image, the limit is %d", who, n_det,
                DET_MAX_DET);
-  PP_CHECK_ARG(ctx, (long long)n_thr * batch * n_det < (1ll << 31), PP_ERR_ARG, "pp_det_match: T * batch * n_det must stay below 2^31");
-  PP_CHECK_ARG(ctx, thresholds && gt_offsets_host && gt_offsets_dev && npos, PP_ERR_ARG, "pp_det_match: null argument");
-  PP_CHECK_ARG(ctx, n_det == 0 || (det_boxes && det_scores && det_labels && match && det_ignored), PP_ERR_ARG,
-               "pp_det_match: null detection tensor");
-  PP_CHECK_ARG(ctx, n_gt == 0 || (gt_boxes && gt_labels), PP_ERR_ARG, "pp_det_match: null ground-truth tensor");
+  PP_CHECK_ARG(ctx, (long long)n_thr * batch * n_det < (1ll << 31), PP_ERR_ARG, "%s: T * batch * n_det must stay below 2^31", who);
+  PP_CHECK_ARG(ctx, boxes || (long long)n_det * n_gt < (1ll << 31), PP_ERR_ARG, "%s: n_det * n_gt pairs must stay below 2^31", who);
+  PP_CHECK_ARG(ctx, thresholds && gt_offsets_host && gt_offsets_dev && npos, PP_ERR_ARG, "%s: null argument", who);
+  PP_CHECK_ARG(ctx, n_det == 0 || ((boxes ? det_boxes != nullptr : true) && det_scores && det_labels && match && det_ignored), PP_ERR_ARG,
+               "%s: null detection tensor", who);
+  PP_CHECK_ARG(ctx, n_gt == 0 || ((boxes ? gt_boxes != nullptr : true) && gt_labels), PP_ERR_ARG, "%s: null ground-truth tensor", who);
   PP_CHECK_ARG(ctx, rule == PP_DET_RULE_COCO || gt_ignore == nullptr, PP_ERR_ARG,
-               "pp_det_match: the reference rule has no ignored ground truth (gt_ignore must be NULL)");
+               "%s: the reference rule has no ignored ground truth (gt_ignore must be NULL)", who);
   det_thresholds thr = {};
   for (int t = 0; t < n_thr; ++t) {
     const double v = thresholds[t];
     PP_CHECK_ARG(ctx, v >= 0.0 && v <= 1.0 && (t == 0 || v > thresholds[t - 1]), PP_ERR_ARG,
-                 "pp_det_match: thresholds must increase within [0, 1]");
+                 "%s: thresholds must increase within [0, 1]", who);
     thr.v[t] = v;
   }
-  PP_CHECK_ARG(ctx, gt_offsets_host[0] == 0 && gt_offsets_host[batch] == n_gt, PP_ERR_ARG, "pp_det_match: gt_offsets must run from 0 to n_gt");
+  PP_CHECK_ARG(ctx, gt_offsets_host[0] == 0 && gt_offsets_host[batch] == n_gt, PP_ERR_ARG, "%s: gt_offsets must run from 0 to n_gt", who);
   for (int b = 0; b < batch; ++b) {
     const int n = gt_offsets_host[b + 1] - gt_offsets_host[b];
-    PP_CHECK_ARG(ctx, n >= 0, PP_ERR_ARG, "pp_det_match: gt_offsets decrease at image %d", b);
-    PP_CHECK_ARG(ctx, n <= DET_MAX_GT, PP_ERR_ARG, "pp_det_match: image %d has %d ground truths, the limit is %d", b, n, DET_MAX_GT);
+    PP_CHECK_ARG(ctx, n >= 0, PP_ERR_ARG, "%s: gt_offsets decrease at image %d", who, b);
+    PP_CHECK_ARG(ctx, n <= DET_MAX_GT, PP_ERR_ARG, "%s: image %d has %d ground truths, the limit is %d", who, b, n, DET_MAX_GT);
   }
   hipLaunchKernelGGL(det_npos_kernel, dim3(n_class), dim3(POSE_TILE), 0, ctx->stream, n_gt, gt_labels, gt_ignore, npos);
-  if (n_det > 0) {
-    auto kernel = rule == PP_DET_RULE_REFERENCE ? det_match_kernel<PP_DET_RULE_REFERENCE> : det_match_kernel<PP_DET_RULE_COCO>;
+  if (n_det > 0 && boxes) {
+    auto kernel = rule == PP_DET_RULE_REFERENCE ? det_match_kernel<PP_DET_RULE_REFERENCE, DET_IOU_BOXES>
+                                                : det_match_kernel<PP_DET_RULE_COCO, DET_IOU_BOXES>;
     hipLaunchKernelGGL(kernel, dim3(batch), dim3(64 * n_thr), 0, ctx->stream, n_det, n_class, n_thr, det_boxes, det_scores, det_labels,
                        gt_boxes, gt_labels, gt_ignore, gt_offsets_dev, thr, match, det_ignored);
+  } else if (n_det > 0 && (n_gt > 0 || iou)) {
+    auto kernel = rule == PP_DET_RULE_REFERENCE ? det_match_kernel<PP_DET_RULE_REFERENCE, DET_IOU_MATRIX>
+                                                : det_match_kernel<PP_DET_RULE_COCO, DET_IOU_MATRIX>;
+    hipLaunchKernelGGL(kernel, dim3(batch), dim3(64 * n_thr), 0, ctx->stream, n_det, n_class, n_thr, iou, det_scores, det_labels,
+                       (const double*)nullptr, gt_labels, gt_ignore, gt_offsets_dev, thr, match, det_ignored);
   }
-  PP_CHECK_LAUNCH(ctx, "pp_det_match");
+  PP_CHECK_LAUNCH(ctx, who);
   return PP_OK;
+}
+
+extern "C" int pp_det_match(pp_ctx* ctx, int batch, int n_det, int n_gt, int n_class, const double* det_boxes, const double* det_scores,
+                            const int* det_labels, const double* gt_boxes, const int* gt_labels, const unsigned char* gt_ignore,
+                            const int* gt_offsets_host, const int* gt_offsets_dev, int n_thr, const double* thresholds, int rule,
+                            int* match, unsigned char* det_ignored, int* npos) {
+  return det_match_launch(ctx, "pp_det_match", batch, n_det, n_gt, n_class, det_boxes, nullptr, det_scores, det_labels, gt_boxes, gt_labels,
+                          gt_ignore, gt_offsets_host, gt_offsets_dev, n_thr, thresholds, rule, match, det_ignored, npos);
+}
+
+extern "C" int pp_det_match_iou(pp_ctx* ctx, int batch, int n_det, int n_gt, int n_class, const double* iou, const double* det_scores,
+                                const int* det_labels, const int* gt_labels, const unsigned char* gt_ignore, const int* gt_offsets_host,
+                                const int* gt_offsets_dev, int n_thr, const double* thresholds, int rule, int* match,
+                                unsigned char* det_ignored, int* npos) {
+  PP_REQUIRE_CTX(ctx);
+  PP_CHECK_ARG(ctx, iou != nullptr, PP_ERR_ARG, "pp_det_match_iou: null IoU matrix (one double is enough when there are no pairs)");
+  return det_match_launch(ctx, "pp_det_match_iou", batch, n_det, n_gt, n_class, nullptr, iou, det_scores, det_labels, nullptr, gt_labels,
+                          gt_ignore, gt_offsets_host, gt_offsets_dev, n_thr, thresholds, rule, match, det_ignored, npos);
 }
 
 // One workgroup of DET_CHUNK threads per (class, threshold): the class's segment of `order` in chunks with a carry.

@@ -1408,6 +1408,213 @@ def det_ap(ctx, class_offsets, npos, recall, prec_env, integration="area", check
     return ap, rf
 
 
+MASK_MAX_CLASS = 256       # PP_MASK_MAX_CLASS: classes whose partial counts pp_mask_confusion holds in LDS
+MASK_IOU_TILE = (4, 4)     # PP_MASK_IOU_TILE_DET x PP_MASK_IOU_TILE_GT: the pairs one workgroup of pp_mask_iou_pairs takes
+MASK_ORDERS = {"row": 0, "column": 1, 0: 0, 1: 1}  # PP_MASK_ORDER_*
+_I64 = torch.int64
+
+
+def _host_f64(v):
+    return np.ascontiguousarray(np.asarray(v, np.float64).reshape(-1))
+
+
+def mask_confusion(ctx, pred, target, thresholds=(0.5,)):
+    """(tp, fp, fn) of the mask head's output against its training target (pp_mask_confusion): cuda float32 pred [B,M,C] (sigmoid
+    values) and target [B,M,C+1] (as anchor_targets writes it; the last channel is not read); thresholds: 1..16 host floats.
+    A pixel is predicted iff pred > threshold as a float64 compare (NaN: not predicted), set iff target != 0
+    -> counts int64 [T,C,3]."""
+    what = "mask_confusion"
+    thr = _host_f64(thresholds)
+    T = int(thr.size)
+    if not 1 <= T <= DET_MAX_THR or np.isnan(thr).any():
+        raise ValueError("%s: need 1..%d thresholds that are not NaN, got %d" % (what, DET_MAX_THR, T))
+    pred = _arg(what, "pred", pred, _F32, (None, None, None))
+    B, M, Cc = (int(s) for s in pred.shape)
+    target = _arg(what, "target", target, _F32, (B, M, Cc + 1))
+    if B < 1 or M < 1 or not 1 <= Cc <= MASK_MAX_CLASS or B * M * (Cc + 1) >= 2 ** 31:
+        raise ValueError("%s: need B, M >= 1, 1 <= C <= %d and B * M * (C + 1) < 2^31, got %s" % (what, MASK_MAX_CLASS, list(pred.shape)))
+    counts = _out(pred, (T, Cc, 3), _I64)
+    check_status(lib.pp_mask_confusion(ctx.handle, B, M, Cc, _ptr(pred), _ptr(target), T, thr.ctypes.data_as(C.POINTER(C.c_double)),
+                                       _ptr(counts)), ctx.handle, "pp_mask_confusion")
+    return counts
+
+
+def _mask_stack(what, name, masks):
+    masks = _arg(what, name, masks, _U8, (None, None, None))
+    N, H, W = (int(s) for s in masks.shape)
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError("%s: %s needs H, W >= 1 and H * W < 2^31, got %s" % (what, name, list(masks.shape)))
+    return masks, N, H, W
+
+
+def mask_pack(ctx, masks):
+    """Byte masks to bits (pp_mask_pack): cuda uint8 [N,H,W], non-zero = set -> (words int64 [N,ceil(H W / 64)] holding the
+    uint64 bit patterns: bit i of word k is pixel 64 k + i in row-major order, tail bits 0; area int64 [N]; word_range int32
+    [N,2]: first non-empty word and one past the last, [0, 0) for an empty mask)."""
+    what = "mask_pack"
+    masks, N, H, W = _mask_stack(what, "masks", masks)
+    n_word = (H * W + 63) // 64
+    words, area, rng = _out(masks, (N, n_word), _I64), _out(masks, (N,), _I64), _out(masks, (N, 2), _I32)
+    check_status(lib.pp_mask_pack(ctx.handle, N, H, W, _ptr(masks), _ptr(words), _ptr(area), _ptr(rng)), ctx.handle, "pp_mask_pack")
+    return words, area, rng
+
+
+def _det_gt_offsets(what, gt_offsets, G, B):
+    gt_offsets, off = _check_offsets(what, gt_offsets, G, True, name="gt_offsets")
+    if off.size != B + 1:
+        raise ValueError("%s: gt_offsets must hold B + 1 = %d entries, got %d" % (what, B + 1, off.size))
+    if B and int(np.diff(off).max()) > DET_MAX_GT:
+        raise ValueError("%s: an image has %d ground truths, the limit is %d" % (what, int(np.diff(off).max()), DET_MAX_GT))
+    return gt_offsets, np.ascontiguousarray(off, np.int32)
+
+
+def mask_iou_pairs(ctx, det_packed, gt_packed, gt_offsets, shape, n_det, det_labels=None, want_inter=False):
+    """IoU of every (detection slot, ground truth) pair of each image (pp_mask_iou_pairs).  det_packed / gt_packed: the
+    (words, area, word_range) triples of mask_pack over the detections' [B * D] slots (slot d of image b is mask b * D + d)
+    and over the [G] ground truths; gt_offsets int32 [B+1] (cuda); shape = (H, W) of the masks; n_det = D; det_labels int32
+    [B,D] or None: slots with a label < 0 are padding (not read, IoU 0) -> (iou float64 [D * G], pair_offsets int64 numpy
+    [B+1]: pair (b, d, g) sits at pair_offsets[b] + d * ng_b + g; with want_inter also inter int64 [D * G])."""
+    what = "mask_iou_pairs"
+    H, W = int(shape[0]), int(shape[1])
+    D = int(n_det)
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError("%s: need H, W >= 1 and H * W < 2^31" % what)
+    n_word = (H * W + 63) // 64
+    dw = _arg(what, "det words", det_packed[0], _I64, (None, n_word))
+    BD = int(dw.shape[0])
+    if D < 0 or D > DET_MAX_DET or (D == 0 and BD) or (D and BD % D):
+        raise ValueError("%s: %d packed detection masks are no multiple of D = %d <= %d" % (what, BD, D, DET_MAX_DET))
+    da, dr = _arg(what, "det area", det_packed[1], _I64, (BD,)), _arg(what, "det word_range", det_packed[2], _I32, (BD, 2))
+    gw = _arg(what, "gt words", gt_packed[0], _I64, (None, n_word))
+    G = int(gw.shape[0])
+    ga, gr = _arg(what, "gt area", gt_packed[1], _I64, (G,)), _arg(what, "gt word_range", gt_packed[2], _I32, (G, 2))
+    gt_offsets = _arg(what, "gt_offsets", gt_offsets, _I32, (None,))
+    B = BD // D if D else int(gt_offsets.numel()) - 1
+    if B < 1 or D * G >= 2 ** 31:
+        raise ValueError("%s: need B >= 1 and D * G < 2^31 pairs, got B = %d, D = %d, G = %d" % (what, B, D, G))
+    det_labels = _arg(what, "det_labels", det_labels, _I32, (B, D), optional=True)
+    gt_offsets, off = _det_gt_offsets(what, gt_offsets, G, B)
+    iou = _out(gw, (D * G,))
+    inter = _out(gw, (D * G,), _I64) if want_inter else None
+    check_status(lib.pp_mask_iou_pairs(ctx.handle, B, D, G, H, W, _ptr(dw), _ptr(da), _ptr(dr), _ptr(det_labels), _ptr(gw), _ptr(ga),
+                                       _ptr(gr), off.ctypes.data_as(C.POINTER(C.c_int)), _ptr(gt_offsets), _ptr(iou), _ptr(inter)),
+                 ctx.handle, "pp_mask_iou_pairs")
+    pair_offsets = off.astype(np.int64) * D
+    return (iou, pair_offsets, inter) if want_inter else (iou, pair_offsets)
+
+
+def det_match_iou(ctx, iou, det_scores, det_labels, gt_labels, gt_offsets, n_class, thresholds, rule="coco", gt_ignore=None, check=True):
+    """det_match with the IoU read from a pair matrix instead of computed from boxes (pp_det_match_iou): iou float64 [D * G]
+    in mask_iou_pairs' layout; everything else -- ranking, tie-breaks, both rules, gt_ignore, padding, the limits, check -- as
+    det_match -> (match int32 [T,B,D], det_ignored uint8 [T,B,D], npos int32 [n_class]), which feed det_pr_curve / det_ap."""
+    what = "det_match_iou"
+    if rule not in DET_RULES:
+        raise ValueError("%s: unknown rule %r (reference | coco)" % (what, rule))
+    thr = _host_f64(thresholds)
+    T = int(thr.size)
+    if not 1 <= T <= DET_MAX_THR:
+        raise ValueError("%s: need 1..%d thresholds, got %d" % (what, DET_MAX_THR, T))
+    if not (np.all(thr >= 0.0) and np.all(thr <= 1.0) and np.all(np.diff(thr) > 0.0)):
+        raise ValueError("%s: thresholds must increase within [0, 1]" % what)
+    n_class = int(n_class)
+    if n_class < 1:
+        raise ValueError("%s: n_class must be >= 1" % what)
+    det_scores = _arg(what, "det_scores", det_scores, _F64, (None, None))
+    B, D = (int(s) for s in det_scores.shape)
+    det_labels = _arg(what, "det_labels", det_labels, _I32, (B, D))
+    gt_labels = _arg(what, "gt_labels", gt_labels, _I32, (None,))
+    G = int(gt_labels.shape[0])
+    if B < 1 or D > DET_MAX_DET or T * B * D >= 2 ** 31 or D * G >= 2 ** 31:
+        raise ValueError("%s: need B >= 1, D <= %d, T * B * D < 2^31 and D * G < 2^31, got B = %d, D = %d, G = %d" %
+                         (what, DET_MAX_DET, B, D, G))
+    iou = _arg(what, "iou", iou, _F64, (D * G,))
+    gt_ignore = _arg(what, "gt_ignore", gt_ignore, _U8, (G,), optional=True)
+    if gt_ignore is not None and rule == "reference":
+        raise ValueError("%s: the reference rule has no ignored ground truth (gt_ignore must be None)" % what)
+    gt_offsets, off = _det_gt_offsets(what, gt_offsets, G, B)
+    if check:
+        _det_labels_ok(what, "det_labels", det_labels, n_class, True)
+        _det_labels_ok(what, "gt_labels", gt_labels, n_class, False)
+    if iou.numel() == 0:
+        iou = _out(det_scores, (1,), fill=0.0)  # (the entry point wants a pointer)
+    match, ign = _out(det_scores, (T, B, D), _I32), _out(det_scores, (T, B, D), _U8)
+    npos = _out(det_scores, (n_class,), _I32)
+    check_status(lib.pp_det_match_iou(ctx.handle, B, D, G, n_class, _ptr(iou), _ptr(det_scores), _ptr(det_labels), _ptr(gt_labels),
+                                      _ptr(gt_ignore), off.ctypes.data_as(C.POINTER(C.c_int)), _ptr(gt_offsets), T,
+                                      thr.ctypes.data_as(C.POINTER(C.c_double)), DET_RULES[rule], _ptr(match), _ptr(ign), _ptr(npos)),
+                 ctx.handle, "pp_det_match_iou")
+    return match, ign, npos
+
+
+def _mask_order(what, order):
+    if order not in MASK_ORDERS:
+        raise ValueError("%s: unknown order %r (row | column)" % (what, order))
+    return MASK_ORDERS[order]
+
+
+def mask_rle(ctx, masks, order="row", capacity=None):
+    """Run lengths of byte masks (pp_mask_rle): cuda uint8 [N,H,W]; order 'row' (row-major, the reference's rle_encode) or
+    'column' (COCO's); capacity: the int32 entries to allocate for the runs, default N * (H * W + 1) bounded by 2^24 and grown
+    once to what the library reports when that is too few (a capacity given by the caller is never grown: ValueError)
+    -> (run_offsets int64 numpy [N+1], counts int32 cuda [run_offsets[N]]): COCO's uncompressed counts of mask n are
+    counts[run_offsets[n]:run_offsets[n+1]], starting with the length of the leading zero run (0 when the first pixel is set)."""
+    what = "mask_rle"
+    order = _mask_order(what, order)
+    masks, N, H, W = _mask_stack(what, "masks", masks)
+    if N < 1 or N * (H * W + 1) >= 2 ** 31:
+        raise ValueError("%s: need N >= 1 and N * (H * W + 1) < 2^31, got %s" % (what, list(masks.shape)))
+    nbytes = lib.pp_mask_rle_workspace_bytes(N)
+    ws = _workspace(nbytes)
+    offs = _out(masks, (N + 1,), _I32)
+    host = np.zeros(N + 1, np.int32)
+    given = capacity is not None
+    cap = int(capacity) if given else min(N * (H * W + 1), 1 << 24)
+    if cap < 0:
+        raise ValueError("%s: capacity must be >= 0" % what)
+    while True:
+        counts = _out(masks, (max(cap, 1),), _I32)
+        rc = lib.pp_mask_rle(ctx.handle, N, H, W, order, _ptr(masks), _ptr(ws), nbytes, cap, _ptr(offs),
+                             host.ctypes.data_as(C.POINTER(C.c_int)), _ptr(counts))
+        if rc != 0 and not given and int(host[N]) > cap:
+            cap = int(host[N])
+            continue
+        check_status(rc, ctx.handle, "pp_mask_rle")
+        return host.astype(np.int64), counts[:int(host[N])]
+
+
+def mask_from_rle(ctx, run_offsets, counts, shape, order="row"):
+    """Runs back to byte masks of 0 / 255 (pp_mask_from_rle): run_offsets [N+1] and counts (host arrays or tensors: the host
+    copy is checked, every mask's lengths must add up to H * W) -> cuda uint8 [N,H,W]."""
+    what = "mask_from_rle"
+    order = _mask_order(what, order)
+    H, W = int(shape[0]), int(shape[1])
+    off = np.ascontiguousarray((run_offsets.cpu().numpy() if torch.is_tensor(run_offsets) else np.asarray(run_offsets)).reshape(-1))
+    cnt = np.ascontiguousarray((counts.cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)).reshape(-1))
+    N = int(off.size) - 1
+    if N < 1 or H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError("%s: need N >= 1 masks, H, W >= 1 and H * W < 2^31" % what)
+    if off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != cnt.size or cnt.size >= 2 ** 31:
+        raise ValueError("%s: run_offsets must rise from 0 to the number of counts (%d)" % (what, cnt.size))
+    if cnt.size and (cnt.min() < 0 or cnt.max() >= 2 ** 31):
+        raise ValueError("%s: run lengths must lie in [0, 2^31)" % what)
+    off, cnt = off.astype(np.int32), cnt.astype(np.int32)
+    sums = np.add.reduceat(np.concatenate([cnt.astype(np.int64), [0]]), off[:-1].astype(np.int64)) * (np.diff(off) > 0)
+    if (sums != H * W).any():
+        bad = int(np.nonzero(sums != H * W)[0][0])
+        raise ValueError("%s: the runs of mask %d add up to %d, the image has %d pixels" % (what, bad, int(sums[bad]), H * W))
+    dev = "cuda:%d" % ctx.device
+    off_d = torch.from_numpy(off).to(dev)
+    cnt_d = counts.to(device=dev, dtype=_I32).contiguous().reshape(-1) if torch.is_tensor(counts) and counts.is_cuda \
+        else torch.from_numpy(cnt).to(dev)
+    if cnt_d.numel() == 0:
+        cnt_d = torch.zeros((1,), dtype=_I32, device=dev)
+    masks = torch.empty((N, H, W), dtype=_U8, device=dev)
+    check_status(lib.pp_mask_from_rle(ctx.handle, N, H, W, order, off.ctypes.data_as(C.POINTER(C.c_int)),
+                                      (cnt if cnt.size else np.zeros(1, np.int32)).ctypes.data_as(C.POINTER(C.c_int)), _ptr(off_d),
+                                      _ptr(cnt_d), _ptr(masks)), ctx.handle, "pp_mask_from_rle")
+    return masks
+
+
 DEPTH_NORMALS_TILE = 32   # pixels per edge of the LDS tile of pp_depth_normals_f64's smoothing launch (its halo: 8 more on every side)
 DEPTH_NORMALS_OUTPUTS = {"normals": (_F64, (3,)), "normals_u8": (_U8, (3,)), "depth": (_F64, ()), "signed": (_F64, (3,))}  # in the ABI's order
 

@@ -157,7 +157,8 @@ BOP_PIXELS = tuple(5 * k for k in range(1, 11))
 
 def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, model_diameters, load_depth, K, threshold=0.5, min_votes=10,
                           delta=0.3, tau=20.0, vsd_threshold=0.3, cost_type="step", symmetric_classes=(), gt_translation_scale=0.001,
-                          depth_scale=1000.0, seed=0, refine=None, weighting=None, instances=None, symmetries=None, bop_vsd=None):
+                          depth_scale=1000.0, seed=0, refine=None, weighting=None, instances=None, symmetries=None, bop_vsd=None,
+                          mask_metrics=None):
     """The metric block of tless_eval.py:470-725 (also in occlusion_eval.py / ycbv_eval.py / homebrewed_eval.py) on top of the
     loop of evaluate_add: per detected, annotated class, the rotation / translation errors re / te (correct when re < 5 deg
     and te < 0.05), the reprojection error (< 5 px), VSD against the image's depth (< vsd_threshold) and ADD (ADI for
@@ -183,6 +184,10 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
     gains 'vsd_bop' (ten values) and 'visib_fract' (the visible fraction of the annotation); the result gains vsd_bop_less
     [10 taus, 10 thresholds, C+1] (ok detections with vsd_bop < BOP_FRACTIONS as thresholds of correctness), vsd_bop_less_rate
     and ar_vsd [C+1], its mean over both axes; with symmetries also ar = (ar_vsd + ar_mssd + ar_mspd) / 3, BOP's average recall.
+    mask_metrics: None (nothing below is computed or returned), or a dict of target (index -> the image's mask training target
+    [M,C+1] or [1,M,C+1] as ops.anchor_targets writes it, an array or a device tensor) and optionally thresholds ((0.5,)): the
+    mask output of every scored image is counted against its target on the device (utils.mask_eval.semantic_scores' pass); the
+    result gains mask_counts [T,C,3] (tp, fp, fn over all scored images), mask_iou [T,C] and mask_miou [T].
     Annotations are not dropped from allPoses by their visible fraction (BOP keeps those of at least 10 %): filter in the
     generator, on scene_gt_info.json or on pose_error.visib_fract_batch.
     Returns dict(allPoses, trueDets, less5, rep_less5, vsd_less_t, add_less [len(ADD_FRACTIONS), C+1], add_fractions, the
@@ -205,12 +210,26 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
             raise ValueError("bop_vsd: unknown keys %s (delta | visib_mode | cost_type)" % sorted(unknown))
         bop_vsd = dict(dict(delta=15.0, visib_mode="bop19", cost_type="step"), **bop_vsd)
         vsd_bop_less = np.zeros((len(BOP_FRACTIONS), len(BOP_FRACTIONS), C + 1), np.uint32)
+    if mask_metrics is not None:
+        from . import mask_eval
+        unknown = set(mask_metrics) - {"target", "thresholds"}
+        if unknown or not callable(mask_metrics.get("target")):
+            raise ValueError("mask_metrics: a dict of target (a callable index -> target) and optionally thresholds, got keys %s" %
+                             sorted(mask_metrics))
+        mask_thresholds = tuple(mask_metrics.get("thresholds", (0.5,)))
+        mask_counts = None
     decode_kw = dict(threeD_boxes=threeD_boxes, threshold=threshold, min_votes=min_votes, seed=seed, weighting=weighting)
     refine = None if refine is None else dict(refine, depth_scale=depth_scale)
-    for index, labels, anno, Kc, depth, _mask, pairs_by_class in _scored_images(
+    for index, labels, anno, Kc, depth, mask_out, pairs_by_class in _scored_images(
             generator, predict_on_batch, decode_kw, K, refine, load_depth, models, gt_translation_scale, instances):
         for lab in labels:
             out["allPoses"][lab + 1] += 1
+        if mask_metrics is not None:
+            import torch
+            pred = torch.as_tensor(mask_out)
+            target = torch.as_tensor(mask_metrics["target"](index))
+            c = mask_eval.semantic_scores(pred.reshape(1, -1, pred.shape[-1]), target.reshape(1, -1, target.shape[-1]), mask_thresholds)["counts"]
+            mask_counts = c if mask_counts is None else mask_counts + c
         for cls, pairs in pairs_by_class:
             group = [d for d, _gi in pairs]
             gt = [np.asarray(anno["poses"][gi], np.float64) for _d, gi in pairs]
@@ -277,5 +296,8 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
             out["ar_vsd"] = out["vsd_bop_less_rate"].mean(axis=(0, 1))
             if symmetries is not None:
                 out["ar"] = (out["ar_vsd"] + out["ar_mssd"] + out["ar_mspd"]) / 3.0
+    if mask_metrics is not None and mask_counts is not None:
+        scored = mask_eval.scores_from_counts(mask_counts)
+        out.update(mask_counts=mask_counts, mask_iou=scored["iou"], mask_miou=scored["miou"])
     out.update(add_less=add_less, add_fractions=np.array(ADD_FRACTIONS), errors=errors)
     return out
