@@ -253,9 +253,13 @@ static size_t render_layout(int n_pose, int n_vert, int n_tri, int width, int he
   return total;
 }
 
+// the scan takes the number of (pose, tile) bins as an int and the bin kernel indexes counts / cursor with it
 static bool render_shape_ok(int n_pose, int n_vert, int n_tri, int width, int height) {
-  return n_pose > 0 && n_pose <= 65535 && n_vert > 0 && n_tri > 0 && width > 0 && height > 0 && width <= 16384 && height <= 16384 &&
-         (long long)n_pose * n_tri * BIN_MAX_TILES <= 0x7FFFFFFFLL && (long long)n_pose * n_vert <= 0x7FFFFFFFLL;
+  if (!(n_pose > 0 && n_pose <= 65535 && n_vert > 0 && n_tri > 0 && width > 0 && height > 0 && width <= 16384 && height <= 16384))
+    return false;
+  const long long tiles = (long long)((width + RT - 1) / RT) * ((height + RT - 1) / RT);
+  return (long long)n_pose * n_tri * BIN_MAX_TILES <= 0x7FFFFFFFLL && (long long)n_pose * n_vert <= 0x7FFFFFFFLL &&
+         (long long)n_pose * tiles <= 0x7FFFFFFFLL;
 }
 
 extern "C" size_t pp_render_workspace_bytes(int n_pose, int n_vert, int n_tri, int width, int height) {
@@ -475,7 +479,8 @@ __device__ __forceinline__ unsigned char rgb_to_u8(float v) { return (unsigned c
 // the two checks every entry point words alike, under its own name
 static int render_check_shape(pp_ctx* ctx, const char* what, int n_pose, int n_vert, int n_tri, int width, int height) {
   PP_CHECK_ARG(ctx, render_shape_ok(n_pose, n_vert, n_tri, width, height), PP_ERR_SHAPE,
-               "%s: need 1..65535 poses, vertices, triangles, a 1..16384 image and n_pose * n_tri * 4 < 2^31", what);
+               "%s: need 1..65535 poses, vertices, triangles, a 1..16384 image, n_pose * n_tri * 4 < 2^31 and n_pose * tiles < 2^31 (32 x 32 pixel tiles)",
+               what);
   return PP_OK;
 }
 

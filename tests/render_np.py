@@ -39,13 +39,12 @@ def top_left(ax, ay, bx, by, s):
     return A > 0.0 or (A == 0.0 and B > 0.0)
 
 
-def render_depth(pts, faces, K, R, t, w, h, clip_near=100.0, clip_far=10000.0, edge_eps=None):
-    """-> depth float32 [h, w]; with edge_eps also a bool mask of pixels whose centre lies within edge_eps pixels of an edge of
-    a triangle that covers or nearly covers them (where device and host may legitimately disagree about coverage)."""
+def render_depth(pts, faces, K, R, t, w, h, clip_near=100.0, clip_far=10000.0):
+    """-> depth float32 [h, w], 0 = empty.  Coverage and depth are the device's at every pixel, pixels on or next to an edge
+    included: both sides decide them with the same float64 expressions on the same float32 screen positions."""
     K = np.asarray(K, np.float64)
     x, y, iz = project(pts, K, R, t)
     zb = np.full((h, w), np.inf)
-    near_edge = np.zeros((h, w), bool)
     for f in np.asarray(faces, np.int64):
         i0, i1, i2 = (int(v) for v in f)
         if min(i0, i1, i2) < 0 or max(i0, i1, i2) >= len(x) or not (iz[i0] > 0 and iz[i1] > 0 and iz[i2] > 0):
@@ -63,17 +62,11 @@ def render_depth(pts, faces, K, R, t, w, h, clip_near=100.0, clip_far=10000.0, e
         c1 = min(int(np.floor(min(max(max(xs) - 0.5, -1.0), float(w)))), w - 1)
         r0 = max(int(np.ceil(min(max(min(ys) - 0.5, -1.0), float(h)))), 0)
         r1 = min(int(np.floor(min(max(max(ys) - 0.5, -1.0), float(h)))), h - 1)
-        g = 1 if edge_eps else 0
-        ra, rb, ca, cb = max(r0 - g, 0), min(r1 + g, h - 1), max(c0 - g, 0), min(c1 + g, w - 1)
-        if ra > rb or ca > cb:
+        if r0 > r1 or c0 > c1:
             continue
-        rr, cc = np.mgrid[ra:rb + 1, ca:cb + 1]
+        rr, cc = np.mgrid[r0:r1 + 1, c0:c1 + 1]
         px, py = cc + 0.5, rr + 0.5
         ws = [s * edge_fn(a[0], a[1], b[0], b[1], px, py) for a, b in edges]
-        if edge_eps:
-            lens = [np.hypot(float(b[0]) - float(a[0]), float(b[1]) - float(a[1])) for a, b in edges]
-            d = np.stack([ws[k] / lens[k] if lens[k] > 0 else np.zeros_like(px) for k in range(3)])
-            near_edge[ra:rb + 1, ca:cb + 1] |= (d.min(0) > -edge_eps) & (np.abs(d) <= edge_eps).any(0)
         inside = np.ones(px.shape, bool)
         for k in range(3):
             inside &= (ws[k] > 0.0) | ((ws[k] == 0.0) & tl[k])
@@ -83,10 +76,9 @@ def render_depth(pts, faces, K, R, t, w, h, clip_near=100.0, clip_far=10000.0, e
             Z = den / num
         keep = inside & (Z >= clip_near) & (Z <= clip_far)
         z32 = Z.astype(np.float32).astype(np.float64)
-        reg = zb[ra:rb + 1, ca:cb + 1]
-        zb[ra:rb + 1, ca:cb + 1] = np.where(keep, np.minimum(reg, z32), reg)
-    out = np.where(np.isfinite(zb), zb, 0.0).astype(np.float32)
-    return (out, near_edge) if edge_eps else out
+        reg = zb[r0:r1 + 1, c0:c1 + 1]
+        zb[r0:r1 + 1, c0:c1 + 1] = np.where(keep, np.minimum(reg, z32), reg)
+    return np.where(np.isfinite(zb), zb, 0.0).astype(np.float32)
 
 
 def box_mesh(sx, sy, sz):

@@ -98,16 +98,10 @@ def test_matches_numpy_restatement():
     ts = [[rng.uniform(-20, 20), rng.uniform(-15, 15), rng.uniform(250, 600)] for _ in range(4)]
     ts[3] = [10.0, -5.0, 70.0]                                           # close-up: triangles far larger than a tile
     got = render(m, Rs, ts, near=10.0)
-    near_edge_total = 0
     for i in range(4):
-        want, near = RN.render_depth(m["pts"], m["faces"], K, Rs[i], ts[i], W, H, 10.0, 10000.0, edge_eps=1e-3)
-        both = (got[i] > 0) & (want > 0)
-        np.testing.assert_allclose(got[i][both], want[both], rtol=1e-6)
-        diff = (got[i] > 0) != (want > 0)
-        assert not (diff & ~near).any(), "coverage differs away from edges"
-        near_edge_total += int(diff.sum())
-        assert both.sum() > 200
-    assert near_edge_total <= 8, near_edge_total
+        want = RN.render_depth(m["pts"], m["faces"], K, Rs[i], ts[i], W, H, 10.0, 10000.0)
+        assert (want > 0).sum() > 200
+        assert np.array_equal(got[i].view(np.uint32), want.view(np.uint32)), (i, int((got[i] != want).sum()))   # coverage and depth, every pixel
 
 
 def test_full_size_batch_is_deterministic_and_equals_single_calls():
@@ -126,9 +120,8 @@ def test_full_size_batch_is_deterministic_and_equals_single_calls():
     Ko = np.array([[1075.65, 0.0, 166.0], [0.0, 1073.9, 125.0], [0.0, 0.0, 1.0]])
     c = render(m, Rs[0], ts[0], K=Ko, w=333, h=251)[0]
     want = RN.render_depth(m["pts"], m["faces"], Ko, Rs[0], ts[0], 333, 251)
-    both = (c > 0) & (want > 0)
-    assert both.sum() > 1000 and ((c > 0) != (want > 0)).sum() <= 4
-    np.testing.assert_allclose(c[both], want[both], rtol=1e-6)
+    assert (want > 0).sum() > 1000
+    assert np.array_equal(c.view(np.uint32), want.view(np.uint32)), int((c != want).sum())
 
 
 def test_render_signature_and_bad_arguments():

@@ -91,11 +91,11 @@ def test_triangle_ids_follow_the_tie_rule(full):
     assert np.array_equal(ids >= 0, depth > 0) and ids.max() < len(MESH["faces"]) and ids.min() == -1
     checked = 0
     for i in range(4):
-        _, near_edge = RN.render_depth(MESH["pts"], MESH["faces"], K, RS[i], TS[i], W, H, NEAR, FAR, edge_eps=1e-3)
-        want = RR.smallest_id_at_depth(MESH["pts"], MESH["faces"], K, RS[i], TS[i], W, H, depth[i], NEAR, FAR)
-        look = (depth[i] > 0) & ~near_edge
-        assert np.array_equal(ids[i][look], want[look]), i
-        checked += int(look.sum())
+        want_depth, want = RR.render_ids(MESH["pts"], MESH["faces"], K, RS[i], TS[i], W, H, NEAR, FAR)
+        assert np.array_equal(ids[i], want), (i, int((ids[i] != want).sum()))                      # every pixel, edges included
+        assert np.array_equal(depth[i].view(np.uint32), want_depth.view(np.uint32)), i
+        assert np.array_equal(want, RR.smallest_id_at_depth(MESH["pts"], MESH["faces"], K, RS[i], TS[i], W, H, depth[i], NEAR, FAR)), i
+        checked += int((want >= 0).sum())
     assert checked > 5000
     # a duplicated face, in both windings: the smaller index everywhere
     tri = {"pts": np.array([RR.unproject(10.25, 10.25, 500.0, K), RR.unproject(90.75, 20.25, 500.0, K), RR.unproject(40.25, 80.75, 650.0, K)])}
