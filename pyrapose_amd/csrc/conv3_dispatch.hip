@@ -1,4 +1,4 @@
-// Forwards the plane-format-dependent entry points of the conv3.hip family to the build the context asks for
+// Forwards the plane-format-dependent entry points of the conv3 units (conv3.hip, conv3_aux.hip) to the build the context asks for
 // (pp_ctx_set_planes_format: 0 = bf16 pairs / bf16x3 arithmetic, 1 = P16 / f16c8 arithmetic; csrc/planes_fmt.h).
 #include "conv_common.h"
 

@@ -1,5 +1,5 @@
-// Device helpers shared by the translation units of the plane-format convolution family (conv3.hip, conv4.hip): included INSIDE
-// the includer's anonymous namespace, after planes_fmt.h (everything here depends on the plane format of the build, PP_FMT).
+// Device helpers shared by the translation units of the plane-format convolution family (the conv3 units, conv4.hip): included by
+// conv3_unit.h INSIDE an anonymous namespace, after planes_fmt.h (everything here depends on the plane format of the build, PP_FMT).
 // The packed plane layout, the LDS-staged epilogue of every implicit-GEMM kernel, raw buffer loads / stores and the LDS-DMA piece.
 #pragma once
 

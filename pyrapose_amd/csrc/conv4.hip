@@ -16,24 +16,14 @@
 //    writes its 64 KB -- the read and write phases of different CUs drift apart instead of alternating chip-wide;
 //  * every stage is an LDS object of its own (the compiler tracks LDS-DMA per object), the epilogue stages through a sixth 32 KB
 //    object: 5 x 32 KB = all 163 840 bytes of the CU with NST = 4, 128 KB with NST = 3.
-// Conditions (host-checked in conv3.hip's dispatch): 1x1, plane-stored gathered operand, no parity-class scatter, buffers < 2 GiB.
-#include "conv_common.h"
-
-#define PP_CAT_(a, b) a##b
-#define PP_CAT(a, b) PP_CAT_(a, b)
-#if PP_FMT == 1
-#define PP_API(name) PP_CAT(name, _fmt1)
-#else
-#define PP_API(name) PP_CAT(name, _fmt0)
-#endif
+// Conditions (host-checked by the planner, conv_plan.h): 1x1, plane-stored gathered operand, no parity-class scatter, buffers < 2 GiB.
+#include "conv3_unit.h"
 #include "conv4.h"
 #ifndef PP_W3W_LA
 #define PP_W3W_LA 2  // wgrad3w: fragment reads in flight ahead of the MFMAs, in units
 #endif
 
 namespace {
-#include "planes_fmt.h"
-#include "conv3_shared.h"
 
 // ---- fragment reads out of the compiler's sight ----
 // The k-loop below keeps NST - 1 LDS-DMA batches in flight across its barriers.  hipcc tracks LDS-DMA per LDS object and puts a

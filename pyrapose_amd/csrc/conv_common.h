@@ -1,4 +1,4 @@
-// Shared pieces of the implicit-GEMM convolution kernels (conv.hip: f32 MFMA; conv3.hip: 3 x bf16 MFMA):
+// Shared pieces of the implicit-GEMM convolution kernels (conv.hip: f32 MFMA; the conv3 units and conv4.hip: 3 x bf16 MFMA):
 // row-space geometry, the gather (row -> source offset per tap), the XCD-aware tile order, descriptor checks
 // and the facts conv_plan.h's planners read.
 #pragma once
@@ -52,7 +52,7 @@ struct IgemmParams {
                    // the remainder of a launch whose full rounds igemm4x_kernel took); split-K slices hold rows m_off .. M - 1
 };
 
-// the weight-gradient kernels (conv3.hip: wgrad3 / wgrad3f; conv4.hip: wgrad3r)
+// the weight-gradient kernels (conv3_wgrad.hip: wgrad3 / wgrad3f; conv4.hip: wgrad3r)
 struct Wgrad3Params {
   int ld_src, ld_dy, ld_w;
   int M, n_seg;

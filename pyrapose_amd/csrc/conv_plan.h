@@ -1,4 +1,4 @@
-// Launch policy of the convolution kernels (conv.hip, conv3.hip, conv4.hip) as plain host C++: the PP_* switches, the facts a
+// Launch policy of the convolution kernels (conv.hip, the conv3 units, conv4.hip) as plain host C++: the PP_* switches, the facts a
 // decision reads, and the plans -- which kernel family runs, with which tile, reduction split, grid and scratch use.  Nothing here
 // needs the HIP runtime: the entry points fill the facts, call a planner and hand the plan to a launch function that only
 // launches; pp_conv_plan_text does the same without a context, so the policy can be tested on a machine without a GPU.
@@ -109,7 +109,7 @@ inline unsigned pp_finish_blocks(long long rows, int Nout, int n_cu) {
   return (unsigned)blocks;
 }
 
-// ---- forward / data-gradient launches (conv3.hip: igemm3*, conv4.hip: igemm4p) ----
+// ---- forward / data-gradient launches (conv3_igemm.hip: igemm3*, conv3_igemm4x.hip: igemm4x, conv4.hip: igemm4p) ----
 struct PpIgemmFacts {
   // the shape (IgemmParams)
   int M, Nout, Cred, kh, kw, ld_out, ld_src, w_rows, w_ld8, w_taps, div, mul, sc_on, w_tstep, w_tx0;
@@ -348,7 +348,8 @@ inline PpIgemmPlan pp_plan_igemm(const PpIgemmFacts& f) {
         }
         // scheduling variants (measured on the regression-head launch, P16): 1 = no iglp_opt hint in the k-step (default: 442 us
         // against 465 with igemm3x's hint, 0), 2 / 3 = s_setprio around the MFMAs of 0 / 1 (466 / 461), 4 = igemm3f's sched_barrier
-        // (per launch: A/B in one process)
+        // (per launch: A/B in one process).  The figures of 0 and 2 are of the build that had igemm4x in one unit with igemm3x: as a unit
+        // of its own the two hinted variants compile to other register counts (profiles/conv3_split_kernel_resources.txt), not re-timed
         const int var = pp_sw_dma_var();
         pl.family = PP_IGEMM4X;
         pl.variant = (var == 0 || var == 2 || var == 3 || var == 4 || var == 9) ? var : 1;
@@ -462,7 +463,7 @@ inline PpS2Merged pp_s2_merge(const PpS2Class cls[4], int BM, int BN, int Nout) 
 // the route applies to what the per-class route applies to (the entry point refuses everything else: no fall-back)
 inline bool pp_dgrad_s2_ok(const PpDgradRouteFacts& r) { return r.stride == 2 && (r.all_f32 || r.all_planes) && r.n_seg == 1; }
 
-// ---- weight-gradient launches (conv3.hip: wgrad3 / wgrad3f, conv4.hip: wgrad3r / wgrad3w) ----
+// ---- weight-gradient launches (conv3_wgrad.hip: wgrad3 / wgrad3f, conv4.hip: wgrad3r / wgrad3w) ----
 struct PpWgradFacts {
   int M, Cin, Cout, kh, kw, stride, pad_t, pad_l, ld_src, ld_dy, ld_w;
   long long src_rows;

@@ -1,4 +1,4 @@
-// The "P16" plane format of the f16c8 arithmetic (csrc/conv3.hip): element = IEEE half (hi plane) + two e5m2 bytes (lo plane):
+// The "P16" plane format of the f16c8 arithmetic (described at the head of csrc/conv3.hip; kernels in the conv3 units and conv4.hip): element = IEEE half (hi plane) + two e5m2 bytes (lo plane):
 // [e5m2(x) | e5m2((x - hi) * 2^12) << 8] for gathered operands, swapped for weights.  value = hi + lo8 * 2^-12 (within 2^-15).
 // Conversions on the hardware's own instructions: v_cvt_pk_f16_f32 (round to nearest even), v_cvt_pk_bf8_f32 (two f32 -> two
 // e5m2 bytes into one word of the destination: exactly one lo unit), v_cvt_f32_bf8 with a byte select -- 5 VALU per encoded

@@ -1,5 +1,5 @@
-// The two (hi, lo) plane formats of the conv3.hip kernel family and their matrix-core arithmetic, behind one interface.
-// conv3.hip is compiled ONCE PER FORMAT (PP_FMT = 0 / 1, csrc/Makefile) into its own namespace; conv3_dispatch.hip picks the
+// The two (hi, lo) plane formats of the conv3 kernel family (conv3*.hip, conv4.hip) and their matrix-core arithmetic, behind one interface.
+// Every unit is compiled ONCE PER FORMAT (PP_FMT = 0 / 1, csrc/Makefile; conv3_unit.h includes this file) into its own namespace; conv3_dispatch.hip picks the
 // build a context asks for (pp_ctx_set_planes_format).  Same packed geometry in both: a tensor [rows][ld] (ld % 8 == 0) is
 // rows * ld * 4 bytes in 32-byte groups of 8 channels, 16 bytes of hi then 16 bytes of lo.
 //

@@ -206,7 +206,7 @@ def test_sparse_forward_of_box_head_is_exact_for_training(ctx, monkeypatch, mode
 def test_positive_row_blocks_and_dilation_match_numpy(ctx):
     """pp_positive_row_blocks / pp_row_block_dilate against a plain restatement: block b is flagged when one of its 32 rows holds
     an anchor with state 1; the dilation flags b when a flagged block meets one of the three 34-row windows
-    [32 b - 1 + j W, 32 b + 32 + j W], j = -1, 0, 1, W = width of the level block b lies in (conv3.hip: rl_dilate_kernel)."""
+    [32 b - 1 + j W, 32 b + 32 + j W], j = -1, 0, 1, W = width of the level block b lies in (conv3_igemm.hip: rl_dilate_kernel)."""
     from pyrapose_amd import ops
     rng = np.random.default_rng(9)
     Bq, shapes, A = 2, [(20, 26), (10, 13), (5, 7)], 9

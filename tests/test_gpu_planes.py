@@ -493,7 +493,7 @@ def planned(ctx, d, pass_, forms):
 
 
 def test_lds_dma_kernel_matches_register_staged(ctx, monkeypatch):
-    """igemm4x (csrc/conv3.hip): the head-conv launch on the multi-stage LDS-DMA pipeline -- taken for planes in / planes out, 3x3
+    """igemm4x (csrc/conv3_igemm4x.hip): the head-conv launch on the multi-stage LDS-DMA pipeline -- taken for planes in / planes out, 3x3
     stride 1, cout % 128 == 0 and at least two rounds of 256 x 128 tiles, with the rows of the last partly filled round going to a
     split-K launch of the 128 x 128 kernel.  Same products in the same order as the register-staged igemm3x (PP_CONV3_DMA=0, read at
     every launch): the whole-round rows are bit-identical, the split-K rows agree to f32 summation order; forward with bias +
@@ -554,7 +554,7 @@ def test_lds_dma_kernel_matches_register_staged(ctx, monkeypatch):
 
 
 def test_lds_dma_kernel_two_workgroups_per_cu_matches_register_staged(ctx, monkeypatch):
-    """Round 4, igemm4x<NWM = 2> (csrc/conv3.hip): the 128 x 128 form of the LDS-DMA pipeline, two workgroups per CU, gathered ring
+    """Round 4, igemm4x<NWM = 2> (csrc/conv3_igemm4x.hip): the 128 x 128 form of the LDS-DMA pipeline, two workgroups per CU, gathered ring
     2 x 16 KB + weight ring 2 x 16 KB -- taken by launches between one round of 128-row tiles and two rounds of 256-row tiles (the
     256-channel heads, the FPN 3x3).  Same products in the same order as igemm3x: EVERY row bit-identical (PP_CONV3_DMA2=0 / 1,
     read per launch); forward with bias + residual + ReLU over a three-level row space, data gradient with addend + mask."""
