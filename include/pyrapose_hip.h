@@ -1059,7 +1059,8 @@ int pp_mask_from_rle(pp_ctx* ctx, int n_mask, int H, int W, int order, const int
  * every product, sum and quotient rounded on its own; maxima by integer atomics on the bits of non-negative doubles, no float
  * atomics: bit-identical to the numpy restatement (tests/depth_normals_np.py) and run to run.  Pinned to the reference's own
  * function through tests/golden/depth_normals.npz wherever its smoothed depth is not exactly 0 (there its cross product of two
- * parallel tangents is rounding noise).  Its three-value variants with cv2.inpaint are not covered.
+ * parallel tangents is rounding noise).  The hole filling that precedes it in the reference's three-value variants is
+ * pp_depth_inpaint below (the project's own fill rule, not cv2.inpaint's; parity with OpenCV is not pinned).
  *
  * pp_depth_normals_f64: n_img images in one call (the batch rides on a grid dimension).
  *   in   depth [n,H,W] float32 (device), finite and >= 0 (NaN is not handled); intr [n,3] float64 (device) = (fx, cx, cy) per
@@ -1154,6 +1155,51 @@ size_t pp_depth_augment_workspace_bytes(int n_img, int H, int W);
 int pp_depth_augment(pp_ctx* ctx, int n_img, int H, int W, const float* depth, const unsigned char* mask, const double* params,
                      const double* params_host, const float* z, void* workspace, size_t workspace_bytes, float* depth_f32,
                      double* depth_f64, unsigned char* mask_u8, double* half_f64, double* sensor_f64);
+
+/* ---- depth-hole filling (csrc/depth_inpaint.hip) --------------------------------------------------------------------------
+ * What the reference does with cv2.inpaint(depth, depth == 0, 5, cv2.INPAINT_NS) at the head of get_normal in seven of its
+ * scripts (annotate_val_LineMOD.py:206-221, annotate_val_LM_BOP.py, annotate_val_LMO_BOP.py, annotate_val_YCBV_BOP.py,
+ * prepare_val_LineMOD_RGB.py, augment_syn_LineMOD.py, augment_syn_Tless.py), and the rescaling that follows it there.  The
+ * method is the project's own, of the same kind as OpenCV's (holes filled from their rim inwards by distance-weighted means)
+ * but order-free: OpenCV's fast marching is a sequential priority queue, and OpenCV is not a dependency, so parity with
+ * cv2.inpaint is not pinned.  float64 throughout where cv2 is float32, every product, sum and quotient rounded on its own; no
+ * floating-point atomics: bit-identical to the numpy restatement (tests/depth_inpaint_np.py) and run to run.  The layer map is
+ * pinned to scipy.ndimage.distance_transform_cdt(metric='chessboard') (tests/test_depth_inpaint_cpu.py).
+ *
+ * pp_depth_inpaint: n_img images in one call.
+ *   in   depth [n,H,W] float32 (device), finite and >= 0 (NaN is not handled); hole_mask [n,H,W] uint8 (device; non-zero = hole)
+ *        or NULL: a hole is depth == 0; radius 1..8 (the reference's inPaiDia 5 is radius 5); max_dist 0..65535, 0 = no limit;
+ *        rescale 0 | 1.
+ *   1. Layer map.  L = the chessboard distance from a pixel to the nearest known (non-hole) pixel of its image, 0 on known
+ *      pixels.  Pixels outside the image do not exist: they are neither known nor holes.  An image without a known pixel has
+ *      L = 65535 everywhere, is returned as it came (the input depth, no rescaling) and counts
+ *      (H W, 0, 0).
+ *   2. Fill.  v = depth as float64 on known pixels and 0 on holes.  For k = 1, 2, ... every pixel p with L(p) = k, and
+ *      k <= max_dist where a limit is set, gets v(p) = (sum_q w v(q)) / (sum_q w) over the q of the (2 radius + 1)^2 window
+ *      around p that lie inside the image and have L(q) < k, taken in row-major order, both sums from 0.0,
+ *      w = 1.0 / (double)((dx^2 + dy^2)(1 + L(q))) with the product an integer.  Layer k reads layers < k only, so the result
+ *      does not depend on the order inside a layer; a pixel of layer k has a neighbour of layer k - 1 at chessboard distance 1,
+ *      so the sums are never empty.  Holes beyond max_dist stay 0.
+ *   3. rescale = 1 (the reference's lines 216-219): v <- ((v - min v) / (max v - min v)) max depth per image, min v and max v
+ *      over the filled image and max depth over the input, each exact (integer atomics on the bits of non-negative doubles).
+ *      Where max v = min v the image stays as it is (the reference divides by zero there).
+ *   out  each may be NULL (skipped, with the launches nobody needs), at least one must not be:
+ *        filled_f32 [n,H,W] v rounded once to float32 (what feeds pp_depth_normals_f64); filled_f64 [n,H,W] v;
+ *        layer_u16 [n,H,W] L; counts [n,3] int32: holes, pixels to fill (1 <= L, and L <= max_dist under a limit), the largest
+ *        L of the image whether or not max_dist cuts it off (0 without holes or without known pixels).
+ *   Launches: row distances (half a wave of 32 lanes per row), the layer map with a histogram of the layers (32 x 8 pixels per
+ *   workgroup), and for the filled outputs a scan of the histogram, a counting sort of the pixels to fill by layer, ONE HOST
+ *   SYNCHRONISATION that reads the layers' offsets back, one fill launch per non-empty layer over that layer's pixels of all
+ *   images, the extrema for rescale = 1, and a last pass that rescales and rounds.  Not capturable in a graph for that reason.
+ *   Workspace: pp_depth_inpaint_workspace_bytes(n_img, H, W) = a(4 (4 n + 12289)) + a(24 n) + 2 a(2 P) + a(4 P) + a(8 P) bytes
+ *   with P = n H W and a(b) = b rounded up to a multiple of 256 (0: a refused shape).
+ *   Errors before anything is launched: n_img outside 1..65535, H or W outside 3..4096, n_img H W >= 2^31: PP_ERR_SHAPE; a null
+ *   depth / workspace, radius outside 1..8, max_dist outside 0..65535, rescale outside {0, 1}, no output, workspace_bytes too
+ *   small: PP_ERR_ARG. */
+size_t pp_depth_inpaint_workspace_bytes(int n_img, int H, int W);
+int pp_depth_inpaint(pp_ctx* ctx, int n_img, int H, int W, const float* depth, const unsigned char* hole_mask, int radius,
+                     int max_dist, int rescale, void* workspace, size_t workspace_bytes, float* filled_f32, double* filled_f64,
+                     unsigned short* layer_u16, int* counts);
 
 #ifdef __cplusplus
 }

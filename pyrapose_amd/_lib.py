@@ -227,6 +227,8 @@ _SIGS = {
     "pp_depth_normals_f64": (_i, [_p, _i, _i, _i, _p, _p, C.POINTER(_d), _i, _p, _sz, _p, _p, _p, _p]),
     "pp_depth_augment_workspace_bytes": (_sz, [_i, _i, _i]),
     "pp_depth_augment": (_i, [_p, _i, _i, _i, _p, _p, _p, C.POINTER(_d), _p, _p, _sz, _p, _p, _p, _p, _p]),
+    "pp_depth_inpaint_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pp_depth_inpaint": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _i, _p, _sz, _p, _p, _p, _p]),
 }
 
 EXPORTS = sorted(_SIGS)

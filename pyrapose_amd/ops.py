@@ -1710,3 +1710,34 @@ def depth_augment(ctx, depth, mask, params, z=None, want=("depth_f32",)):
     check(lib.pp_depth_augment(ctx.handle, n, H, W, _ptr(depth), _ptr(mask), _ptr(dev), host.ctypes.data_as(C.POINTER(C.c_double)),
                                _ptr(z), _ptr(ws), nbytes, *[_ptr(out.get(k)) for k in DEPTH_AUG_OUTPUTS]), ctx.handle, "pp_depth_augment")
     return out
+
+
+DEPTH_INPAINT_TILE = 32        # lanes per image row of pp_depth_inpaint's row pass, pixels per row of a workgroup of its layer pass
+DEPTH_INPAINT_ROWS = 8         # image rows per workgroup in both
+DEPTH_INPAINT_MAX_RADIUS = 8
+DEPTH_INPAINT_MAX_DIST = 65535
+DEPTH_INPAINT_MAX_SIDE = 4096
+DEPTH_INPAINT_NO_LAYER = 65535  # 'layer' of every pixel of an image without a known pixel
+DEPTH_INPAINT_OUTPUTS = {"filled_f32": _F32, "filled_f64": _F64, "layer": torch.uint16, "counts": _I32}  # in the ABI's order
+
+
+def depth_inpaint(ctx, depth, hole_mask=None, radius=5, max_dist=0, rescale=False, want=("filled_f32",)):
+    """Layered filling of depth holes on n images (pp_depth_inpaint, the rule in include/pyrapose_hip.h): cuda tensors depth
+    float32 [n,H,W] (finite, >= 0) and hole_mask uint8 [n,H,W] (non-zero = hole; None: a hole is depth == 0); radius 1..8 of the
+    window, max_dist the deepest layer that is filled (0: all), rescale the reference's stretch to [0, max depth]; want: any of
+    DEPTH_INPAINT_OUTPUTS -> dict of the requested outputs: 'filled_f32' / 'filled_f64' [n,H,W], 'layer' uint16 [n,H,W] (the
+    chessboard distance to the nearest known pixel; DEPTH_INPAINT_NO_LAYER in an image without one), 'counts' int32 [n,3] =
+    (holes, pixels to fill, largest layer).  The filled outputs cost one host synchronisation."""
+    what = "depth_inpaint"
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(o not in DEPTH_INPAINT_OUTPUTS for o in want):
+        raise ValueError("%s: want must name at least one of %s, got %r" % (what, " | ".join(DEPTH_INPAINT_OUTPUTS), want))
+    depth = _arg(what, "depth", depth, _F32, (None, None, None))
+    n, H, W = (int(s) for s in depth.shape)
+    hole_mask = _arg(what, "hole_mask", hole_mask, _U8, (n, H, W), optional=True)
+    nbytes = lib.pp_depth_inpaint_workspace_bytes(n, H, W)
+    ws = _workspace(nbytes)  # (0 bytes: a refused shape, which the entry point reports)
+    out = {k: _out(depth, (n, 3) if k == "counts" else (n, H, W), dt) for k, dt in DEPTH_INPAINT_OUTPUTS.items() if k in want}
+    check(lib.pp_depth_inpaint(ctx.handle, n, H, W, _ptr(depth), _ptr(hole_mask), int(radius), int(max_dist), 1 if rescale else 0,
+                               _ptr(ws), nbytes, *[_ptr(out.get(k)) for k in DEPTH_INPAINT_OUTPUTS]), ctx.handle, "pp_depth_inpaint")
+    return out

@@ -1,5 +1,5 @@
-"""Depth images on the device: the reference's augmentDepth and get_normal, the two steps between a depth render and the
-surface-normal image the reference writes as every sample's _dep.png.
+"""Depth images on the device: the reference's augmentDepth, hole filling and get_normal, the steps between a depth render (or a
+sensor's depth frame) and the surface-normal image the reference writes as every sample's _dep.png.
 
 get_normal (annotation_scripts/Augmentations.py:394-467, the same function copied into annotate_val_LineMOD.py,
 annotate_val_LM_BOP.py, annotate_val_LMO_BOP.py, annotate_val_YCBV_BOP.py, prepare_val_LineMOD_RGB.py, augment_syn_LineMOD.py
@@ -13,7 +13,9 @@ What is and is not the reference's:
   * An image whose smoothed depth is all zero, or whose scaled normal image is all zero, makes the reference divide by zero under
     for_vis=False; here its uint8 image and its scaled depth are all zero.
   * The reference's int16 pixel table wraps beyond +-32767 pixels from the principal point; here it does not.
-  * The three-value variants of augment_syn_LineMOD.py / augment_syn_Tless.py (cv2.inpaint) are not covered.
+  * The three-value variants (annotate_val_LineMOD.py:202-, augment_syn_LineMOD.py:425-, augment_syn_Tless.py:363- and the other
+    annotate_* / prepare_* copies), which fill the depth holes first and return the filled depth as a third value, are
+    get_normal_inpaint and normals_from_depth_batch(inpaint=...), with the hole filling described below in place of cv2.inpaint.
 Pinned to the reference's own function by tests/golden/depth_normals.npz, at every pixel whose smoothed depth is not exactly 0.
 
 augmentDepth (annotation_scripts/Augmentations.py:10-134; augment_syn_LineMOD.py:273-418 and augment_syn_Tless.py:219-356 with
@@ -33,7 +35,23 @@ What is and is not the reference's there:
   * cv2 is restated from its documented rules (morphologyEx's default border, resize INTER_LINEAR, GaussianBlur's
     BORDER_REFLECT_101 and getGaussianKernel) and not pinned; the majority filter is pinned to scipy.signal.medfilt2d and the
     opening to scipy.ndimage's grey erosion and dilation.
-  * obj_mask is accepted and ignored, as the reference ignores it."""
+  * obj_mask is accepted and ignored, as the reference ignores it.
+
+Hole filling (csrc/depth_inpaint.hip, inpaint_depth_batch): where the reference calls cv2.inpaint(depth, depth == 0, 5,
+cv2.INPAINT_NS) and stretches the result back to [0, max depth] (annotate_val_LineMOD.py:206-219), holes (depth = 0: the
+shadows augmentDepth cuts, the missing returns of a real sensor) are filled here layer by layer from their rim inwards, bit for
+bit the numpy restatement tests/depth_inpaint_np.py.
+
+What is and is not the reference's there:
+  * The fill rule is the project's own, not OpenCV's Navier-Stokes fast marching: a hole pixel at chessboard distance k from the
+    nearest known pixel is the mean of the pixels of lower layers in its (2 radius + 1)^2 window, weighted by
+    1 / (squared distance x (1 + layer)).  Of the same kind (values propagate inwards from the rim), order-free and
+    bit-reproducible, which a priority queue is not.  The reference's inPaiDia = 5 is radius = 5.
+  * The arithmetic is float64, where cv2.inpaint computes a float32 image in float32.
+  * Parity with cv2.inpaint is not pinned: OpenCV is not a dependency of this project or of its tests.  The layer map is pinned
+    to scipy.ndimage.distance_transform_cdt(metric='chessboard').
+  * An image without a known pixel is returned as it came; where the filled image is constant the rescaling leaves it alone (the
+    reference divides by zero).  NaN depth is not handled."""
 import numpy as np
 import torch
 
@@ -68,7 +86,31 @@ def _depth_stack(depth):
     return to_device(depth, torch.float32)
 
 
-def normals_from_depth_batch(depth, K_or_intrinsics, for_vis=True, signed=False, ctx=None):
+def inpaint_depth_batch(depth, hole_mask=None, radius=5, max_dist=0, rescale=False, ctx=None):
+    """Fill the holes of n depth images in one call: depth [n,H,W] (array or tensor, host or device; converted to float32),
+    hole_mask [n,H,W] (non-zero = hole; None means depth == 0), radius 1..ops.DEPTH_INPAINT_MAX_RADIUS of the window (the
+    reference's inPaiDia), max_dist the deepest layer that is filled, in pixels from the nearest known pixel (0: every hole, however
+    large -- an empty background is then filled too; give a limit to keep it empty), rescale=True the reference's stretch of the
+    filled image to [0, max depth] -> cuda float32 [n,H,W], ready for normals_from_depth_batch.
+    One call takes at most 65535 images and fewer than 2^31 pixels (pp_depth_inpaint's limits; ValueError beyond them) and does
+    not split a larger batch itself: the images are independent, so call it on slices of the batch and concatenate."""
+    if not 1 <= int(radius) <= ops.DEPTH_INPAINT_MAX_RADIUS or not 0 <= int(max_dist) <= ops.DEPTH_INPAINT_MAX_DIST:
+        raise ValueError("inpaint_depth_batch: radius must be 1..%d and max_dist 0..%d, got %r and %r" %
+                         (ops.DEPTH_INPAINT_MAX_RADIUS, ops.DEPTH_INPAINT_MAX_DIST, radius, max_dist))
+    depth = depth if torch.is_tensor(depth) else np.asarray(depth)  # (a nested list has no shape to check)
+    if hole_mask is not None:
+        hole_mask = hole_mask if torch.is_tensor(hole_mask) else np.asarray(hole_mask)
+        if tuple(hole_mask.shape) != tuple(depth.shape):
+            raise ValueError("hole_mask must be %s like depth, got %s" % (tuple(depth.shape), tuple(hole_mask.shape)))
+    d = _depth_stack(depth)
+    m = None
+    if hole_mask is not None:
+        m = hole_mask if torch.is_tensor(hole_mask) else torch.from_numpy(np.ascontiguousarray(np.asarray(hole_mask) != 0))
+        m = (m.to(device="cuda") != 0).to(torch.uint8).contiguous()
+    return ops.depth_inpaint(ctx or default_context(), d, m, int(radius), int(max_dist), bool(rescale), ("filled_f32",))["filled_f32"]
+
+
+def normals_from_depth_batch(depth, K_or_intrinsics, for_vis=True, signed=False, ctx=None, inpaint=None):
     """get_normal on n depth images in one call: depth [n,H,W], a numpy array or a tensor (host or device; converted to
     float32), K_or_intrinsics one 3x3 camera matrix or [n,3,3], or (fx, cx, cy) as [3] or [n,3]
     -> (normals, depth_smoothed) as cuda tensors:
@@ -76,6 +118,9 @@ def normals_from_depth_batch(depth, K_or_intrinsics, for_vis=True, signed=False,
        for_vis=False  uint8 [n,H,W,3] the reference's _dep image, float64 [n,H,W] smoothed depth / its per-image maximum
     signed=True (for_vis=True only) returns the unit normals before the absolute value instead, zero where the reference's
     are zero.  A 3x3 K with n = 3 is read as one camera matrix, never as three (fx, cx, cy) rows.
+    inpaint=dict(radius=5, ...) (the keywords of inpaint_depth_batch; an empty dict for its defaults) fills the depth holes first
+    and returns (normals, depth_smoothed, filled depth as cuda float32 [n,H,W]), the three values of the reference's later
+    get_normal; inpaint=None is the two-value call, untouched.
 
     The renderers' depth goes straight in -- render_depth_batch's device tensor, and the scene depth that
     scene_gt.scene_gt_info composes for the scenes scene_gt.render_scenes draws:
@@ -85,9 +130,14 @@ def normals_from_depth_batch(depth, K_or_intrinsics, for_vis=True, signed=False,
         gt = scene_gt.scene_gt_info(scenes, models, K, im_size=(640, 480))            # .depth: float32 [S,480,640], composed
         programs = sample_depth_programs(np.random.default_rng(0), len(scenes))       # host: one parameter row per image
         noisy = augment_depth_batch(gt.depth, None, programs)                         # the Kinect look: float32 [S,480,640]
-        dep_png, _ = normals_from_depth_batch(noisy, K, for_vis=False)                # the samples' _dep: uint8 [S,480,640,3]"""
+        filled = inpaint_depth_batch(noisy, radius=5, rescale=True)                   # its shadow holes closed: float32 [S,480,640]
+        dep_png, _ = normals_from_depth_batch(filled, K, for_vis=False)               # the samples' _dep: uint8 [S,480,640,3]
+    (the last two lines in one: normals_from_depth_batch(noisy, K, for_vis=False, inpaint=dict(radius=5, rescale=True)))"""
     if signed and not for_vis:
         raise ValueError("normals_from_depth_batch: signed=True goes with for_vis=True (the uint8 image has no sign)")
+    if inpaint is not None:
+        filled = inpaint_depth_batch(depth, ctx=ctx, **dict(inpaint))
+        return normals_from_depth_batch(filled, K_or_intrinsics, for_vis, signed, ctx) + (filled,)
     d = _depth_stack(depth)
     intr = to_device(_intrinsics(K_or_intrinsics, int(d.shape[0])))
     first = "signed" if signed else ("normals" if for_vis else "normals_u8")
@@ -104,6 +154,18 @@ def get_normal(depth_refine, fx=-1, fy=-1, cx=-1, cy=-1, for_vis=True):
         raise ValueError("get_normal: depth_refine must be [H,W], got %s" % (depth.shape,))
     n, d = normals_from_depth_batch(depth[None], np.array([fx, cx, cy], np.float64), for_vis=for_vis)
     return n[0].cpu().numpy(), d[0].cpu().numpy()
+
+
+def get_normal_inpaint(depth_refine, fx=-1, fy=-1, cx=-1, cy=-1, for_vis=True):
+    """The reference's later get_normal (annotate_val_LineMOD.py:202-, augment_syn_LineMOD.py:425-), signature and return triple:
+    the holes (depth == 0) filled with radius 5 and the filled image stretched to [0, max depth], then get_normal on it
+    -> (normals, smoothed depth, filled depth [H,W] float32) as numpy arrays; the first two as get_normal returns them."""
+    depth = np.asarray(depth_refine)
+    if depth.ndim != 2:
+        raise ValueError("get_normal_inpaint: depth_refine must be [H,W], got %s" % (depth.shape,))
+    n, d, filled = normals_from_depth_batch(depth[None], np.array([fx, cx, cy], np.float64), for_vis=for_vis,
+                                            inpaint=dict(radius=5, rescale=True))
+    return n[0].cpu().numpy(), d[0].cpu().numpy(), filled[0].cpu().numpy()
 
 
 def _program_row(k_open, k_med, k_blur, blur_sigma, depth_noise, method, freq, octaves, w_xy, w_z, seed):
