@@ -1201,6 +1201,56 @@ int pp_depth_inpaint(pp_ctx* ctx, int n_img, int H, int W, const float* depth, c
                      int max_dist, int rescale, void* workspace, size_t workspace_bytes, float* filled_f32, double* filled_f64,
                      unsigned short* layer_u16, int* counts);
 
+/* ---- evaluation overlays: boxes, wireframes, discs, bitmap text and an id layer over uint8 images (overlay.hip) ----
+ * What the reference draws with OpenCV: cv2.rectangle and cv2.putText for detections and annotations
+ * (utils/visualization.py), twelve cv2.line calls per projected 3-D box and cv2.circle per voted corner
+ * (linemod_eval.py:537-620), draw_axis (annotation_scripts/misc.py:8), and the mask head's output as an image
+ * (linemod_eval.py:343-369).  The rules below are the project's own: exact integer coverage tests, no Bresenham stepping, no
+ * anti-aliasing (the reference passes LINE_AA to cv2.rectangle), no Hershey font -- glyph bitmaps travel in the records, the
+ * library holds no font.  OpenCV is not a dependency, so parity with cv2 is not pinned.  Integer arithmetic only, no atomics, no
+ * floating point: the result is a pure function of the inputs, byte for byte the numpy restatement (tests/overlay_np.py) and the
+ * same run to run.
+ *
+ * pp_draw_overlay_u8: B images in ONE launch, no workspace, no host synchronisation (capturable in a graph).
+ *   in   images [B,H,W,3] uint8 (device).  The channel order is the caller's: a colour names channels by index.
+ *        prims [n_total,8] int32 and image_offsets [B+1] int32 (device): image b owns the records image_offsets[b] ..
+ *        image_offsets[b+1], painted in list order, later over earlier.  The offsets are read on the device and never checked on
+ *        the host: each is cut to 0 .. n_total and an end below its begin is an empty list.  n_total may be 0 with prims NULL.
+ *        ids [B,H,W] uint8 (device) or NULL: the id layer; palette [256] int32 (device) packed colours, entry 0 is never drawn;
+ *        id_mode: bit 0 = fill, bit 1 = outline (0: the id layer is off; ignored with ids NULL); outline_width 1..4.
+ *   out  out [B,H,W,3] uint8 (device).  It may be the same pointer as images (every pixel is read and written by one thread only);
+ *        any other overlap of the two is undefined.
+ *   Colour: c0 | c1 << 8 | c2 << 16 | A << 24, c_k the value of channel k.  Painting a pixel value p with it is, per channel,
+ *        p <- (A c + (255 - A) p + 127) / 255 in integers: the identity at A = 0, a plain store at A = 255.
+ *   Record: (kind, a0, a1, a2, a3, size, colour, reserved); reserved is not read.  Pixel (x, y), 0 <= x < W, 0 <= y < H:
+ *     0 SEGMENT    (a0, a1) = P0, (a2, a3) = P1, size = thickness t, 1 <= t <= 64, every coordinate |v| <= 8192.  Covered iff
+ *                  the squared distance from the pixel to the segment is <= t^2 / 4, exactly: with d = P1 - P0, L2 = d.d,
+ *                  w = P - P0, s = w.d:  s <= 0: 4 |w|^2 <= t^2;  s >= L2: 4 |P - P1|^2 <= t^2;  otherwise
+ *                  4 cross(d, w)^2 <= t^2 L2 (int64: |d|, |w| <= 2^14 per coordinate, |cross| <= 2^29, 4 cross^2 <= 2^60).
+ *                  Round caps; P0 == P1 is the filled disc of diameter t (the reference's cv2.circle(..., 3, ..., -2) is t = 7:
+ *                  4 |w|^2 <= 49, |w|^2 <= 12).  Rectangles and box wireframes are segments, built on the host.
+ *     1 GLYPH      (a0, a1) = the top-left of an 8 x 8 cell grid, |v| <= 8192 (beyond it no cell reaches an image);
+ *                  a2 = bits 0..31, a3 = bits 32..63 of a bitmap whose bit 8 row + col is cell (col, row);
+ *                  size = scale | dilate << 8, scale 1..4, dilate 0..2, the bits above zero.  Position (qx, qy) lies in cell
+ *                  (floor((qx - a0) / scale), floor((qy - a1) / scale)) where both are in 0..7.  Covered iff some position
+ *                  within chessboard distance dilate of the pixel -- inside the image or not -- lies in a set cell.
+ *     2 FILL_RECT  (a0, a1), (a2, a3): corners, inclusive, in any order, any int32; size is not read.
+ *     Any other kind, or a field outside these ranges, paints nothing (tested once per record, not per pixel).
+ *   Id layer, before the records, with L = ids at the pixel: fill paints every pixel with L != 0 with palette[L]; outline then
+ *        paints (with palette[L] again, over the fill where both are on) every pixel with L != 0 for which some pixel within
+ *        chessboard distance outline_width that lies inside the image has an id other than L (0 included): an inner contour.
+ *        Pixels outside the image are ignored, so a label that runs into the image border has no contour along it.
+ *   Launch: a workgroup of 256 threads per 32 x 32 tile and image, 4 adjacent pixels per thread held in registers from the one
+ *   read to the one write; the id tile with its halo of 4 in LDS; the records in chunks of 256, those whose bounding box reaches
+ *   the tile compacted into LDS in list order (ballot, popcount prefix), then walked by every pixel.  Every tile reads its
+ *   image's whole list.
+ *   Errors before anything is launched, PP_ERR_ARG each: B < 1, H or W outside 1..8192, n_total outside 0..2^24, a null images /
+ *   out / image_offsets, null prims with n_total > 0, id_mode outside 0..3, ids without palette, outline_width outside 1..4
+ *   while outlining (ids set and bit 1 of id_mode). */
+int pp_draw_overlay_u8(pp_ctx* ctx, int B, int H, int W, const unsigned char* images, unsigned char* out, const int* prims,
+                       const int* image_offsets, int n_total, const unsigned char* ids, const int* palette, int id_mode,
+                       int outline_width);
+
 #ifdef __cplusplus
 }
 #endif

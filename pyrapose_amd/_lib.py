@@ -229,6 +229,7 @@ _SIGS = {
     "pp_depth_augment": (_i, [_p, _i, _i, _i, _p, _p, _p, C.POINTER(_d), _p, _p, _sz, _p, _p, _p, _p, _p]),
     "pp_depth_inpaint_workspace_bytes": (_sz, [_i, _i, _i]),
     "pp_depth_inpaint": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _i, _p, _sz, _p, _p, _p, _p]),
+    "pp_draw_overlay_u8": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _i, _i]),
 }
 
 EXPORTS = sorted(_SIGS)

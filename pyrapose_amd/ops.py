@@ -1741,3 +1741,63 @@ def depth_inpaint(ctx, depth, hole_mask=None, radius=5, max_dist=0, rescale=Fals
     check(lib.pp_depth_inpaint(ctx.handle, n, H, W, _ptr(depth), _ptr(hole_mask), int(radius), int(max_dist), 1 if rescale else 0,
                                _ptr(ws), nbytes, *[_ptr(out.get(k)) for k in DEPTH_INPAINT_OUTPUTS]), ctx.handle, "pp_depth_inpaint")
     return out
+
+
+OVERLAY_SEGMENT, OVERLAY_GLYPH, OVERLAY_FILL_RECT = 0, 1, 2  # record kinds of pp_draw_overlay_u8
+OVERLAY_TILE = 32            # pixels per side of a workgroup's tile
+OVERLAY_CHUNK = 256          # records per pass over an image's list
+OVERLAY_MAX_SIDE = 8192
+OVERLAY_MAX_COORD = 8192     # |coordinate| of a segment's end points and of a glyph's corner
+OVERLAY_MAX_THICK = 64
+OVERLAY_MAX_SCALE = 4
+OVERLAY_MAX_DILATE = 2
+OVERLAY_MAX_OUTLINE = 4
+OVERLAY_MAX_PRIMS = 1 << 24
+
+
+def draw_overlay(ctx, images, prims, image_offsets, ids=None, palette=None, fill=False, outline=0, out=None):
+    """An ordered list of primitives and an id layer painted over B images in one launch (pp_draw_overlay_u8, the rule in
+    include/pyrapose_hip.h): cuda tensors images uint8 [B,H,W,3] (any channel order: colours go by channel index), prims int32
+    [n,8] records (kind, a0, a1, a2, a3, size, colour, reserved), image_offsets int32 [B+1] (image b owns the records
+    image_offsets[b] .. image_offsets[b+1], later over earlier; read on the device, not checked); the id layer: ids uint8
+    [B,H,W] with palette int32 [256] packed colours (entry 0 is never drawn), fill: paint every labelled pixel, outline 0..4: the
+    width of the inner contour, 0 = none.  out: None allocates the result, `images` draws in place, otherwise a cuda uint8
+    [B,H,W,3] tensor that does not overlap images -> out."""
+    what = "draw_overlay"
+    if out is images and torch.is_tensor(images) and not images.is_contiguous():
+        raise ValueError("%s: drawing in place needs contiguous images" % what)
+    in_place = out is images
+    images = _arg(what, "images", images, _U8, (None, None, None, 3))
+    B, H, W = (int(s) for s in images.shape[:3])
+    if B < 1 or not (1 <= H <= OVERLAY_MAX_SIDE and 1 <= W <= OVERLAY_MAX_SIDE):
+        raise ValueError("%s: need at least one image of 1..%d x 1..%d pixels, got %d of %d x %d" % (what, OVERLAY_MAX_SIDE, OVERLAY_MAX_SIDE, B, H, W))
+    prims = _arg(what, "prims", prims, _I32, (None, 8))
+    n = int(prims.shape[0])
+    if n > OVERLAY_MAX_PRIMS:
+        raise ValueError("%s: %d records, at most %d" % (what, n, OVERLAY_MAX_PRIMS))
+    image_offsets = _arg(what, "image_offsets", image_offsets, _I32, (B + 1,))
+    ids = _arg(what, "ids", ids, _U8, (B, H, W), optional=True)
+    palette = _arg(what, "palette", palette, _I32, (256,), optional=True)
+    if ids is not None and palette is None:
+        raise ValueError("%s: ids need a palette" % what)
+    outline = int(outline)
+    if not 0 <= outline <= OVERLAY_MAX_OUTLINE:
+        raise ValueError("%s: outline %d, need 0 (none) .. %d" % (what, outline, OVERLAY_MAX_OUTLINE))
+    if ids is None and (fill or outline):
+        raise ValueError("%s: fill / outline need ids" % what)
+    if in_place:
+        out = images
+    elif out is None:
+        out = _out(images, (B, H, W, 3), _U8)
+    else:
+        ok = torch.is_tensor(out) and out.is_cuda and out.dtype == _U8 and tuple(out.shape) == (B, H, W, 3) and out.is_contiguous()
+        if not ok:
+            raise ValueError("%s: out must be a contiguous cuda uint8 tensor [%d,%d,%d,3]" % (what, B, H, W))
+        if out.data_ptr() != images.data_ptr():
+            lo, hi, size = out.data_ptr(), images.data_ptr(), B * H * W * 3
+            if lo < hi + size and hi < lo + size:
+                raise ValueError("%s: out overlaps images without being images" % what)
+    id_mode = (1 if fill else 0) | (2 if outline else 0)
+    check(lib.pp_draw_overlay_u8(ctx.handle, B, H, W, _ptr(images), _ptr(out), _ptr(prims) if n else None, _ptr(image_offsets), n,
+                                 _ptr(ids), _ptr(palette), id_mode, max(outline, 1)), ctx.handle, "pp_draw_overlay_u8")
+    return out

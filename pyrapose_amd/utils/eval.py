@@ -81,10 +81,11 @@ def evaluate(generator, model, iou_threshold=0.5, score_threshold=0.05, max_dete
     has_label, load_image, preprocess_image, resize_image, load_annotations), model.predict_on_batch(...)[:3] are boxes, scores,
     labels; per image the detections above score_threshold, best max_detections first.  The images' detections are gathered
     into one padded batch; matching, curves and the integral run on the device (evaluate_detections, rule 'reference').
-    Equal scores keep their input order here (the reference's argsort leaves them undefined).  Drawing is out of scope:
-    save_path other than None raises NotImplementedError."""
+    Equal scores keep their input order here (the reference's argsort leaves them undefined).  Drawing is not part of this
+    loop: save_path other than None raises NotImplementedError; visualization.save_detection_images writes those images."""
     if save_path is not None:
-        raise NotImplementedError("evaluate: save_path (drawing detections) is not implemented")
+        raise NotImplementedError("evaluate: save_path (drawing detections) is not implemented here: "
+                                  "utils.visualization.save_detection_images(generator, model, save_path) writes the images")
     n_img, n_class, cap = generator.size(), generator.num_classes(), int(max_detections)
     boxes = np.zeros((n_img, cap, 4), np.float64)
     scores = np.zeros((n_img, cap), np.float64)

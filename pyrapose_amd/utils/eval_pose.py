@@ -63,7 +63,7 @@ def _refine(dets, refine, depth, mask_out, K, models):
 
 
 def _scored_images(generator, predict_on_batch, decode_kw, K, refine, load_depth, models, gt_translation_scale, instances,
-                   depth_always=False):
+                   depth_always=False, draw=None):
     """The per-image loop of evaluate_add and evaluate_pose_metrics, once.  Per image with at least one label: predict, decode
     (pose_decode.poses_from_outputs with threeD_boxes and the keywords of `decode_kw`, its seed plus the image index), keep the
     detections of annotated classes (the reference only scores those, linemod_eval.py:327-329), optionally refine them, and
@@ -71,11 +71,15 @@ def _scored_images(generator, predict_on_batch, decode_kw, K, refine, load_depth
     load_depth: None, or index -> depth image, called once per image where a detection survived the class filter (with
     depth_always: on every labelled image, and `refine` then also sees an empty detection list, as evaluate_add has it).
     Yields (index, labels, anno, Kc, depth or None, mask, pairs_by_class) for every such image, pairs_by_class =
-    [(cls, [(det, annotation index), ...])] with classes ascending and no empty class."""
+    [(cls, [(det, annotation index), ...])] with classes ascending and no empty class.
+    draw: None, or dict(save_path, every=1, bgr=True): every such image (every `every`-th index) is also written to
+    save_path/{index}.png with the cuboid wireframes of its annotations and of the detections that are scored
+    (visualization.save_pose_image, one device pass); what is yielded does not change."""
     kw = dict(decode_kw)
     threeD_boxes, seed = kw.pop("threeD_boxes"), kw.pop("seed")
     for index in range(generator.size()):
-        image = generator.preprocess_image(generator.load_image(index))
+        raw_image = generator.load_image(index)
+        image = generator.preprocess_image(raw_image.copy() if draw is not None else raw_image)
         image, _scale = generator.resize_image(image)
         anno = generator.load_annotations(index)
         if len(anno["labels"]) < 1:
@@ -97,12 +101,15 @@ def _scored_images(generator, predict_on_batch, decode_kw, K, refine, load_depth
             pairs = _class_pairs([d for d in dets if d["cls"] == cls], cls, labels, anno, gt_translation_scale, instances)
             if pairs:
                 pairs_by_class.append((cls, pairs))
+        if draw is not None:
+            from . import visualization
+            visualization.save_pose_image(draw, index, raw_image, dets, anno, threeD_boxes, Kc, gt_translation_scale)
         yield index, labels, anno, Kc, depth, mask, pairs_by_class
 
 
 def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_diameters, K=None, threshold=0.5, min_votes=10,
                  symmetric_classes=(), gt_translation_scale=0.001, seed=0, refine=None, load_depth=None, weighting=None,
-                 instances=None):
+                 instances=None, draw=None):
     """generator: load_image / preprocess_image / resize_image / load_annotations / size() (preprocessing/generator.py);
     predict_on_batch: the prediction model's method (x [1,H,W,3] -> [boxes3D, scores, mask]);
     threeD_boxes [C,8,3], model_points: list of [n_c,3], model_diameters [C] -- all in the unit of the estimated translation
@@ -115,7 +122,8 @@ def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_
     pose_decode.poses_from_outputs on every RANSAC pose (before the optional ICP).  instances: None (one pose per class, scored
     against the first annotation of the class, as the reference does), or the dict of poses_from_outputs: poses are decoded per
     object instance, matched per class to all annotations of that class (match_instances), every matched pair is scored as the
-    single pair is otherwise, trueDets counts matched pairs and each error tuple gains (instance, gt).  Returns dict(allPoses, trueDets, truePoses, recall, detections, recall_all, detections_all, errors) with the
+    single pair is otherwise, trueDets counts matched pairs and each error tuple gains (instance, gt).  draw: None, or dict(save_path, every=1): one
+    overlay PNG per scored image (_scored_images); nothing else changes.  Returns dict(allPoses, trueDets, truePoses, recall, detections, recall_all, detections_all, errors) with the
     reference's 1-based class indexing."""
     C = len(model_diameters)
     if K is None:
@@ -126,7 +134,7 @@ def evaluate_add(generator, predict_on_batch, threeD_boxes, model_points, model_
     # depth only serves the refinement here, which runs on every labelled image
     for index, labels, anno, _Kc, _depth, _mask, pairs_by_class in _scored_images(
             generator, predict_on_batch, decode_kw, K, refine, load_depth if refine is not None else None, model_points,
-            gt_translation_scale, instances, depth_always=True):
+            gt_translation_scale, instances, depth_always=True, draw=draw):
         for lab in labels:
             allPoses[lab + 1] += 1
         for cls, pairs in pairs_by_class:
@@ -158,7 +166,7 @@ BOP_PIXELS = tuple(5 * k for k in range(1, 11))
 def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, model_diameters, load_depth, K, threshold=0.5, min_votes=10,
                           delta=0.3, tau=20.0, vsd_threshold=0.3, cost_type="step", symmetric_classes=(), gt_translation_scale=0.001,
                           depth_scale=1000.0, seed=0, refine=None, weighting=None, instances=None, symmetries=None, bop_vsd=None,
-                          mask_metrics=None):
+                          mask_metrics=None, draw=None):
     """The metric block of tless_eval.py:470-725 (also in occlusion_eval.py / ycbv_eval.py / homebrewed_eval.py) on top of the
     loop of evaluate_add: per detected, annotated class, the rotation / translation errors re / te (correct when re < 5 deg
     and te < 0.05), the reprojection error (< 5 px), VSD against the image's depth (< vsd_threshold) and ADD (ADI for
@@ -190,6 +198,7 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
     result gains mask_counts [T,C,3] (tp, fp, fn over all scored images), mask_iou [T,C] and mask_miou [T].
     Annotations are not dropped from allPoses by their visible fraction (BOP keeps those of at least 10 %): filter in the
     generator, on scene_gt_info.json or on pose_error.visib_fract_batch.
+    draw: None, or dict(save_path, every=1): one overlay PNG per scored image (_scored_images); nothing else changes.
     Returns dict(allPoses, trueDets, less5, rep_less5, vsd_less_t, add_less [len(ADD_FRACTIONS), C+1], add_fractions, the
     matching rates (counter / allPoses) and errors: one dict per scored detection); index = class id + 1 as in evaluate_add."""
     C = len(model_diameters)
@@ -221,7 +230,7 @@ def evaluate_pose_metrics(generator, predict_on_batch, threeD_boxes, models, mod
     decode_kw = dict(threeD_boxes=threeD_boxes, threshold=threshold, min_votes=min_votes, seed=seed, weighting=weighting)
     refine = None if refine is None else dict(refine, depth_scale=depth_scale)
     for index, labels, anno, Kc, depth, mask_out, pairs_by_class in _scored_images(
-            generator, predict_on_batch, decode_kw, K, refine, load_depth, models, gt_translation_scale, instances):
+            generator, predict_on_batch, decode_kw, K, refine, load_depth, models, gt_translation_scale, instances, draw=draw):
         for lab in labels:
             out["allPoses"][lab + 1] += 1
         if mask_metrics is not None:
