@@ -1251,6 +1251,47 @@ int pp_draw_overlay_u8(pp_ctx* ctx, int B, int H, int W, const unsigned char* im
                        const int* image_offsets, int n_total, const unsigned char* ids, const int* palette, int id_mode,
                        int outline_width);
 
+/* ---- connected components: the mask head's planes, or an id image, to instance labels and masks (cc.hip) ----
+ * The step between a class plane and instance masks, which the reference's area clustering hands to a PCL binary (encode_area,
+ * annotate_val_LineMOD.py:88-130; its point-cloud smoothness condition is not restated).  Integers only: every output is a
+ * pure function of the inputs, byte for byte the numpy restatement (tests/cc_np.py), whose labels are pinned to
+ * scipy.ndimage.label (tests/test_cc_cpu.py).  Parity with cv2.connectedComponents, which numbers differently, is not pinned.
+ *
+ * pp_cc_label: N planes in one call, no host synchronisation (capturable in a graph).
+ *   in   planes [N,H,W] uint8 (device); connectivity 4 | 8; mode PP_CC_BINARY: a non-zero byte is foreground and any two
+ *        adjacent foreground pixels connect; PP_CC_VALUE: two adjacent pixels connect iff their bytes are equal and non-zero
+ *        (an instance-id image, an arg-max class image); weight [N,H,W] int32 >= 0 (device) or NULL; max_components M.
+ *   out  labels [N,H,W] int32: 0 on background; the components of a plane are numbered 1 .. n in the raster order
+ *        (smallest y W + x) of their first pixels, whatever M is.
+ *        counts [N] int32: n, also where n > M.
+ *        stats [N,M,6] int32: area, x_min, y_min, x_max, y_max (inclusive), value (the component's byte in value mode, 1 in
+ *        binary mode) of component k + 1 in row k; rows k >= min(n, M) are zero.
+ *        sums [N,M,3] int64: the sums of x, of y and of weight over the component's pixels (0 without weight), rows as in stats.
+ *   Launches: a workgroup per 32 x 32 tile labels its tile in LDS (minimum over the compatible neighbours, pointer jumping,
+ *   until a round changes nothing) and writes each pixel the plane index of its tile-local root; a thread per pixel beside a
+ *   tile seam joins the trees across it (atomicMin of the smaller root into the larger); every pixel then takes its root, which
+ *   is the component's first raster pixel; one workgroup per plane scans the root flags in chunks with a carry; a last pass
+ *   writes labels = rank of the root + 1 and folds the statistics with integer atomics.  No loop waits for another workgroup.
+ *   Every data-dependent loop counts its steps against a bound from the sizes (1024 rounds of a tile, H W steps of a chase, H W
+ *   retries of a union); one that reaches it stops and sets a bit in the error word, the first int32 of the workspace, which
+ *   the call zeroes first: 1 the tile pass, 2 a chase, 4 a union.  The call cannot see the word without waiting for the device,
+ *   so it is the caller who reads it, after the stream has drained; the outputs of a call whose word is not 0 are undefined.
+ *   Workspace: a(4) + 2 a(4 N H W) bytes, a(b) = b rounded up to a multiple of 256: the error word, the parents, the ranks;
+ *   256-byte aligned.
+ *   Errors before anything is launched: N < 1, H or W < 1, H W >= 2^31, H > 32 * 65535: PP_ERR_SHAPE; connectivity, mode,
+ *   max_components outside 1..65535, a null planes / workspace / output, workspace_bytes too small or misaligned: PP_ERR_ARG.
+ *
+ * pp_cc_select: masks [S,H,W] uint8 (device), masks[s] = (labels[slot_plane[s]] == slot_label[s]) as 0 / 1, one pixel pass,
+ *   four pixels per dword store where H W is a multiple of 4.  labels [N,H,W] int32, slot_plane / slot_label [S] int32 (device).
+ *   A slot with slot_plane outside 0 .. N - 1 or slot_label <= 0 gives a zero mask and reads no label plane; so does a label
+ *   above its plane's count.  S = 0 does nothing.  Errors: the shape rules above and S < 0: PP_ERR_SHAPE; null: PP_ERR_ARG. */
+#define PP_CC_BINARY 0
+#define PP_CC_VALUE 1
+int pp_cc_label(pp_ctx* ctx, int N, int H, int W, const unsigned char* planes, int connectivity, int mode, const int* weight,
+                int max_components, void* workspace, size_t workspace_bytes, int* labels, int* counts, int* stats, long long* sums);
+int pp_cc_select(pp_ctx* ctx, int N, int H, int W, const int* labels, int S, const int* slot_plane, const int* slot_label,
+                 unsigned char* masks);
+
 #ifdef __cplusplus
 }
 #endif

@@ -230,6 +230,8 @@ _SIGS = {
     "pp_depth_inpaint_workspace_bytes": (_sz, [_i, _i, _i]),
     "pp_depth_inpaint": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _i, _p, _sz, _p, _p, _p, _p]),
     "pp_draw_overlay_u8": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _i, _i]),
+    "pp_cc_label": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _i, _p, _sz, _p, _p, _p, _p]),
+    "pp_cc_select": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _p]),
 }
 
 EXPORTS = sorted(_SIGS)

@@ -1801,3 +1801,68 @@ def draw_overlay(ctx, images, prims, image_offsets, ids=None, palette=None, fill
     check(lib.pp_draw_overlay_u8(ctx.handle, B, H, W, _ptr(images), _ptr(out), _ptr(prims) if n else None, _ptr(image_offsets), n,
                                  _ptr(ids), _ptr(palette), id_mode, max(outline, 1)), ctx.handle, "pp_draw_overlay_u8")
     return out
+
+
+CC_TILE = 32                  # pixels per side of a workgroup's tile of pp_cc_label
+CC_MAX_COMPONENTS = 65535
+CC_MODES = ("binary", "value")  # in the ABI's order (PP_CC_BINARY, PP_CC_VALUE)
+CC_ERRORS = {1: "the tile pass", 2: "a chase", 4: "a union"}  # bits of the error word
+
+
+def cc_workspace_bytes(N, H, W):
+    """the workspace of pp_cc_label: the error word, the parents and the ranks, each rounded up to 256 bytes"""
+    return 256 + 2 * ((4 * N * H * W + 255) // 256 * 256)
+
+
+def cc_label(ctx, planes, connectivity=8, mode="binary", weight=None, max_components=256, check=False):
+    """Connected components of N planes in one call (pp_cc_label, the rule in include/pyrapose_hip.h): cuda tensors planes uint8
+    [N,H,W] and weight int32 [N,H,W] (>= 0) or None; connectivity 4 | 8; mode 'binary' (non-zero = foreground) | 'value' (equal
+    non-zero bytes connect); max_components M in 1..65535 -> dict: labels int32 [N,H,W] (0 = background, 1 .. n in the raster
+    order of the components' first pixels: scipy.ndimage.label's numbering, never capped), counts int32 [N] (n, also beyond M),
+    stats int32 [N,M,6] (area, x_min, y_min, x_max, y_max, value), sums int64 [N,M,3] (sum_x, sum_y, sum_w), rows from
+    min(n, M) on zero, and error int32 [1]: the kernels' error word, 0 unless a loop reached its bound.  No host
+    synchronisation; check=True reads the word here (one) and raises RuntimeError on a set bit."""
+    what = "cc_label"  # (the scalars first: their refusals need no device tensor)
+    if connectivity not in (4, 8):
+        raise ValueError("%s: connectivity %r, need 4 or 8" % (what, connectivity))
+    if mode not in CC_MODES:
+        raise ValueError("%s: mode %r, need %s" % (what, mode, " | ".join(CC_MODES)))
+    M = int(max_components)
+    if M != max_components or not 1 <= M <= CC_MAX_COMPONENTS:
+        raise ValueError("%s: max_components %r, need an integer in 1..%d" % (what, max_components, CC_MAX_COMPONENTS))
+    planes, N, H, W = _mask_stack(what, "planes", planes)
+    if N < 1:
+        raise ValueError("%s: planes must hold at least one plane, got %s" % (what, list(planes.shape)))
+    weight = _arg(what, "weight", weight, _I32, (N, H, W), optional=True)
+    nbytes = cc_workspace_bytes(N, H, W)
+    ws = _workspace(nbytes)
+    out = dict(labels=_out(planes, (N, H, W), _I32), counts=_out(planes, (N,), _I32), stats=_out(planes, (N, M, 6), _I32),
+               sums=_out(planes, (N, M, 3), _I64))
+    check_status(lib.pp_cc_label(ctx.handle, N, H, W, _ptr(planes), int(connectivity), CC_MODES.index(mode), _ptr(weight), M, _ptr(ws),
+                                 nbytes, _ptr(out["labels"]), _ptr(out["counts"]), _ptr(out["stats"]), _ptr(out["sums"])),
+                 ctx.handle, "pp_cc_label")
+    out["error"] = ws[:4].view(_I32)
+    if check:
+        word = int(out["error"].item())
+        if word:
+            raise RuntimeError("%s: %s reached its iteration bound (error word %d)" %
+                               (what, ", ".join(v for k, v in CC_ERRORS.items() if word & k), word))
+    return out
+
+
+def cc_select(ctx, labels, slot_plane, slot_label):
+    """Label planes to instance masks (pp_cc_select): cuda int32 tensors labels [N,H,W], slot_plane [S], slot_label [S] ->
+    masks uint8 [S,H,W], masks[s] = (labels[slot_plane[s]] == slot_label[s]) as 0 / 1.  A slot with slot_plane < 0 (or past the
+    last plane) or slot_label <= 0 is padding: an all-zero mask, no label plane read."""
+    what = "cc_select"
+    labels = _arg(what, "labels", labels, _I32, (None, None, None))
+    N, H, W = (int(s) for s in labels.shape)
+    if N < 1 or H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError("%s: labels needs N, H, W >= 1 and H * W < 2^31, got %s" % (what, list(labels.shape)))
+    slot_plane = _arg(what, "slot_plane", slot_plane, _I32, (None,))
+    S = int(slot_plane.shape[0])
+    slot_label = _arg(what, "slot_label", slot_label, _I32, (S,))
+    masks = _out(labels, (S, H, W), _U8)
+    check_status(lib.pp_cc_select(ctx.handle, N, H, W, _ptr(labels), S, _ptr(slot_plane), _ptr(slot_label), _ptr(masks)), ctx.handle,
+                 "pp_cc_select")
+    return masks
