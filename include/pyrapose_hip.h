@@ -884,6 +884,64 @@ int pp_farthest_points_f64(pp_ctx* ctx, int n_model, int n_total, const double* 
                            int k, int rule, const double* min_dist, const int* start, void* workspace, size_t workspace_bytes,
                            int* index);
 
+/* ---- mesh geometry: face normals, area, volume, vertex normals, surface samples (csrc/mesh.hip) --------------------------
+ * What a mesh that brings no normals and too few vertices to stand for its surface needs before it can be rendered with phong
+ * shading or measured by the point-set metrics.  float64; every product and sum rounded on its own; squared lengths and dot
+ * products associate as (x x' + y y') + z z'.  The reference computes none of this and no library that does was at hand: the
+ * rules are this project's, restated in tests/mesh_np.py, which every output is bit-identical to, as it is from run to run
+ * ("restated, unpinned").  No float atomics; integer atomics never decide a result.  Inputs must be finite.
+ * Common to the three: pts [n_v,3], faces [n_f,3] int32, 1 <= n_v, n_f <= 2^22 and 1 <= n_samples <= 2^24 (PP_ERR_SHAPE
+ * otherwise); null pointers (but those named optional) and a workspace shorter than the entry point's *_workspace_bytes (0: a
+ * refused size) are PP_ERR_ARG; both are checked before anything is launched.  No host synchronisation, no workgroup waits on
+ * another, every loop is bounded by the sizes.  A face that names a vertex outside 0..n_v-1 counts as degenerate everywhere:
+ * zero normal, zero area, in no adjacency list, never sampled; its points are never read.
+ *
+ * pp_mesh_face_geometry_f64:
+ *   normal [n_f,3] = (p1 - p0) x (p2 - p0), not normalised; area2 [n_f] = its length by sqrt, twice the face's area
+ *   totals [8]     = {sum area2, sum p0 . normal (six times the signed volume), sum area2 (p0 + p1 + p2) [3] (the numerator
+ *                    of the area-weighted centroid: divide by 3 totals[0]), max area2 (exact), 0, 0}
+ *                    The sums run in one fixed order: chunks of 256 faces in face order, each by the halving tree of the VSD
+ *                    tile sums (lane t += lane t + 128, + 64, ... + 1; a missing face adds +0.0), then the chunks in order.
+ *   status [1]     = int32: bit 0 a face names a vertex out of range, bit 1 every area is zero
+ *
+ * pp_mesh_vertex_normals_f64: face_normal and totals as pp_mesh_face_geometry_f64 wrote them for the same mesh.
+ *   vnormal [n_v,3]     = the sum of the normals of the vertex's incident faces, added one by one in ascending face index (a
+ *                         face that lists the vertex twice is added twice), divided by the sum's length; (0,0,0) for a zero
+ *                         sum.  Area weighting: the normals are not normalised first.  outward != 0: every normal is negated
+ *                         when totals[1] < 0 (inward winding); the sign is read on the device.
+ *   adj_offsets [n_v+1] = int32, CSR: the faces of vertex v are adj_faces[adj_offsets[v] .. adj_offsets[v+1])
+ *   adj_faces [3 n_f]   = int32, ascending within each vertex; entries past adj_offsets[n_v] are -1
+ *   The ascending order is reached by ranking each segment after an atomic fill: cost sum over the vertices of valence^2,
+ *   spread over valence lanes each; the result does not depend on the order the atomics land in.
+ *
+ * pp_mesh_sample_surface_f64: n_samples points uniform by area.  face_normal, area2, totals as above.
+ *   q_f = floor(ldexp(area2_f, 39 - ilogb(totals[5]))), so the largest lies in [2^39, 2^40); cum = the inclusive integer scan.
+ *   Sample i: word(j) = splitmix64(splitmix64(4 seed + j) + i) mod 2^64; u = word(0) in mode 0; in mode 1 the Weyl sequence
+ *   u = splitmix64(4 seed + 3) + i 0x9E3779B97F4A7C15 mod 2^64 (low discrepancy over the area).  The face is the first f with
+ *   cum[f] > high 64 bits of u * cum[n_f-1].  A face with q_f = 0 -- one that covers less than 2^-39 of the largest face -- is
+ *   never chosen: that is the rule.  r1, r2 = (word(1) >> 11) 2^-53, (word(2) >> 11) 2^-53; s = sqrt(r1); a = 1 - s,
+ *   b = s (1 - r2), c = s r2.
+ *   Outputs, each skipped when NULL:
+ *     points [n,3]        = (a p0 + b p1) + c p2 per coordinate
+ *     face [n]            = int32
+ *     bary [n,3]          = (a, b, c)
+ *     normals [n,3]       = the face's normal / area2, negated when outward != 0 and totals[1] < 0
+ *     attr_out [n,n_attr] = the same blend of the rows of attr [n_v,n_attr], 1 <= n_attr <= 8 (PP_ERR_SHAPE otherwise; attr
+ *                           must not be NULL then); n_attr is not looked at when attr_out is NULL
+ *   When every area is zero (status bit 1) every output is zero and face is -1.  mode other than 0 or 1: PP_ERR_ARG. */
+size_t pp_mesh_face_geometry_workspace_bytes(int n_f);
+int pp_mesh_face_geometry_f64(pp_ctx* ctx, int n_v, int n_f, const double* pts, const int* faces, void* workspace,
+                              size_t workspace_bytes, double* normal, double* area2, double* totals, int* status);
+size_t pp_mesh_vertex_normals_workspace_bytes(int n_v, int n_f);
+int pp_mesh_vertex_normals_f64(pp_ctx* ctx, int n_v, int n_f, const int* faces, const double* face_normal, const double* totals,
+                               int outward, void* workspace, size_t workspace_bytes, double* vnormal, int* adj_offsets,
+                               int* adj_faces);
+size_t pp_mesh_sample_surface_workspace_bytes(int n_f);
+int pp_mesh_sample_surface_f64(pp_ctx* ctx, int n_v, int n_f, const double* pts, const int* faces, const double* face_normal,
+                               const double* area2, const double* totals, int n_samples, unsigned long long seed, int mode,
+                               int outward, int n_attr, const double* attr, void* workspace, size_t workspace_bytes,
+                               double* points, int* face, double* bary, double* normals, double* attr_out);
+
 /* ---- 2-D detection average precision (csrc/det_eval.hip) -----------------------------------------------------------------
  * utils/eval.py:147-235 (evaluate, the 'mAP' of callbacks/eval.py) and BOP's detection score (COCO AP with ignored ground
  * truth) on the device: greedy matching per image, then true / false positive scans, precision envelope and the integral per

@@ -232,6 +232,12 @@ _SIGS = {
     "pp_draw_overlay_u8": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _i, _i]),
     "pp_cc_label": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _i, _p, _sz, _p, _p, _p, _p]),
     "pp_cc_select": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _p]),
+    "pp_mesh_face_geometry_workspace_bytes": (_sz, [_i]),
+    "pp_mesh_face_geometry_f64": (_i, [_p, _i, _i, _p, _p, _p, _sz, _p, _p, _p, _p]),
+    "pp_mesh_vertex_normals_workspace_bytes": (_sz, [_i, _i]),
+    "pp_mesh_vertex_normals_f64": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _sz, _p, _p, _p]),
+    "pp_mesh_sample_surface_workspace_bytes": (_sz, [_i]),
+    "pp_mesh_sample_surface_f64": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _i, C.c_ulonglong, _i, _i, _i, _p, _p, _sz, _p, _p, _p, _p, _p]),
 }
 
 EXPORTS = sorted(_SIGS)

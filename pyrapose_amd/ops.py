@@ -1866,3 +1866,97 @@ def cc_select(ctx, labels, slot_plane, slot_label):
     check_status(lib.pp_cc_select(ctx.handle, N, H, W, _ptr(labels), S, _ptr(slot_plane), _ptr(slot_label), _ptr(masks)), ctx.handle,
                  "pp_cc_select")
     return masks
+
+
+MESH_THREADS = 256          # workgroup size of every kernel of csrc/mesh.hip = faces per chunk of the fixed-order float sums
+MESH_SCAN_CHUNK = 1024      # quantised areas per workgroup of pp_mesh_sample_surface_f64's integer scan
+MESH_MAX_ELEMS = 1 << 22    # vertices and faces at most
+MESH_MAX_SAMPLES = 1 << 24
+MESH_MAX_ATTR = 8
+MESH_MODES = {"random": 0, "weyl": 1}
+MESH_SAMPLE_OUTPUTS = ("points", "face", "bary", "normals", "attr_out")  # in the ABI's order
+
+
+def _mesh_args(what, pts, faces):
+    pts = _arg(what, "pts", pts, _F64, (None, 3))
+    faces = _arg(what, "faces", faces, _I32, (None, 3))
+    n_v, n_f = int(pts.shape[0]), int(faces.shape[0])
+    if not (1 <= n_v <= MESH_MAX_ELEMS and 1 <= n_f <= MESH_MAX_ELEMS):
+        raise ValueError("%s: need 1..2^22 vertices and faces, got %d and %d" % (what, n_v, n_f))
+    return pts, faces, n_v, n_f
+
+
+def mesh_face_geometry(ctx, pts, faces):
+    """Per-face and whole-mesh geometry (pp_mesh_face_geometry_f64, the rules in include/pyrapose_hip.h): cuda float64 pts
+    [n_v,3], int32 faces [n_f,3] -> dict: normal float64 [n_f,3] (the cross product, not normalised), area2 [n_f] (its length),
+    totals [8] = (sum area2, six signed volumes, the centroid's numerator [3], max area2, 0, 0), status int32 [1] (bit 0: a
+    face names a vertex out of range and counts as degenerate; bit 1: every area is zero).  Nothing is read back here."""
+    what = "mesh_face_geometry"
+    pts, faces, n_v, n_f = _mesh_args(what, pts, faces)
+    nbytes = lib.pp_mesh_face_geometry_workspace_bytes(n_f)
+    ws = _workspace(nbytes)
+    out = dict(normal=_out(pts, (n_f, 3)), area2=_out(pts, (n_f,)), totals=_out(pts, (8,)), status=_out(pts, (1,), _I32))
+    check(lib.pp_mesh_face_geometry_f64(ctx.handle, n_v, n_f, _ptr(pts), _ptr(faces), _ptr(ws), nbytes, _ptr(out["normal"]),
+                                        _ptr(out["area2"]), _ptr(out["totals"]), _ptr(out["status"])), ctx.handle, "pp_mesh_face_geometry_f64")
+    return out
+
+
+def _mesh_geom(what, geom, n_f):
+    if not isinstance(geom, dict):
+        raise ValueError("%s: geom must be what mesh_face_geometry returned for this mesh" % what)
+    return (_arg(what, "geom['normal']", geom.get("normal"), _F64, (n_f, 3)), _arg(what, "geom['area2']", geom.get("area2"), _F64, (n_f,)),
+            _arg(what, "geom['totals']", geom.get("totals"), _F64, (8,)))
+
+
+def mesh_vertex_normals(ctx, n_v, faces, geom, outward=True):
+    """Area-weighted vertex normals and the vertex-to-face adjacency (pp_mesh_vertex_normals_f64): n_v vertices, cuda int32
+    faces [n_f,3], geom = mesh_face_geometry's dict of the same mesh -> (vnormal float64 [n_v,3], adj_offsets int32 [n_v+1],
+    adj_faces int32 [3 n_f]: the faces of vertex v ascending in adj_faces[adj_offsets[v]:adj_offsets[v+1]], -1 past the last).
+    outward: all normals negated when the mesh's signed volume is negative; the sign is read on the device."""
+    what = "mesh_vertex_normals"
+    faces = _arg(what, "faces", faces, _I32, (None, 3))
+    n_v, n_f = int(n_v), int(faces.shape[0])
+    if not (1 <= n_v <= MESH_MAX_ELEMS and 1 <= n_f <= MESH_MAX_ELEMS):
+        raise ValueError("%s: need 1..2^22 vertices and faces, got %d and %d" % (what, n_v, n_f))
+    normal, _, totals = _mesh_geom(what, geom, n_f)
+    nbytes = lib.pp_mesh_vertex_normals_workspace_bytes(n_v, n_f)
+    ws = _workspace(nbytes)
+    vnormal, offsets, adj = _out(faces, (n_v, 3)), _out(faces, (n_v + 1,), _I32), _out(faces, (3 * n_f,), _I32)
+    check(lib.pp_mesh_vertex_normals_f64(ctx.handle, n_v, n_f, _ptr(faces), _ptr(normal), _ptr(totals), 1 if outward else 0, _ptr(ws), nbytes,
+                                         _ptr(vnormal), _ptr(offsets), _ptr(adj)), ctx.handle, "pp_mesh_vertex_normals_f64")
+    return vnormal, offsets, adj
+
+
+def mesh_sample_surface(ctx, pts, faces, geom, n_samples, seed=0, mode="random", outward=True, attr=None,
+                        want=("points", "face", "bary", "normals")):
+    """n_samples points uniform by area (pp_mesh_sample_surface_f64): pts, faces and geom as above; seed an integer (taken mod
+    2^64); mode 'random' (counter-based splitmix64 draws) | 'weyl' (a low-discrepancy sequence decides the face); attr: cuda
+    float64 [n_v,n_attr], 1 <= n_attr <= 8, blended like the points into 'attr_out'; want: which of points [n,3], face int32
+    [n], bary [n,3], normals [n,3] (the face's unit normal, outward as for the vertex normals) to compute ('attr_out' comes
+    with attr) -> dict of cuda tensors.  A mesh whose areas are all zero gives zeros and face = -1."""
+    what = "mesh_sample_surface"  # (the scalars first: their refusals need no device tensor)
+    if mode not in MESH_MODES:
+        raise ValueError("%s: mode %r, need random | weyl" % (what, mode))
+    n = int(n_samples)
+    if n != n_samples or not 1 <= n <= MESH_MAX_SAMPLES:
+        raise ValueError("%s: n_samples %r, need an integer in 1..2^24" % (what, n_samples))
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if any(w not in MESH_SAMPLE_OUTPUTS[:4] for w in want):
+        raise ValueError("%s: want must name some of %s, got %r" % (what, " | ".join(MESH_SAMPLE_OUTPUTS[:4]), want))
+    pts, faces, n_v, n_f = _mesh_args(what, pts, faces)
+    normal, area2, totals = _mesh_geom(what, geom, n_f)
+    n_attr = 0
+    if attr is not None:
+        attr = _arg(what, "attr", attr, _F64, (n_v, None))
+        n_attr = int(attr.shape[1])
+        if not 1 <= n_attr <= MESH_MAX_ATTR:
+            raise ValueError("%s: attr must hold 1..%d values per vertex, got %d" % (what, MESH_MAX_ATTR, n_attr))
+        want = want + ("attr_out",)
+    shapes = dict(points=((n, 3), _F64), face=((n,), _I32), bary=((n, 3), _F64), normals=((n, 3), _F64), attr_out=((n, n_attr), _F64))
+    out = {w: _out(pts, *shapes[w]) for w in MESH_SAMPLE_OUTPUTS if w in want}
+    nbytes = lib.pp_mesh_sample_surface_workspace_bytes(n_f)
+    ws = _workspace(nbytes)
+    check(lib.pp_mesh_sample_surface_f64(ctx.handle, n_v, n_f, _ptr(pts), _ptr(faces), _ptr(normal), _ptr(area2), _ptr(totals), n,
+                                         int(seed) & (2 ** 64 - 1), MESH_MODES[mode], 1 if outward else 0, n_attr, _ptr(attr), _ptr(ws), nbytes,
+                                         *[_ptr(out.get(w)) for w in MESH_SAMPLE_OUTPUTS]), ctx.handle, "pp_mesh_sample_surface_f64")
+    return out
